@@ -1,6 +1,6 @@
 """bench.py -- BASELINE.json's headline metric on the MI355X-native path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload wav2letter|jasper_large]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload wav2letter|jasper_large] [--dump-outputs DIR]
 
 N > 1 without WORLD_SIZE in the environment: this process touches no GPU and starts its own N ranks as a CHILD
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`, the role of train.py:1057-1073's mp.spawn), relays rank 0's
@@ -84,6 +84,8 @@ def parse_args(argv = None):
 			'with the wgrad side stream, whose time the line also reports), off for wav2letter (~110 launches, GPU-bound either way: +-0 measured, and the dominant kernel stays event-timed '
 			'inside the timed region) and for N > 1 (RCCL has not run under capture on this pool).  With graphs on, per-kernel HIP-event durations come from the second, eager pass')
 	ap.add_argument('--no-jasper-leg', action = 'store_true', help = 'skip the bounded BASELINE configs[4] leg (extra.jasper_large) of the default line')
+	ap.add_argument('--dump-outputs', metavar = 'DIR', default = None, help = 'after the timed steps, write what the last timed step computed as DIR/<name>.npy: its scalars (loss, loss_cur, entropy, grad_norm, skipped; '
+		'float64) and a fixed, seeded sample of the updated fp32 parameter arena (float32, with its indices in float64); under 64 MB in all.  Rank 0 only')
 	ap.add_argument('--launcher-dry-run', action = 'store_true', help = 'test hook: ranks only rendezvous (gloo, CPU tensors) and rank 0 prints a line; exercises the self-launch path without a GPU')
 	args = ap.parse_args(argv)
 	if args.dtype is None:
@@ -554,7 +556,7 @@ def dry_run_rank(args):
 	t = torch.tensor([float(rank + 1)])
 	t0 = time.perf_counter()
 	dist.all_reduce(t)
-	dist.barrier()
+	dist.monitored_barrier()  # (gloo's host barrier: dist.barrier() would initialise the GPU runtime in each of these CPU-only ranks)
 	el = torch.tensor([time.perf_counter() - t0], dtype = torch.float64)
 	dist.all_reduce(el, op = dist.ReduceOp.MAX)
 	backend = dist.get_backend()
@@ -743,9 +745,34 @@ def predicted_comm(engine, world, step_s):
 		return dict(error = f'{type(e).__name__}: {e}')
 
 
-def measure(args, device, rank, world, use_dist, dist_info, fence, probe = None):
+DUMP_PARAM_SAMPLE = 1 << 21  # parameters in --dump-outputs' sample of the arena: 8 MB of values + 16 MB of float64 indices
+
+
+def dump_outputs(out_dir, res, flat):
+	"""--dump-outputs: what a caller of the timed path holds after its last step -- the step's result scalars (train.train_step's
+	dict) and the updated parameters (the fp32 arena, sampled at DUMP_PARAM_SAMPLE positions drawn from a fixed seed: the same
+	positions for the same model).  Returns the names written."""
+	import numpy as np
+	import torch
+	os.makedirs(out_dir, exist_ok = True)
+	arrays = {}
+	for k, v in res.items():
+		if v is None:
+			continue
+		arrays[k] = np.asarray(v.detach().double().cpu().numpy() if torch.is_tensor(v) else float(bool(v)), dtype = np.float64)
+	n = flat.numel
+	idx = np.arange(n) if n <= DUMP_PARAM_SAMPLE else np.unique(np.random.default_rng(0).integers(0, n, size = DUMP_PARAM_SAMPLE))
+	arrays['params_sample'] = flat.data[torch.from_numpy(idx).to(flat.data.device)].cpu().numpy().astype(np.float32)
+	arrays['params_sample_index'] = idx.astype(np.float64)
+	assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+	for k, a in arrays.items():
+		np.save(os.path.join(out_dir, f'{k}.npy'), a)
+	return sorted(arrays)
+
+
+def measure(args, device, rank, world, use_dist, dist_info, fence, probe = None, dump_dir = None):
 	"""One workload on this rank: W warm-up steps (+ the untimed priming of the step graphs), K timed steps between two fences, the
-	second (event-timed, eager) pass.  Returns (the JSON line as a dict -- rank 0 only, else None --, rank 0's launch sequence of one step)."""
+	second (event-timed, eager) pass.  dump_dir: --dump-outputs of the timed region's last step (taken before the second pass steps on).  Returns (the JSON line as a dict -- rank 0 only, else None --, rank 0's launch sequence of one step)."""
 	import torch
 	import torch.distributed as dist
 	import convasr_amd as ca
@@ -763,6 +790,7 @@ def measure(args, device, rank, world, use_dist, dist_info, fence, probe = None)
 	# (the dominant kernel included) then comes from the second pass, which runs eagerly on one stream
 	elapsed, audio, flops, last, kt, sequence, step = run_timed(args, wl, engine, world, fence, time_main_kernel = not args.no_kernel_timer and rank == 0 and not args.side_stream and not graphed,
 		on_warm = (lambda: flat.loss_scaler.current[7].item()) if flat.loss_scaler is not None else None, probe = probe)
+	dumped = dump_outputs(dump_dir, last, flat) if dump_dir else None
 	device_state = probe.summary() if probe is not None else None
 	overflows0 = run_timed.warm_value or 0.0  # the scaler's overflow count when the timed region starts (warm-up overflows are not the timed region's)
 	exposed = engine.exposed_comm_ms() if use_dist else None
@@ -863,6 +891,8 @@ def measure(args, device, rank, world, use_dist, dist_info, fence, probe = None)
 				gflop_per_padded_audio_s_fwd = round(flops[0] / audio[1] / 1e9, 2), gflop_per_step_fwd_bwd = round((flops[0] + flops[1]) / args.steps / 1e9, 1),
 				batch_shapes_in_timed_region = len({tuple(wl.batches[wl.batch_of(args.warmup + i)][0].shape) for i in range(args.steps)}),
 				note = 'value counts the utterances\' own durations; the kernels also compute the padded frames (temporal_mask = False, like the reference): whole_step_frac is over the padded FLOPs')
+		if dumped:
+			line['dumped_outputs'] = dict(dir = os.path.abspath(dump_dir), arrays = dumped, step = args.warmup + args.steps - 1)
 	del engine, last, flat, step
 	wl.release()
 	torch.cuda.empty_cache()
@@ -928,7 +958,7 @@ def main(argv = None):
 		torch.cuda.synchronize()
 
 	probe = DeviceProbe(device) if rank == 0 and os.environ.get('CONVASR_NO_PROBE') != '1' else None  # (CONVASR_NO_PROBE=1: A/B hook) host-side sampler of the card's clock / power / PPT residency (sysfs + librocm_smi64 through ctypes: no GPU call)
-	line, sequence = measure(args, device, rank, world, use_dist, dist_info, fence, probe)
+	line, sequence = measure(args, device, rank, world, use_dist, dist_info, fence, probe, dump_dir = args.dump_outputs if rank == 0 else None)
 	if use_dist:
 		dist.destroy_process_group()
 	if rank == 0:

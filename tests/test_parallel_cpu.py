@@ -79,7 +79,7 @@ def _worker(rank, world, port, out):
 	engine.finish_gradient_sync()
 	for p in params:
 		assert torch.allclose(p.grad, torch.full_like(p, 2 * expect)), (rank, p.grad.flatten()[:4])
-	dist.barrier()
+	dist.monitored_barrier()  # (gloo's host barrier: dist.barrier() would initialise the GPU runtime in every worker of this CPU test)
 	dist.destroy_process_group()
 	out.put((rank, 'ok'))
 
@@ -249,6 +249,32 @@ def test_bench_launches_its_own_ranks_world2():
 	out = json.loads(lines[0])
 	assert out['n_gpus'] == 2 and out['steps'] == 4 and out['warmup'] == 1
 	assert out['dist'] == dict(backend = 'gloo', world_size = 2, launcher = True)
+
+
+def test_bench_dump_outputs_writes_the_step_result_and_a_fixed_parameter_sample(tmp_path):
+	"""bench.py --dump-outputs DIR: the last timed step's result scalars in float64 and a seeded sample of the fp32 parameter arena,
+	the same positions for the same arena size, under 64 MB in all."""
+	import sys
+	import types
+	import numpy as np
+	set_by_bench = 'HSA_ENABLE_IPC_MODE_LEGACY' not in os.environ
+	import bench  # (conftest.py puts the repository root on sys.path)
+	if set_by_bench:  # (bench.py sets it for its own GPU runs at import: the rest of this session keeps its environment)
+		os.environ.pop('HSA_ENABLE_IPC_MODE_LEGACY', None)
+	assert bench.parse_args(['--dump-outputs', str(tmp_path)]).dump_outputs == str(tmp_path) and bench.parse_args([]).dump_outputs is None
+	res = dict(loss = torch.tensor(1.25), loss_cur = torch.tensor(2.5), entropy = torch.tensor(0.5), grad_norm = None, skipped = torch.tensor(False))
+	for n, name in ((1000, 'small'), (3 * bench.DUMP_PARAM_SAMPLE, 'large')):
+		flat = types.SimpleNamespace(numel = n, data = torch.arange(n, dtype = torch.float32))
+		names = bench.dump_outputs(str(tmp_path / name), res, flat)
+		assert names == ['entropy', 'loss', 'loss_cur', 'params_sample', 'params_sample_index', 'skipped']
+		got = {k: np.load(str(tmp_path / name / f'{k}.npy')) for k in names}
+		assert got['loss'].dtype == np.float64 and float(got['loss']) == 1.25 and float(got['skipped']) == 0.0
+		assert got['params_sample'].dtype == np.float32 and got['params_sample_index'].dtype == np.float64
+		np.testing.assert_array_equal(got['params_sample'], got['params_sample_index'].astype(np.float32))
+		assert sum(a.nbytes for a in got.values()) <= 64 << 20
+	assert len(got['params_sample']) > bench.DUMP_PARAM_SAMPLE // 2
+	again = bench.dump_outputs(str(tmp_path / 'again'), res, types.SimpleNamespace(numel = 3 * bench.DUMP_PARAM_SAMPLE, data = torch.zeros(3 * bench.DUMP_PARAM_SAMPLE)))
+	np.testing.assert_array_equal(np.load(str(tmp_path / 'again' / 'params_sample_index.npy')), got['params_sample_index'])
 
 
 def test_bench_launcher_propagates_a_rank_failure():
