@@ -1,0 +1,461 @@
+// CTC prefix beam search without a language model: decoders.BeamSearchDecoder (decoders.py:19-55, ctcdecode.CTCBeamDecoder with
+// lm_path = None), train.py --decoder BeamSearchDecoder / --decoder-topk / --beam-width.  The semantics are normative in
+// include/convasr_hip.h and restated in float64 by tests/_ctc_beam_ref.py.
+//
+// One workgroup per utterance; the frame loop runs inside the kernel.  Per frame:
+//   1. P_t: radix select of the top-N classes (key = (descending lp, class)); sorted and cut only when cutoff_prob < 1.
+//   2. The current beams go into an LDS hash table keyed by their 64-bit prefix hash; every beam looks up its parent prefix there.
+//      When the parent is a current beam i and last(l_j) is in P_t, the extension l_i + last(l_j) is folded into l_j's own
+//      candidate and its bit in i's fold mask is set, so it is not a candidate of its own.
+//   3. Candidates (beam i, own or position p in P_t) are never materialised: a radix select over the 64-bit key of the candidate's
+//      score finds the W-th best (score recomputed each pass: one fp64 add, or the stored own score), then the exact ties at the
+//      boundary are resolved by the candidate key (rank << 14 | c + 1).  The selected ones (<= W) are compacted and bitonic-sorted
+//      by (score, key): that order is the next frame's ranking.
+//   4. A selected extension creates a node in the global arena (parent node, token); node id = t * W + rank, so the frame of a token
+//      is node / W.  The best topk beams are walked back once at the end.
+// Beam scores are fp64 (the log-probs are read as fp32): the selection boundary of a wide beam over hundreds of frames sits among
+// tens of thousands of candidates, and fp32 accumulation would reorder near-ties that the float64 restatement keeps apart.
+#include "common.h"
+
+#define BS_MAX_W 1024
+#define BS_MAX_N 128
+#define BS_MAX_C 8192
+#define BS_KEY_C_BITS 14  // candidate key = rank << 14 | (c + 1): c + 1 <= 8192 < 2^14, rank < 1024 -> 24 bits
+
+__host__ __device__ static inline int bs_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
+
+struct BsSel {
+	uint64_t P, M;       // resolved high bits of the boundary key / their mask
+	unsigned KP, KM;     // the same over the candidate key, among exact score ties
+	int need, full, all, tie;
+	int bucket, before, cnt;
+	int n, np, m, cut;   // beams, |P_t|, selected, cutoff length
+};
+
+struct BsLayout {
+	int W, NW, C, S, TB;        // beams, fold words per beam, classes, sort size, hash table size
+	size_t lpb, lpnb, tot, own_nb, own_nnb, own_s, hash, phash, su, plp;  // 8-byte arrays
+	size_t sel;                                                              // the selection state (BsSel)
+	size_t last, node, len, fold, sk, htab, pc, hist, pos;                   // 4- / 2-byte arrays
+	size_t bytes;
+};
+
+__host__ __device__ static inline BsLayout bs_layout(int W, int N, int C) {
+	BsLayout L;
+	L.W = W; L.NW = (N + 31) / 32; L.C = C;
+	L.S = bs_pow2(W > BS_MAX_N ? W : BS_MAX_N);
+	L.TB = bs_pow2(2 * W > 64 ? 2 * W : 64);
+	size_t o = 0;
+	L.lpb = o; o += 8 * (size_t)W;
+	L.lpnb = o; o += 8 * (size_t)W;
+	L.tot = o; o += 8 * (size_t)W;
+	L.own_nb = o; o += 8 * (size_t)W;
+	L.own_nnb = o; o += 8 * (size_t)W;
+	L.own_s = o; o += 8 * (size_t)W;
+	L.hash = o; o += 8 * (size_t)W;
+	L.phash = o; o += 8 * (size_t)W;
+	L.su = o; o += 8 * (size_t)L.S;
+	L.plp = o; o += 8 * (size_t)BS_MAX_N;
+	L.sel = o; o += (sizeof(BsSel) + 15) & ~(size_t)15;
+	L.last = o; o += 4 * (size_t)W;
+	L.node = o; o += 4 * (size_t)W;
+	L.len = o; o += 4 * (size_t)W;
+	L.fold = o; o += 4 * (size_t)W * L.NW;
+	L.sk = o; o += 4 * (size_t)L.S;
+	L.htab = o; o += 4 * (size_t)L.TB;
+	L.pc = o; o += 4 * (size_t)BS_MAX_N;
+	L.hist = o; o += 4 * 256;
+	L.pos = o; o += 2 * (size_t)C;
+	L.bytes = (o + 15) & ~(size_t)15;
+	return L;
+}
+
+// numpy's npy_logaddexp, so that the kernel and the float64 restatement round the same way
+__device__ __forceinline__ double bs_lae(double x, double y) {
+	if (x == y) return x + 0.69314718055994530942;
+	const double d = x - y;
+	if (d > 0) return x + log1p(exp(-d));
+	if (d <= 0) return y + log1p(exp(d));
+	return d;  // NaN
+}
+
+// ascending key of a DEscending score (smaller key = better); -0.0 is folded onto +0.0
+__device__ __forceinline__ uint64_t bs_desc64(double x) {
+	const uint64_t b = (uint64_t)__double_as_longlong(x + 0.0);
+	const uint64_t o = (b >> 63) ? ~b : (b | (1ull << 63));
+	return ~o;
+}
+__device__ __forceinline__ double bs_undesc64(uint64_t u) {
+	const uint64_t o = ~u;
+	return __longlong_as_double((long long)((o >> 63) ? (o & ~(1ull << 63)) : ~o));
+}
+__device__ __forceinline__ uint32_t bs_desc32(float x) {
+	const uint32_t b = __float_as_uint(x + 0.f);
+	const uint32_t o = (b >> 31) ? ~b : (b | 0x80000000u);
+	return ~o;
+}
+
+__device__ __forceinline__ uint64_t bs_extend_hash(uint64_t h, int c) { return convasr_mix_seed(h ^ ((uint64_t)(c + 1) * 0x9E3779B97F4A7C15ull)); }
+#define BS_EMPTY_HASH 0x243F6A8885A308D3ull
+
+
+// hist[bin] += 1 for every calling lane (bin >= 0).  In the first passes nearly every candidate of a frame falls into one or two bins (the
+// scores share sign and exponent), and 64 lanes adding to one LDS word are serialised: the lanes of the wave's two most common bins
+// among the callers are counted with a ballot and added by one lane each; the rest add one by one.  Callable from divergent code.
+// Only in the 1,024-thread workgroups (W > 256): with 16 waves contending the aggregation took W = 1024 from 106.7 to 86.9 ms
+// (64 x 750 frames), with 4 waves the extra ballots cost more than they saved (W = 64: 19.6 -> 21.5 ms).
+__device__ __forceinline__ void bs_hist_add(int* hist, int bin) {
+	const int lane = threadIdx.x & 63;
+	if (blockDim.x <= 256) {
+		if (bin >= 0) atomicAdd(&hist[bin], 1);
+		return;
+	}
+#pragma unroll
+	for (int r = 0; r < 2; ++r) {
+		const uint64_t act = __ballot(bin >= 0);
+		if (!act) return;
+		const int lead = __shfl(bin, __ffsll((long long)act) - 1, 64);  // (the source lane is active and holds a bin)
+		const uint64_t same = __ballot(bin == lead);
+		if (bin == lead) {
+			if (lane == __ffsll((long long)same) - 1) atomicAdd(&hist[lead], __popcll(same));
+			bin = -1;
+		}
+	}
+	if (bin >= 0) atomicAdd(&hist[bin], 1);
+}
+
+// Wave 0: the bucket of `hist` where the running count reaches `need`; `all` when the whole histogram holds fewer.
+__device__ __forceinline__ void bs_pick(const int* hist, BsSel* s) {
+	const int lane = threadIdx.x;
+	const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+	const int sum = h0 + h1 + h2 + h3;
+	int incl = sum;
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1) {
+		const int v = __shfl_up(incl, o, 64);
+		if (lane >= o) incl += v;
+	}
+	const int excl = incl - sum, need = s->need;
+	if (excl < need && need <= incl) {
+		int b = 4 * lane, before = excl, h = h0;
+		while (before + h < need) { before += h; h = hist[++b]; }
+		s->bucket = b; s->before = before; s->cnt = h;
+	}
+	if (lane == 63 && incl < need) s->all = 1;
+}
+
+// Radix select of the k best (smallest (u, key)) among the candidates `enumerate` visits; afterwards bs_selected() tells them apart.
+// Every thread of the workgroup calls it.
+template <class E>
+__device__ void bs_radix_select(E enumerate, int k, int* hist, BsSel* s) {
+	const int tid = threadIdx.x, nth = blockDim.x;
+	if (tid == 0) { s->P = 0; s->M = 0; s->KP = 0; s->KM = 0; s->need = k; s->full = 0; s->all = 0; s->tie = 0; }
+	__syncthreads();
+	for (int shift = 56; shift >= 0; shift -= 8) {
+		for (int i = tid; i < 256; i += nth) hist[i] = 0;
+		__syncthreads();
+		const uint64_t P = s->P, M = s->M;
+		enumerate([&](uint64_t u, unsigned) { bs_hist_add(hist, (u & M) == P ? (int)((u >> shift) & 255) : -1); });
+		__syncthreads();
+		if (tid < 64) bs_pick(hist, s);
+		__syncthreads();
+		if (s->all) return;
+		if (tid == 0) {
+			s->P |= (uint64_t)s->bucket << shift; s->M |= 255ull << shift; s->need -= s->before;
+			if (s->cnt == s->need) s->full = 1;
+		}
+		__syncthreads();
+		if (s->full) return;
+	}
+	// more candidates than needed share the boundary score exactly: the smallest keys among them
+	if (tid == 0) s->tie = 1;
+	for (int shift = 16; shift >= 0; shift -= 8) {
+		for (int i = tid; i < 256; i += nth) hist[i] = 0;
+		__syncthreads();
+		const uint64_t P = s->P;
+		const unsigned KP = s->KP, KM = s->KM;
+		enumerate([&](uint64_t u, unsigned key) { bs_hist_add(hist, u == P && (key & KM) == KP ? (int)((key >> shift) & 255) : -1); });
+		__syncthreads();
+		if (tid < 64) bs_pick(hist, s);
+		__syncthreads();
+		if (tid == 0) {
+			s->KP |= (unsigned)s->bucket << shift; s->KM |= 255u << shift; s->need -= s->before;
+			if (s->cnt == s->need) s->full = 1;
+		}
+		__syncthreads();
+		if (s->full) return;
+	}
+}
+
+__device__ __forceinline__ bool bs_selected(const BsSel& s, uint64_t u, unsigned key) {
+	if (s.all || u < s.P) return true;
+	if ((u & s.M) != s.P) return false;
+	if (!s.tie) return true;
+	return key < s.KP || (key & s.KM) == s.KP;
+}
+
+// ascending bitonic sort of (su, sk) pairs, S a power of two
+__device__ void bs_sort(uint64_t* su, int* sk, int S) {
+	const int tid = threadIdx.x, nth = blockDim.x;
+	for (int k = 2; k <= S; k <<= 1)
+		for (int j = k >> 1; j > 0; j >>= 1) {
+			for (int i = tid; i < S; i += nth) {
+				const int l = i ^ j;
+				if (l > i) {
+					const uint64_t a = su[i], b = su[l];
+					const int ka = sk[i], kb = sk[l];
+					const bool gt = a > b || (a == b && ka > kb);
+					if (gt == ((i & k) == 0)) { su[i] = b; su[l] = a; sk[i] = kb; sk[l] = ka; }
+				}
+			}
+			__syncthreads();
+		}
+}
+
+__global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
+                                                                int64_t* __restrict__ out_tokens, int* __restrict__ out_offsets,
+                                                                int64_t* __restrict__ out_lengths, float* __restrict__ out_logp,
+                                                                int2* __restrict__ arena_all, int T, int C, int blank, int W, int N,
+                                                                float cutoff_prob, int topk) {
+	extern __shared__ __align__(16) unsigned char bs_smem[];
+	const BsLayout Ly = bs_layout(W, N, C);
+	BsSel& s = *(BsSel*)(bs_smem + Ly.sel);  // (dynamic: static LDS would stop the 160 KiB opt-in)
+	double* lpb = (double*)(bs_smem + Ly.lpb);
+	double* lpnb = (double*)(bs_smem + Ly.lpnb);
+	double* tot = (double*)(bs_smem + Ly.tot);
+	double* own_nb = (double*)(bs_smem + Ly.own_nb);
+	double* own_nnb = (double*)(bs_smem + Ly.own_nnb);
+	double* own_s = (double*)(bs_smem + Ly.own_s);
+	uint64_t* hash = (uint64_t*)(bs_smem + Ly.hash);
+	uint64_t* phash = (uint64_t*)(bs_smem + Ly.phash);
+	uint64_t* su = (uint64_t*)(bs_smem + Ly.su);
+	double* plp = (double*)(bs_smem + Ly.plp);
+	int* last = (int*)(bs_smem + Ly.last);
+	int* node = (int*)(bs_smem + Ly.node);
+	int* len = (int*)(bs_smem + Ly.len);
+	unsigned* fold = (unsigned*)(bs_smem + Ly.fold);
+	int* sk = (int*)(bs_smem + Ly.sk);
+	int* htab = (int*)(bs_smem + Ly.htab);
+	int* pc = (int*)(bs_smem + Ly.pc);
+	int* hist = (int*)(bs_smem + Ly.hist);
+	short* pos = (short*)(bs_smem + Ly.pos);
+	const int NW = Ly.NW, TB = Ly.TB;
+	const int tid = threadIdx.x, nth = blockDim.x, b = blockIdx.x;
+	int64_t Lb = lengths[b];
+	Lb = Lb < 0 ? 0 : (Lb > T ? T : Lb);
+	int2* arena = arena_all + (int64_t)b * T * W;
+	const double NEG = -INFINITY;
+
+	for (int c = tid; c < C; c += nth) pos[c] = -1;
+	if (tid == 0) {
+		lpb[0] = 0.0; lpnb[0] = NEG; tot[0] = 0.0; hash[0] = BS_EMPTY_HASH; phash[0] = 0; last[0] = -1; node[0] = -1; len[0] = 0;
+		s.n = 1; s.np = 0;
+	}
+	__syncthreads();
+
+	for (int t = 0; t < (int)Lb; ++t) {
+		const float* row = log_probs + ((int64_t)b * T + t) * C;
+		// ---- 1. P_t
+		for (int p = tid; p < s.np; p += nth) pos[pc[p]] = -1;
+		if (tid == 0) s.m = 0;
+		__syncthreads();
+		int np;
+		if (N >= C) {
+			for (int c = tid; c < C; c += nth) pc[c] = c;
+			np = C;
+		} else {
+			auto classes = [&](auto&& fn) { for (int c = tid; c < C; c += nth) fn(((uint64_t)bs_desc32(row[c]) << 32) | (unsigned)c, 0u); };
+			bs_radix_select(classes, N, hist, &s);
+			const BsSel sel = s;
+			for (int c = tid; c < C; c += nth)
+				if (bs_selected(sel, ((uint64_t)bs_desc32(row[c]) << 32) | (unsigned)c, 0u)) pc[atomicAdd(&s.m, 1)] = c;
+			np = N;
+		}
+		__syncthreads();
+		if (cutoff_prob < 1.f) {  // the shortest leading run of the sorted P_t whose probability reaches cutoff_prob
+			for (int i = tid; i < BS_MAX_N; i += nth) {
+				su[i] = i < np ? (((uint64_t)bs_desc32(row[pc[i]]) << 32) | (unsigned)pc[i]) : ~0ull;
+				sk[i] = 0;
+			}
+			__syncthreads();
+			bs_sort(su, sk, BS_MAX_N);
+			if (tid < 64) {
+				const int p0 = 2 * tid, p1 = 2 * tid + 1;
+				const int c0 = (int)(su[p0] & 0xffffffffu), c1 = (int)(su[p1] & 0xffffffffu);
+				const double v0 = p0 < np ? exp((double)row[c0]) : 0.0, v1 = p1 < np ? exp((double)row[c1]) : 0.0;
+				double incl = v0 + v1;
+#pragma unroll
+				for (int o = 1; o < 64; o <<= 1) {
+					const double v = __shfl_up(incl, o, 64);
+					if (tid >= o) incl += v;
+				}
+				const double excl = incl - (v0 + v1);
+				const double cum0 = excl + v0, cum1 = excl + v0 + v1;
+				const uint64_t hit = __ballot((p0 < np && cum0 >= (double)cutoff_prob) || (p1 < np && cum1 >= (double)cutoff_prob));
+				if (tid == 0) s.cut = np;
+				if (hit) {
+					const int first = __ffsll((long long)hit) - 1;
+					if (tid == first) s.cut = (p0 < np && cum0 >= (double)cutoff_prob) ? p0 + 1 : p1 + 1;
+				}
+				if (p0 < np) pc[p0] = c0;
+				if (p1 < np) pc[p1] = c1;
+			}
+			__syncthreads();
+			np = s.cut;
+		}
+		for (int p = tid; p < np; p += nth) { plp[p] = (double)row[pc[p]]; pos[pc[p]] = (short)p; }
+		if (tid == 0) s.np = np;
+		// ---- 2. hash table of the current beams, fold masks cleared
+		const int n = s.n;
+		for (int i = tid; i < TB; i += nth) htab[i] = 0;
+		for (int i = tid; i < n * NW; i += nth) fold[i] = 0;
+		if (tid == 0) s.m = 0;
+		__syncthreads();
+		for (int j = tid; j < n; j += nth) {
+			const uint64_t h = hash[j];
+			int slot = (int)((h ^ (h >> 32)) & (uint64_t)(TB - 1));
+			while (atomicCAS(&htab[slot], 0, j + 1) != 0) slot = (slot + 1) & (TB - 1);
+		}
+		__syncthreads();
+		// ---- own candidates (and the folds of extensions into existing beams)
+		const int pb = pos[blank];
+		for (int j = tid; j < n; j += nth) {
+			double nb = NEG, nnb = NEG;
+			if (pb >= 0) nb = plp[pb] + tot[j];
+			const int lj = last[j];
+			const int pl = lj >= 0 ? pos[lj] : -1;
+			if (pl >= 0) {
+				nnb = plp[pl] + lpnb[j];
+				const uint64_t h = phash[j];
+				int slot = (int)((h ^ (h >> 32)) & (uint64_t)(TB - 1)), i = -1;
+				for (int e; (e = htab[slot]) != 0; slot = (slot + 1) & (TB - 1))
+					if (hash[e - 1] == h) { i = e - 1; break; }
+				if (i >= 0) {
+					nnb = bs_lae(nnb, plp[pl] + (last[i] == lj ? lpb[i] : tot[i]));
+					atomicOr(&fold[i * NW + (pl >> 5)], 1u << (pl & 31));
+				}
+			}
+			own_nb[j] = nb; own_nnb[j] = nnb; own_s[j] = bs_lae(nb, nnb);
+		}
+		__syncthreads();
+		// ---- 3. top W of the candidates (beam i, q): q = 0 its own, q = p + 1 its extension by pc[p]
+		const int S = np + 1, total = n * S;
+		auto candidates = [&](auto&& fn) {
+			int i = tid / S, q = tid % S;
+			const int di = nth / S, dq = nth % S;
+			for (int e = tid; e < total; e += nth) {
+				double sc;
+				unsigned key = (unsigned)i << BS_KEY_C_BITS;
+				bool ok;
+				if (q == 0) { sc = own_s[i]; ok = true; }
+				else {
+					const int p = q - 1, c = pc[p];
+					ok = c != blank && !((fold[i * NW + (p >> 5)] >> (p & 31)) & 1u);
+					sc = plp[p] + (c == last[i] ? lpb[i] : tot[i]);
+					key |= (unsigned)(c + 1);
+				}
+				if (ok && sc > NEG) fn(bs_desc64(sc), key);
+				q += dq; i += di;
+				if (q >= S) { q -= S; ++i; }
+			}
+		};
+		bs_radix_select(candidates, W, hist, &s);
+		{
+			const BsSel sel = s;
+			candidates([&](uint64_t u, unsigned key) {
+				if (bs_selected(sel, u, key)) { const int r = atomicAdd(&s.m, 1); su[r] = u; sk[r] = (int)key; }
+			});
+		}
+		__syncthreads();
+		const int m = s.m, Sm = bs_pow2(m);
+		for (int r = m + tid; r < Sm; r += nth) { su[r] = ~0ull; sk[r] = 0x7fffffff; }
+		__syncthreads();
+		bs_sort(su, sk, Sm);
+		// ---- 4. the next beams, in rank order (one per thread: nth >= W >= m)
+		double nlpb = 0, nlpnb = 0, ntot = 0;
+		uint64_t nh = 0, nph = 0;
+		int nlast = 0, nnode = 0, nlen = 0;
+		if (tid < m) {
+			const unsigned key = (unsigned)sk[tid];
+			const int i = (int)(key >> BS_KEY_C_BITS), c = (int)(key & ((1u << BS_KEY_C_BITS) - 1)) - 1;
+			ntot = bs_undesc64(su[tid]);
+			if (c < 0) {
+				nlpb = own_nb[i]; nlpnb = own_nnb[i]; nh = hash[i]; nph = phash[i]; nlast = last[i]; nnode = node[i]; nlen = len[i];
+			} else {
+				nlpb = NEG; nlpnb = ntot; nh = bs_extend_hash(hash[i], c); nph = hash[i]; nlast = c; nlen = len[i] + 1;
+				nnode = t * W + tid;
+				arena[nnode] = make_int2(node[i], c);
+			}
+		}
+		__syncthreads();
+		if (tid < m) { lpb[tid] = nlpb; lpnb[tid] = nlpnb; tot[tid] = ntot; hash[tid] = nh; phash[tid] = nph; last[tid] = nlast; node[tid] = nnode; len[tid] = nlen; }
+		if (tid == 0) s.n = m;
+		__syncthreads();
+	}
+
+	// ---- results: the best topk beams, walked back through the arena
+	const int n = s.n;
+	int64_t* tok_b = out_tokens + (int64_t)b * topk * T;
+	int* off_b = out_offsets + (int64_t)b * topk * T;
+	for (int64_t e = tid; e < (int64_t)topk * T; e += nth) {
+		const int k = (int)(e / T), p = (int)(e % T);
+		if (p >= (k < n ? len[k] : 0)) { tok_b[e] = 0; off_b[e] = 0; }
+	}
+	for (int k = tid; k < topk; k += nth) {
+		if (k < n) {
+			int p = len[k] - 1;
+			for (int nd = node[k]; nd >= 0 && p >= 0; --p) {
+				const int2 v = arena[nd];
+				tok_b[(int64_t)k * T + p] = v.y;
+				off_b[(int64_t)k * T + p] = nd / W;
+				nd = v.x;
+			}
+			out_lengths[(int64_t)b * topk + k] = len[k];
+			out_logp[(int64_t)b * topk + k] = (float)tot[k];
+		} else {
+			out_lengths[(int64_t)b * topk + k] = 0;
+			out_logp[(int64_t)b * topk + k] = -INFINITY;
+		}
+	}
+}
+
+static const char* bs_envelope(int B, int T, int C, int W, int N, int topk, int* code) {
+	*code = CONVASR_EINVAL;
+	if (B < 1 || T < 1) return "B and T must be >= 1";
+	if (W < 1) return "beam width must be >= 1";
+	if (C < 2) return "C must be >= 2";
+	if (N < 1 || N > C) return "cutoff_top_n must be in [1, C]";
+	if (topk < 1 || topk > W) return "topk must be in [1, beam width]";
+	*code = CONVASR_EUNSUPPORTED;
+	if (W > BS_MAX_W) return "beam width > 1024 is outside the supported envelope";
+	if (N > BS_MAX_N) return "cutoff_top_n > 128 is outside the supported envelope";
+	if (C > BS_MAX_C) return "C > 8192 is outside the supported envelope";
+	if ((int64_t)B * T * W >= (1ll << 31)) return "B * T * beam width >= 2^31 (workspace arena)";
+	if ((int64_t)B * topk * T >= (1ll << 31)) return "B * topk * T >= 2^31 (outputs)";
+	return nullptr;
+}
+
+extern "C" int64_t convasr_ctc_beam_search_workspace_bytes(int B, int T, int C, int W, int N, int topk) {
+	int code;
+	if (const char* why = bs_envelope(B, T, C, W, N, topk, &code)) return convasr_fail(code, "ctc_beam_search: %s (B %d T %d C %d W %d N %d topk %d)", why, B, T, C, W, N, topk);
+	return (int64_t)B * T * W * (int64_t)sizeof(int2);
+}
+
+extern "C" int convasr_ctc_beam_search(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                       float* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob,
+                                       int topk, void* stream) {
+	CONVASR_CHECK_ARG(log_probs && lengths && tokens && offsets && out_lengths && log_prob && workspace, "ctc_beam_search: NULL pointer");
+	int code;
+	if (const char* why = bs_envelope(B, T, C, W, N, topk, &code)) return convasr_fail(code, "ctc_beam_search: %s (B %d T %d C %d W %d N %d topk %d)", why, B, T, C, W, N, topk);
+	CONVASR_CHECK_ARG(blank >= 0 && blank < C, "ctc_beam_search: blank %d outside [0, %d)", blank, C);
+	CONVASR_CHECK_ARG(cutoff_prob > 0.f && cutoff_prob <= 1.f, "ctc_beam_search: cutoff_prob must be in (0, 1]");
+	const BsLayout Ly = bs_layout(W, N, C);
+	if (Ly.bytes > 160 * 1024) return convasr_fail(CONVASR_EUNSUPPORTED, "ctc_beam_search: %zu bytes of LDS (W %d N %d C %d)", Ly.bytes, W, N, C);
+	const int threads = W <= 256 ? 256 : 1024;
+	static unsigned long long set = 0;
+	convasr_allow_160k_lds(reinterpret_cast<const void*>(ctc_beam_search_kernel), set);
+	hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(threads), Ly.bytes, (hipStream_t)stream, log_probs, lengths, tokens, offsets, out_lengths,
+	                   log_prob, (int2*)workspace, T, C, blank, W, N, cutoff_prob, topk);
+	CONVASR_CHECK_LAUNCH("ctc_beam_search");
+	return 0;
+}

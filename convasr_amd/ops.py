@@ -858,3 +858,30 @@ def ctc_alignment(log_probs_btc, targets, input_lengths, target_lengths, blank):
 	ws = workspace(_lib.load().convasr_ctc_alignment_workspace_bytes(B, T, S_max), dev, 'ctc_alignment')
 	call('convasr_ctc_alignment', ptr(log_probs_btc), ptr(targets), ptr(il), ptr(tl), ptr(out), ptr(ws), B, T, C, S_max, int(blank), stream_ptr())
 	return out
+
+
+def ctc_beam_search(log_probs_bct, lengths, blank, beam_width, cutoff_top_n = 40, cutoff_prob = 1.0, topk = 1):
+	"""CTC prefix beam search without a language model (include/convasr_hip.h: convasr_ctc_beam_search).  log_probs_bct: (B, C, T) log-probs
+	on the GPU (the model's channels-last fp32 is read in place, anything else is converted); lengths (B,) frames per utterance or None (all T).
+	Returns (tokens (B, topk, T) int64, offsets (B, topk, T) int32, out_lengths (B, topk) int64, log_prob (B, topk) fp32), best first.
+	The kernel's prefix-node arena is allocated for the call: B x T x beam_width x 8 bytes.
+	cutoff_top_n above C means C.  Outside the kernel's envelope (beam_width <= 1024, cutoff_top_n <= 128, C <= 8192, ...) it raises ConvasrHipError."""
+	require_cuda(log_probs_bct)
+	B, C, T = log_probs_bct.shape
+	lp = as_cl(log_probs_bct, torch.float32)
+	dev = lp.device
+	lengths = torch.full((B,), T, dtype = torch.int64, device = dev) if lengths is None else torch.as_tensor(lengths).to(device = dev, dtype = torch.int64).contiguous()
+	if lengths.shape != (B,):
+		raise ValueError(f'ctc_beam_search: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
+	N = C if cutoff_top_n is None else min(int(cutoff_top_n), C)  # (ctcdecode's pruning takes min(cutoff_top_n, C) too: the reference's default 40 over its 38 classes)
+	W, topk = int(beam_width), int(topk)
+	nbytes = _lib.load().convasr_ctc_beam_search_workspace_bytes(B, T, C, W, N, topk)
+	if nbytes < 0:
+		raise _lib.ConvasrHipError(_lib.load().convasr_last_error().decode())
+	tokens = torch.empty(B, topk, T, dtype = torch.int64, device = dev)
+	offsets = torch.empty(B, topk, T, dtype = torch.int32, device = dev)
+	out_lengths = torch.empty(B, topk, dtype = torch.int64, device = dev)
+	log_prob = torch.empty(B, topk, dtype = torch.float32, device = dev)
+	ws = torch.empty(nbytes, dtype = torch.uint8, device = dev)  # per call, not the grow-only cache: B x T x W nodes of 8 bytes (393 MB at 64 x 750 x 1024) go back to the allocator
+	call('convasr_ctc_beam_search', ptr(lp), ptr(lengths), ptr(tokens), ptr(offsets), ptr(out_lengths), ptr(log_prob), ptr(ws), B, T, C, int(blank), W, N, float(cutoff_prob), topk, stream_ptr())
+	return tokens, offsets, out_lengths, log_prob

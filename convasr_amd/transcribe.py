@@ -2,7 +2,8 @@
 
 * setup(args) -> (text_pipeline, frontend, model, generator)                          transcribe.py:23-60
   checkpoint -> frontend + model (the reference's class names / state-dict keys) -> eval() -> fuse_conv_bn_eval() ->
-  compute dtype from args.fp16 (None / 'O0': exact fp32; 'O1'..'O3': fp16 storage + MFMA as under apex.amp, or bf16 when models.AMP_DTYPE says so) -> greedy generator.
+  compute dtype from args.fp16 (None / 'O0': exact fp32; 'O1'..'O3': fp16 storage + MFMA as under apex.amp, or bf16 when models.AMP_DTYPE says so) -> greedy generator,
+  or with args.decoder = 'BeamSearchDecoder' the CTC prefix beam search (args.beam_width, args.decoder_topk; no language model).
 * transcribe_batch(...)                                                                transcribe.py:140-200
   the per-batch body of transcribe.main: forward (every op a HIP kernel; the argmax of the greedy decode too), per-frame time
   stamps, GreedyCTCGenerator with time stamps (one segment per word), optional forced alignment of the reference text
@@ -16,7 +17,7 @@ import types
 import torch
 
 from . import ctc, models
-from .transcript_generators import CharTokenizerLegacy, GreedyCTCGenerator
+from .transcript_generators import BeamCTCGenerator, CharTokenizerLegacy, GreedyCTCGenerator
 
 RU_ALPHABET = 'абвгдеёжзийклмнопрстуфхцчшщъыьэюя'  # configs/ru_text_config.json:10
 
@@ -71,7 +72,10 @@ def setup(args):
 			models.master_module(model).set_compute_dtype(level, inference = True)
 		else:
 			model, *_ = models.data_parallel_and_autocast(model, opt_level = level)
-	generator = GreedyCTCGenerator()
+	if getattr(args, 'decoder', None) == 'BeamSearchDecoder':  # transcribe.py:323-327: --decoder, --beam-width, --decoder-topk, --lm (no LM scorer here: --lm raises)
+		generator = BeamCTCGenerator(beam_width = args.beam_width, topk = getattr(args, 'decoder_topk', 1), lm_path = getattr(args, 'lm', None))
+	else:
+		generator = GreedyCTCGenerator()
 	return text_pipeline, frontend, model, generator
 
 
@@ -95,6 +99,7 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 		out.alignment = ctc.alignment_bct(log_probs, y[:, 0, :], olen, ylen[:, 0], blank = tokenizer.eps_id)
 		aligned_ts = ts.gather(1, out.alignment)
 		one_hot = torch.nn.functional.one_hot(y[:, 0, :], num_classes = log_probs.shape[1]).permute(0, 2, 1).to(torch.float32)
-		ref_segments = [alternatives[0] for alternatives in generator.generate(tokenizer = tokenizer, log_probs = one_hot, begin = begin, end = end, output_lengths = ylen[:, 0], time_stamps = aligned_ts, segment_text_key = 'ref', segment_extra_info = segment_extra_info)]
+		ref_generator = generator if isinstance(generator, GreedyCTCGenerator) else GreedyCTCGenerator()  # one-hot targets: the argmax collapse gives back y; a beam search over 0 / 1 "log-probs" would not
+		ref_segments = [alternatives[0] for alternatives in ref_generator.generate(tokenizer = tokenizer, log_probs = one_hot, begin = begin, end = end, output_lengths = ylen[:, 0], time_stamps = aligned_ts, segment_text_key = 'ref', segment_extra_info = segment_extra_info)]
 		out.ref_segments = [map_text(text_pipeline.postprocess, ref = ref) for ref in ref_segments]
 	return out

@@ -4,6 +4,8 @@ The per-frame argmax over classes runs on the GPU (convasr_argmax); the collapse
 repeats unless a blank intervened, >= blank_amount_to_space consecutive blanks insert one space, a blank right after a space
 is ignored, a new segment starts at every word-start token when time stamps are given -- stay a host loop over B x t ints,
 as in the reference."""
+import types
+
 import torch
 
 from . import ops
@@ -94,4 +96,55 @@ class GreedyCTCGenerator:
 			if len(tokens) > 1:
 				flush()
 			result.append([transcript])
+		return result
+
+
+class BeamCTCGenerator:
+	"""GreedyCTCGenerator's interface over the CTC prefix beam search (convasr_ctc_beam_search; the reference's transcribe.py
+	--decoder BeamSearchDecoder, without a language model).  Per utterance it returns topk alternatives, best first; each is a Transcript
+	of word segments built from that beam's tokens: leading silence tokens are skipped, a new segment starts at every word-start token
+	when time stamps are given, and a token's time is begin + time_stamps[its frame offset].  GPU only: log_probs must be a CUDA tensor
+	(GreedyCTCGenerator also decodes CPU tensors); for the one-hot targets of --align, transcribe_batch uses a GreedyCTCGenerator."""
+
+	def __init__(self, beam_width = 64, topk = 1, cutoff_top_n = 40, cutoff_prob = 1.0, lm_path = None):
+		from . import decoders
+		self.topk = int(topk)
+		self.decoder = lambda blank: decoders.BeamSearchDecoder(types.SimpleNamespace(blank_idx = blank), lm_path = lm_path, beam_width = beam_width, cutoff_top_n = cutoff_top_n, cutoff_prob = cutoff_prob, topk = topk)
+		self.decoder(0)  # (an lm_path raises here, at setup)
+
+	def generate(self, tokenizer, log_probs, begin, end, output_lengths = None, time_stamps = None, segment_text_key = 'hyp', segment_extra_info = None):
+		tokens, offsets, lengths, _ = self.decoder(tokenizer.eps_id).decode_with_scores(log_probs, output_lengths)
+		tokens, offsets, lengths = tokens.cpu().tolist(), offsets.cpu().tolist(), lengths.cpu().tolist()
+		ts_all = time_stamps.cpu().tolist() if time_stamps is not None else None
+		begin = torch.clamp(begin, min = 0.0).cpu().tolist() if time_stamps is not None else begin.cpu().tolist()
+		end = end.cpu().tolist()
+		silence = tokenizer.silence_tokens_ids
+		result = []
+		for i in range(len(tokens)):
+			ts = ts_all[i] if ts_all is not None else None
+			alternatives = []
+			for k in range(self.topk):
+				toks, offs = tokens[i][k][:lengths[i][k]], offsets[i][k][:lengths[i][k]]
+				transcript = Transcript()
+				start = next((j for j, c in enumerate(toks) if c not in silence), len(toks))
+				at = lambda j: begin[i] + ts[offs[j]] if ts is not None else None
+				seg_tokens, t_begin, t_end = [], at(start) if ts is not None and start < len(toks) else begin[i], end[i]
+
+				def flush():
+					seg = Segment(begin = t_begin, end = t_end, **{segment_text_key: tokenizer.decode([seg_tokens])[0]})
+					if segment_extra_info is not None:
+						seg.update(segment_extra_info[i])
+					transcript.append(seg)
+
+				for j in range(start, len(toks)):
+					c = toks[j]
+					if ts is not None and tokenizer.is_start_word_token(c) and seg_tokens:
+						flush()
+						seg_tokens, t_begin = [], at(j)
+					seg_tokens.append(c)
+					t_end = at(j) if ts is not None else end[i]
+				if seg_tokens:
+					flush()
+				alternatives.append(transcript)
+			result.append(alternatives)
 		return result

@@ -510,6 +510,33 @@ int convasr_ctc_alignment(const float* log_probs, const int64_t* targets, const 
 int convasr_collate_pad(const void* packed, const int64_t* offsets, const int64_t* lengths, void* out, int elem_bytes, int B, int rows,
                         int64_t Tpad, void* stream);
 
+/* ---- CTC prefix beam search without a language model: decoders.py:19-55 (BeamSearchDecoder, ctcdecode.CTCBeamDecoder with
+ * lm_path = None), train.py:975-995 / transcribe.py:323-327 (--decoder BeamSearchDecoder, --beam-width, --decoder-topk) ---------- */
+
+/* Bytes of workspace convasr_ctc_beam_search needs (the prefix-node arena: B * T * W nodes of 8 bytes); a negative CONVASR_E* code
+ * with a message when the arguments are outside the envelope below. */
+int64_t convasr_ctc_beam_search_workspace_bytes(int B, int T, int C, int W, int N, int topk);
+/* log_probs: fp32, element (b, c, t) at ((b * T + t) * C + c); lengths (B,) int64, frames t < lengths[b] are decoded (clamped to
+ * [0, T]).  One workgroup per utterance, the frame loop inside the kernel; the workspace needs no initialisation and the call has no
+ * memset, copy or host synchronisation, so it can be captured into a graph.  Per frame t:
+ *   P_t = the classes sorted by lp[t] descending (ties: lower index), the first N; cutoff_prob < 1 keeps the shortest leading run whose
+ *   cumulative probability reaches cutoff_prob (at least one class).  For every beam l (lpb / lpnb: log-probability that it ends
+ *   in blank / non-blank; the search starts from the empty prefix, lpb = 0, lpnb = -inf) and c in P_t, with logaddexp as the sum:
+ *   c == blank: nb(l) += lp + lpb(l) + lpnb(l); c == last(l): nnb(l) += lp + lpnb(l), nnb(l + c) += lp + lpb(l); otherwise
+ *   nnb(l + c) += lp + lpb(l) + lpnb(l).  An extension equal to a beam already held is folded into that beam's candidate; a candidate
+ *   that got no contribution or whose total is -inf is dropped.  The best W candidates by lpb + lpnb survive, ties broken by
+ *   ascending key (rank of the source beam, -1) for a beam's own candidate and (rank of i, c) for an unmerged extension of beam i
+ *   by c; that order is the next frame's ranking.  Beam scores are kept in fp64.
+ * Outputs, best hypothesis first: tokens (B, topk, T) int64 and offsets (B, topk, T) int32 (the frame at which each token was appended
+ * by the extension that created it; 0 past a hypothesis' length), out_lengths (B, topk) int64, log_prob (B, topk) fp32 = lpb + lpnb
+ * (the MOST probable hypotheses; a slot the search could not fill has length 0 and -inf).  lengths[b] = 0: one empty hypothesis, 0.
+ * Envelope, checked before any launch: 1 <= W <= 1024, 1 <= N <= min(C, 128), 1 <= topk <= W, 2 <= C <= 8192, 0 <= blank < C,
+ * 0 < cutoff_prob <= 1, B * T * W < 2^31; outside it CONVASR_EINVAL / CONVASR_EUNSUPPORTED (the reference's default
+ * --beam-width 5000 among them). */
+int convasr_ctc_beam_search(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                            float* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
