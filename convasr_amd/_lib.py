@@ -97,6 +97,9 @@ _SIGNATURES = dict(
 	convasr_ctc_alignment = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_ctc_beam_search_workspace_bytes = (c_i64, [c_int] * 6),
 	convasr_ctc_beam_search = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int, c_p]),
+	convasr_ctc_beam_search_lm_workspace_bytes = (c_i64, [c_int] * 6),
+	convasr_ctc_beam_search_lm = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int,
+	                                      c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p]),
 )
 
 _lib = None

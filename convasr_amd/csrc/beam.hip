@@ -15,12 +15,36 @@
 //      is node / W.  The best topk beams are walked back once at the end.
 // Beam scores are fp64 (the log-probs are read as fp32): the selection boundary of a wide beam over hundreds of frames sits among
 // tens of thousands of candidates, and fp32 accumulation would reorder near-ties that the float64 restatement keeps apart.
+//
+// With an n-gram LM (convasr_ctc_beam_search_lm; tables built by convasr_amd/lm.py, restated by tests/_ctc_beam_lm_ref.py) the same body
+// runs as bs_body<true>.  Each beam also keeps in LDS its vocabulary-trie node (the current word), its LM state (the entry id of the
+// longest listed suffix of its word history), the mask of the classes it may be extended by (the trie node's children, plus the space
+// when the current word is a word of V), and the fp64 LM term of a space extension.  All four are set once when the beam is created
+// (step 4: one trie step, and for a word that ends there the n-gram lookups of its score), so the frame loop only tests mask bits and
+// adds the cached term.  bs_body<false> is the LM-free kernel: every LM statement sits under `if constexpr (LM)`.
+#include <cmath>
+
 #include "common.h"
 
 #define BS_MAX_W 1024
 #define BS_MAX_N 128
 #define BS_MAX_C 8192
 #define BS_KEY_C_BITS 14  // candidate key = rank << 14 | (c + 1): c + 1 <= 8192 < 2^14, rank < 1024 -> 24 bits
+#define BS_LM_MAX_C 256
+#define BS_LM_MAX_ORDER 6
+#define BS_LM_EMPTY_KEY (-2)
+
+// The LM tables (convasr_amd/lm.py documents them); MW = ceil(C / 32) mask words per trie node.
+struct BsLm {
+	const unsigned* node_mask;  // (n_nodes, MW)
+	const int* node_child;      // (n_nodes,)
+	const int* node_word;       // (n_nodes,)
+	const double2* ent_pb;      // (n_ent,): (log10 p, log10 bow)
+	const int2* ent_sl;         // (n_ent,): (longest listed proper suffix, order)
+	const int4* slots;          // (n_slots,): (context entry, word, entry, 0)
+	int n_slots, space, order, start;
+	double alpha, beta;
+};
 
 __host__ __device__ static inline int bs_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
@@ -37,10 +61,12 @@ struct BsLayout {
 	size_t lpb, lpnb, tot, own_nb, own_nnb, own_s, hash, phash, su, plp;  // 8-byte arrays
 	size_t sel;                                                              // the selection state (BsSel)
 	size_t last, node, len, fold, sk, htab, pc, hist, pos;                   // 4- / 2-byte arrays
+	size_t lmsp, lnode, lstate, lmask;                                       // LM only: fp64 term, trie node, LM state, MW mask words
+	int MW;
 	size_t bytes;
 };
 
-__host__ __device__ static inline BsLayout bs_layout(int W, int N, int C) {
+__host__ __device__ static inline BsLayout bs_layout(int W, int N, int C, bool lm = false) {
 	BsLayout L;
 	L.W = W; L.NW = (N + 31) / 32; L.C = C;
 	L.S = bs_pow2(W > BS_MAX_N ? W : BS_MAX_N);
@@ -66,6 +92,15 @@ __host__ __device__ static inline BsLayout bs_layout(int W, int N, int C) {
 	L.pc = o; o += 4 * (size_t)BS_MAX_N;
 	L.hist = o; o += 4 * 256;
 	L.pos = o; o += 2 * (size_t)C;
+	L.MW = 0; L.lmsp = L.lnode = L.lstate = L.lmask = 0;
+	if (lm) {
+		L.MW = (C + 31) / 32;
+		o = (o + 7) & ~(size_t)7;
+		L.lmsp = o; o += 8 * (size_t)W;
+		L.lnode = o; o += 4 * (size_t)W;
+		L.lstate = o; o += 4 * (size_t)W;
+		L.lmask = o; o += 4 * (size_t)W * L.MW;
+	}
 	L.bytes = (o + 15) & ~(size_t)15;
 	return L;
 }
@@ -212,13 +247,57 @@ __device__ void bs_sort(uint64_t* su, int* sk, int S) {
 		}
 }
 
-__global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
-                                                                int64_t* __restrict__ out_tokens, int* __restrict__ out_offsets,
-                                                                int64_t* __restrict__ out_lengths, float* __restrict__ out_logp,
-                                                                int2* __restrict__ arena_all, int T, int C, int blank, int W, int N,
-                                                                float cutoff_prob, int topk) {
+// ---- LM lookups (lm.py: _hash, NgramLM.log10_cond); every loop is bounded even over tables that break lm.py's invariants
+__device__ __forceinline__ unsigned bs_lm_hash(int ctx, int word) {
+	unsigned h = ((unsigned)ctx * 0x9E3779B1u) ^ ((unsigned)word * 0x85EBCA77u);
+	h ^= h >> 15;
+	h *= 0x2C1B3C6Du;
+	h ^= h >> 12;
+	return h;
+}
+
+// the entry (ctx, word) of order >= 2, -1 when the model does not list it; ctx = -1: the unigram entry, which is the word id
+__device__ __forceinline__ int bs_lm_find(const BsLm& lm, int ctx, int word) {
+	if (ctx < 0) return word;
+	unsigned slot = bs_lm_hash(ctx, word) & (unsigned)(lm.n_slots - 1);
+	for (int probe = 0; probe < lm.n_slots; ++probe, slot = (slot + 1) & (unsigned)(lm.n_slots - 1)) {
+		const int4 v = lm.slots[slot];
+		if (v.x == ctx && v.y == word) return v.z;
+		if (v.x == BS_LM_EMPTY_KEY) return -1;
+	}
+	return -1;
+}
+
+// log10 P(word | state) by the backoff rule: the first listed (suffix, word), plus the backoff weights of the longer suffixes
+__device__ double bs_lm_log10(const BsLm& lm, int s, int word) {
+	double acc = 0.0;
+	for (int it = 0; it <= BS_LM_MAX_ORDER; ++it) {
+		const int e = bs_lm_find(lm, s, word);
+		if (e >= 0) return acc + lm.ent_pb[e].x;
+		acc += lm.ent_pb[s].y;
+		s = lm.ent_sl[s].x;
+	}
+	return acc + lm.ent_pb[word].x;
+}
+
+// the state after `word` follows state s: the longest listed (suffix of s of at most order - 2 words, word)
+__device__ int bs_lm_advance(const BsLm& lm, int s, int word) {
+	if (lm.order == 1) return -1;
+	if (s >= 0 && lm.ent_sl[s].y > lm.order - 2) s = lm.ent_sl[s].x;
+	for (int it = 0; it <= BS_LM_MAX_ORDER; ++it) {
+		const int e = bs_lm_find(lm, s, word);
+		if (e >= 0) return e;
+		s = lm.ent_sl[s].x;
+	}
+	return word;
+}
+
+template <bool LM>
+__device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths, int64_t* __restrict__ out_tokens,
+                                        int* __restrict__ out_offsets, int64_t* __restrict__ out_lengths, void* __restrict__ out_logp,
+                                        int2* __restrict__ arena_all, int T, int C, int blank, int W, int N, float cutoff_prob, int topk, const BsLm& lm) {
 	extern __shared__ __align__(16) unsigned char bs_smem[];
-	const BsLayout Ly = bs_layout(W, N, C);
+	const BsLayout Ly = bs_layout(W, N, C, LM);
 	BsSel& s = *(BsSel*)(bs_smem + Ly.sel);  // (dynamic: static LDS would stop the 160 KiB opt-in)
 	double* lpb = (double*)(bs_smem + Ly.lpb);
 	double* lpnb = (double*)(bs_smem + Ly.lpnb);
@@ -239,6 +318,13 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __re
 	int* pc = (int*)(bs_smem + Ly.pc);
 	int* hist = (int*)(bs_smem + Ly.hist);
 	short* pos = (short*)(bs_smem + Ly.pos);
+	double* lmsp = (double*)(bs_smem + Ly.lmsp);
+	int* lnode = (int*)(bs_smem + Ly.lnode);
+	int* lstate = (int*)(bs_smem + Ly.lstate);
+	unsigned* lmask = (unsigned*)(bs_smem + Ly.lmask);
+	const int MW = LM ? Ly.MW : 0;
+	const int space = LM ? lm.space : -1;
+	const double LN10 = 2.302585092994045684;
 	const int NW = Ly.NW, TB = Ly.TB;
 	const int tid = threadIdx.x, nth = blockDim.x, b = blockIdx.x;
 	int64_t Lb = lengths[b];
@@ -250,6 +336,10 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __re
 	if (tid == 0) {
 		lpb[0] = 0.0; lpnb[0] = NEG; tot[0] = 0.0; hash[0] = BS_EMPTY_HASH; phash[0] = 0; last[0] = -1; node[0] = -1; len[0] = 0;
 		s.n = 1; s.np = 0;
+	}
+	if constexpr (LM) {
+		if (tid == 0) { lmsp[0] = 0.0; lnode[0] = 0; lstate[0] = lm.start; }
+		for (int k = tid; k < MW; k += nth) lmask[k] = lm.node_mask[k];  // the root's children; the space is not allowed
 	}
 	__syncthreads();
 
@@ -330,8 +420,13 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __re
 				int slot = (int)((h ^ (h >> 32)) & (uint64_t)(TB - 1)), i = -1;
 				for (int e; (e = htab[slot]) != 0; slot = (slot + 1) & (TB - 1))
 					if (hash[e - 1] == h) { i = e - 1; break; }
+				if constexpr (LM)
+					if (i >= 0 && !((lmask[i * MW + (lj >> 5)] >> (lj & 31)) & 1u)) i = -1;  // (l_j exists, so l_i + last(l_j) is allowed: never taken)
 				if (i >= 0) {
-					nnb = bs_lae(nnb, plp[pl] + (last[i] == lj ? lpb[i] : tot[i]));
+					double e = plp[pl] + (last[i] == lj ? lpb[i] : tot[i]);
+					if constexpr (LM)
+						if (lj == space) e += lmsp[i];
+					nnb = bs_lae(nnb, e);
 					atomicOr(&fold[i * NW + (pl >> 5)], 1u << (pl & 31));
 				}
 			}
@@ -350,8 +445,11 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __re
 				if (q == 0) { sc = own_s[i]; ok = true; }
 				else {
 					const int p = q - 1, c = pc[p];
-					ok = c != blank && !((fold[i * NW + (p >> 5)] >> (p & 31)) & 1u);
+					if constexpr (LM) ok = ((lmask[i * MW + (c >> 5)] >> (c & 31)) & 1u) && !((fold[i * NW + (p >> 5)] >> (p & 31)) & 1u);  // (never the blank)
+					else ok = c != blank && !((fold[i * NW + (p >> 5)] >> (p & 31)) & 1u);
 					sc = plp[p] + (c == last[i] ? lpb[i] : tot[i]);
+					if constexpr (LM)
+						if (c == space) sc += lmsp[i];
 					key |= (unsigned)(c + 1);
 				}
 				if (ok && sc > NEG) fn(bs_desc64(sc), key);
@@ -375,48 +473,130 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __re
 		double nlpb = 0, nlpnb = 0, ntot = 0;
 		uint64_t nh = 0, nph = 0;
 		int nlast = 0, nnode = 0, nlen = 0;
+		double nlmsp = 0.0;
+		int nlnode = 0, nlstate = 0;
+		unsigned nmask[BS_LM_MAX_C / 32];
 		if (tid < m) {
 			const unsigned key = (unsigned)sk[tid];
 			const int i = (int)(key >> BS_KEY_C_BITS), c = (int)(key & ((1u << BS_KEY_C_BITS) - 1)) - 1;
 			ntot = bs_undesc64(su[tid]);
 			if (c < 0) {
 				nlpb = own_nb[i]; nlpnb = own_nnb[i]; nh = hash[i]; nph = phash[i]; nlast = last[i]; nnode = node[i]; nlen = len[i];
+				if constexpr (LM) {
+					nlmsp = lmsp[i]; nlnode = lnode[i]; nlstate = lstate[i];
+#pragma unroll
+					for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nmask[k] = k < MW ? lmask[i * MW + k] : 0u;
+				}
 			} else {
 				nlpb = NEG; nlpnb = ntot; nh = bs_extend_hash(hash[i], c); nph = hash[i]; nlast = c; nlen = len[i] + 1;
 				nnode = t * W + tid;
 				arena[nnode] = make_int2(node[i], c);
+				if constexpr (LM) {
+					nlstate = lstate[i];
+					int word;
+					if (c == space) {  // the current word ends: the next one starts at the root, in the state after it
+						word = lm.node_word[lnode[i]];
+						nlstate = bs_lm_advance(lm, nlstate, word);
+						nlnode = 0;
+						word = -1;
+					} else {  // one trie step: the child's index among its siblings = the parent's children below c
+						const int pn = lnode[i];
+						int below = 0;
+#pragma unroll
+						for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+							if (k < MW) {
+								unsigned bits = lm.node_mask[(int64_t)pn * MW + k];
+								if (32 * k + 32 <= c) below += __popc(bits);
+								else if (32 * k <= c) below += __popc(bits & ((1u << (c & 31)) - 1u));
+							}
+						nlnode = lm.node_child[pn] + below;
+						word = lm.node_word[nlnode];
+					}
+#pragma unroll
+					for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nmask[k] = k < MW ? lm.node_mask[(int64_t)nlnode * MW + k] : 0u;
+					nlmsp = 0.0;
+					if (word >= 0) {  // the current word is in V: the space may follow, with this LM term
+						nlmsp = lm.alpha * (bs_lm_log10(lm, nlstate, word) * LN10) + lm.beta;
+#pragma unroll
+						for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+							if (k == (space >> 5)) nmask[k] |= 1u << (space & 31);
+					}
+				}
 			}
 		}
 		__syncthreads();
 		if (tid < m) { lpb[tid] = nlpb; lpnb[tid] = nlpnb; tot[tid] = ntot; hash[tid] = nh; phash[tid] = nph; last[tid] = nlast; node[tid] = nnode; len[tid] = nlen; }
+		if constexpr (LM) {
+			if (tid < m) {
+				lmsp[tid] = nlmsp; lnode[tid] = nlnode; lstate[tid] = nlstate;
+#pragma unroll
+				for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+					if (k < MW) lmask[tid * MW + k] = nmask[k];
+			}
+		}
 		if (tid == 0) s.n = m;
 		__syncthreads();
 	}
 
 	// ---- results: the best topk beams, walked back through the arena
 	const int n = s.n;
+	if constexpr (LM) {  // the end-of-utterance term F(l), then the beams re-ranked by lpb + lpnb + F (ties: rank); tot[] = the fused score
+		const double oov = lm.alpha * -1000.0 + lm.beta;
+		const int Sn = bs_pow2(n);
+		for (int r = tid; r < Sn; r += nth) {
+			if (r < n) {
+				const bool in_v = (lmask[r * MW + (space >> 5)] >> (space & 31)) & 1u;
+				const double F = (len[r] == 0 || last[r] == space) ? 0.0 : (in_v ? lmsp[r] : oov);
+				su[r] = bs_desc64(tot[r] + F); sk[r] = r;
+			} else {
+				su[r] = ~0ull; sk[r] = 0x7fffffff;
+			}
+		}
+		__syncthreads();
+		bs_sort(su, sk, Sn);
+	}
 	int64_t* tok_b = out_tokens + (int64_t)b * topk * T;
 	int* off_b = out_offsets + (int64_t)b * topk * T;
 	for (int64_t e = tid; e < (int64_t)topk * T; e += nth) {
 		const int k = (int)(e / T), p = (int)(e % T);
-		if (p >= (k < n ? len[k] : 0)) { tok_b[e] = 0; off_b[e] = 0; }
+		if (p >= (k < n ? len[LM ? sk[k] : k] : 0)) { tok_b[e] = 0; off_b[e] = 0; }
 	}
 	for (int k = tid; k < topk; k += nth) {
 		if (k < n) {
-			int p = len[k] - 1;
-			for (int nd = node[k]; nd >= 0 && p >= 0; --p) {
+			const int r = LM ? sk[k] : k;
+			int p = len[r] - 1;
+			for (int nd = node[r]; nd >= 0 && p >= 0; --p) {
 				const int2 v = arena[nd];
 				tok_b[(int64_t)k * T + p] = v.y;
 				off_b[(int64_t)k * T + p] = nd / W;
 				nd = v.x;
 			}
-			out_lengths[(int64_t)b * topk + k] = len[k];
-			out_logp[(int64_t)b * topk + k] = (float)tot[k];
+			out_lengths[(int64_t)b * topk + k] = len[r];
+			if constexpr (LM) ((double*)out_logp)[(int64_t)b * topk + k] = bs_undesc64(su[k]);
+			else ((float*)out_logp)[(int64_t)b * topk + k] = (float)tot[k];
 		} else {
 			out_lengths[(int64_t)b * topk + k] = 0;
-			out_logp[(int64_t)b * topk + k] = -INFINITY;
+			if constexpr (LM) ((double*)out_logp)[(int64_t)b * topk + k] = -INFINITY;
+			else ((float*)out_logp)[(int64_t)b * topk + k] = -INFINITY;
 		}
 	}
+}
+
+__global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
+                                                                int64_t* __restrict__ out_tokens, int* __restrict__ out_offsets,
+                                                                int64_t* __restrict__ out_lengths, float* __restrict__ out_logp,
+                                                                int2* __restrict__ arena_all, int T, int C, int blank, int W, int N,
+                                                                float cutoff_prob, int topk) {
+	const BsLm none{};
+	bs_body<false>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, T, C, blank, W, N, cutoff_prob, topk, none);
+}
+
+__global__ __launch_bounds__(1024) void ctc_beam_search_lm_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
+                                                                   int64_t* __restrict__ out_tokens, int* __restrict__ out_offsets,
+                                                                   int64_t* __restrict__ out_lengths, double* __restrict__ out_logp,
+                                                                   int2* __restrict__ arena_all, int T, int C, int blank, int W, int N,
+                                                                   float cutoff_prob, int topk, BsLm lm) {
+	bs_body<true>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, T, C, blank, W, N, cutoff_prob, topk, lm);
 }
 
 static const char* bs_envelope(int B, int T, int C, int W, int N, int topk, int* code) {
@@ -457,5 +637,54 @@ extern "C" int convasr_ctc_beam_search(const float* log_probs, const int64_t* le
 	hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(threads), Ly.bytes, (hipStream_t)stream, log_probs, lengths, tokens, offsets, out_lengths,
 	                   log_prob, (int2*)workspace, T, C, blank, W, N, cutoff_prob, topk);
 	CONVASR_CHECK_LAUNCH("ctc_beam_search");
+	return 0;
+}
+
+// ---- with an n-gram LM
+static const char* bs_lm_envelope(int B, int T, int C, int W, int N, int topk, int* code) {
+	if (const char* why = bs_envelope(B, T, C, W, N, topk, code)) return why;
+	*code = CONVASR_EUNSUPPORTED;
+	if (C > BS_LM_MAX_C) return "C > 256 is outside the envelope of the LM search";
+	const BsLayout Ly = bs_layout(W, N, C, true);
+	if (Ly.bytes > 160 * 1024) return "the beam state exceeds 160 KiB of LDS (LM search: see the header for the largest beam width per C and N)";
+	return nullptr;
+}
+
+extern "C" int64_t convasr_ctc_beam_search_lm_workspace_bytes(int B, int T, int C, int W, int N, int topk) {
+	int code;
+	if (const char* why = bs_lm_envelope(B, T, C, W, N, topk, &code))
+		return convasr_fail(code, "ctc_beam_search_lm: %s (B %d T %d C %d W %d N %d topk %d; %zu bytes of LDS)", why, B, T, C, W, N, topk, bs_layout(W, N, C, true).bytes);
+	return (int64_t)B * T * W * (int64_t)sizeof(int2);
+}
+
+extern "C" int convasr_ctc_beam_search_lm(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                          double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                                          const uint32_t* node_mask, const int32_t* node_child, const int32_t* node_word, int n_nodes,
+                                          const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
+                                          int space, int order, int start_state, double alpha, double beta, void* stream) {
+	CONVASR_CHECK_ARG(log_probs && lengths && tokens && offsets && out_lengths && log_prob && workspace, "ctc_beam_search_lm: NULL pointer");
+	CONVASR_CHECK_ARG(node_mask && node_child && node_word && ent_pb && ent_sl && slots, "ctc_beam_search_lm: NULL LM table");
+	int code;
+	if (const char* why = bs_lm_envelope(B, T, C, W, N, topk, &code))
+		return convasr_fail(code, "ctc_beam_search_lm: %s (B %d T %d C %d W %d N %d topk %d; %zu bytes of LDS)", why, B, T, C, W, N, topk, bs_layout(W, N, C, true).bytes);
+	CONVASR_CHECK_ARG(blank >= 0 && blank < C, "ctc_beam_search_lm: blank %d outside [0, %d)", blank, C);
+	CONVASR_CHECK_ARG(cutoff_prob > 0.f && cutoff_prob <= 1.f, "ctc_beam_search_lm: cutoff_prob must be in (0, 1]");
+	CONVASR_CHECK_ARG(space >= 0 && space < C && space != blank, "ctc_beam_search_lm: space class %d must be in [0, %d) and differ from the blank %d", space, C, blank);
+	CONVASR_CHECK_ARG(order >= 1 && order <= BS_LM_MAX_ORDER, "ctc_beam_search_lm: LM order %d outside [1, %d]", order, BS_LM_MAX_ORDER);
+	CONVASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "ctc_beam_search_lm: alpha and beta must be finite");
+	CONVASR_CHECK_ARG(n_nodes >= 1 && n_ent >= 1, "ctc_beam_search_lm: empty LM tables (%d trie nodes, %d n-gram entries)", n_nodes, n_ent);
+	CONVASR_CHECK_ARG(n_slots >= 1 && (n_slots & (n_slots - 1)) == 0, "ctc_beam_search_lm: n_slots %d is not a power of two", n_slots);
+	CONVASR_CHECK_ARG(start_state >= -1 && start_state < n_ent, "ctc_beam_search_lm: start state %d outside [-1, %d)", start_state, n_ent);
+	const BsLayout Ly = bs_layout(W, N, C, true);
+	const int threads = W <= 256 ? 256 : 1024;
+	static unsigned long long set = 0;
+	convasr_allow_160k_lds(reinterpret_cast<const void*>(ctc_beam_search_lm_kernel), set);
+	BsLm lm;
+	lm.node_mask = node_mask; lm.node_child = node_child; lm.node_word = node_word;
+	lm.ent_pb = (const double2*)ent_pb; lm.ent_sl = (const int2*)ent_sl; lm.slots = (const int4*)slots;
+	lm.n_slots = n_slots; lm.space = space; lm.order = order; lm.start = start_state; lm.alpha = alpha; lm.beta = beta;
+	hipLaunchKernelGGL(ctc_beam_search_lm_kernel, dim3(B), dim3(threads), Ly.bytes, (hipStream_t)stream, log_probs, lengths, tokens, offsets, out_lengths,
+	                   log_prob, (int2*)workspace, T, C, blank, W, N, cutoff_prob, topk, lm);
+	CONVASR_CHECK_LAUNCH("ctc_beam_search_lm");
 	return 0;
 }

@@ -1,13 +1,18 @@
 """The reference's decoders module (decoders.py:1-55) on the GPU.
 
 * GreedyDecoder: per-frame best class (K = 1: the convasr_argmax kernel), the reference's return form.
-* BeamSearchDecoder: CTC prefix beam search without a language model (convasr_ctc_beam_search, one workgroup per utterance, the frame
-  loop inside the kernel) in place of ctcdecode.CTCBeamDecoder.  No LM scorer exists here: lm_path must be None.
+* BeamSearchDecoder: CTC prefix beam search (convasr_ctc_beam_search, one workgroup per utterance, the frame loop inside the kernel) in
+  place of ctcdecode.CTCBeamDecoder; with lm_path an ARPA n-gram model is fused into the search (convasr_ctc_beam_search_lm, lm.NgramLM)
+  as ctcdecode's KenLM scorer is.  A KenLM binary model or any other non-ARPA path raises NotImplementedError.
 
 Scores: ctcdecode documents its beam scores as -log p, so the reference's decoded_scores.topk(topk) would pick the LEAST probable beams of
 its output (not verified against an installed ctcdecode).  This module returns the MOST probable beams, best first, and log p itself."""
+import math
+import os
+
 import torch
 
+from . import lm as lm_mod
 from . import ops
 
 
@@ -16,6 +21,19 @@ def _blank_of(labels):
 		if getattr(labels, name, None) is not None:
 			return int(getattr(labels, name))
 	raise ValueError('labels need a blank_idx (reference Labels) or an eps_id (tokenizer) attribute')
+
+
+def _labels_of(labels):
+	"""The label string, one character per class: a str, a tokenizer's idx2char / vocab, a `labels` attribute, or str(labels)."""
+	if isinstance(labels, str):
+		return labels
+	for name in ('idx2char', 'vocab', 'labels'):
+		v = getattr(labels, name, None)
+		if v is not None and not callable(v):
+			if not isinstance(v, str) and not all(isinstance(x, str) and len(x) == 1 for x in v):
+				raise ValueError(f'BeamSearchDecoder: the labels {name} are not one character per class: an LM needs character labels')
+			return ''.join(v)
+	return str(labels)
 
 
 def _lengths(output_lengths, log_probs):
@@ -35,21 +53,40 @@ class GreedyDecoder:
 
 
 class BeamSearchDecoder:
-	"""decoders.BeamSearchDecoder without a language model.  beam_width <= 1024, cutoff_top_n <= 128 (None or more than C: C), C <= 8192; outside
-	that envelope decode() raises (the reference transcribe.py's default --beam-width 5000 among them).  beam_alpha / beam_beta weigh the
-	LM and are ignored; num_workers is the reference's CPU thread count and has no meaning here.  beam_width is required, as in the reference
-	(it is a keyword here only because lm_path got a default).  The search runs on the GPU only: log_probs must be a CUDA tensor."""
+	"""decoders.BeamSearchDecoder.  beam_width <= 1024, cutoff_top_n <= 128 (None or more than C: C), C <= 8192; outside that envelope decode()
+	raises (the reference transcribe.py's default --beam-width 5000 among them).  num_workers is the reference's CPU thread count and has no
+	meaning here.  beam_width is required, as in the reference (it is a keyword here only because lm_path got a default).  The search runs on
+	the GPU only: log_probs must be a CUDA tensor.
+
+	lm_path: None (no LM; beam_alpha / beam_beta are ignored), the path of an ARPA text file, or an lm.NgramLM already built for these
+	labels (one model for many decoders).  With an LM the labels (a string, or a tokenizer / Labels object whose idx2char, vocab or str()
+	gives one character per class, lowercased) need exactly one space, which is not the blank; C <= 256; beam_alpha and beam_beta weigh
+	the LM term alpha * ln P(word | context) + beta, and the returned scores are the fused log p (include/convasr_hip.h).  A path that
+	cannot be read as ARPA text (a KenLM binary among them) raises NotImplementedError."""
 
 	def __init__(self, labels, lm_path = None, beam_width = None, beam_alpha = 0, beam_beta = 0, cutoff_top_n = 40, cutoff_prob = 1.0, num_workers = 1, topk = 1):
-		if lm_path is not None:
-			raise NotImplementedError(f'BeamSearchDecoder: lm_path = {lm_path!r}, but there is no language-model scorer in convasr_amd (LM-free beam search only)')
+		self.lm = None
+		if lm_path is not None and not isinstance(lm_path, lm_mod.NgramLM):
+			arpa = lm_path if isinstance(lm_path, lm_mod.Arpa) else lm_mod.read_arpa(os.fspath(lm_path))  # (NotImplementedError for a non-ARPA path)
+			lm_path = lm_mod.NgramLM(arpa, _labels_of(labels))
 		if beam_width is None:
 			raise TypeError('BeamSearchDecoder: beam_width is required')
 		self.blank = _blank_of(labels)
 		self.beam_width, self.cutoff_top_n, self.cutoff_prob, self.topk = int(beam_width), cutoff_top_n, float(cutoff_prob), int(topk)
+		if lm_path is not None:
+			if lm_path.space == self.blank:
+				raise ValueError(f'BeamSearchDecoder: the space class {lm_path.space} is the blank')
+			self.alpha, self.beta = float(beam_alpha), float(beam_beta)
+			if not (math.isfinite(self.alpha) and math.isfinite(self.beta)):
+				raise ValueError(f'BeamSearchDecoder: beam_alpha {beam_alpha} and beam_beta {beam_beta} must be finite')
+			lm_path.tables(self.blank)  # (the vocabulary's ValueError / NotImplementedError, here rather than at the first decode)
+			self.lm = lm_path
 
 	def decode_with_scores(self, log_probs, output_lengths = None):
-		"""(tokens (B, topk, T) int64, offsets (B, topk, T) int32 frames, lengths (B, topk) int64, log_prob (B, topk) fp32), best first."""
+		"""(tokens (B, topk, T) int64, offsets (B, topk, T) int32 frames, lengths (B, topk) int64, log_prob (B, topk)), best first; log_prob is
+		fp32 log p without an LM, fp64 fused log p with one."""
+		if self.lm is not None:
+			return ops.ctc_beam_search_lm(log_probs, output_lengths, self.blank, self.beam_width, self.lm, self.alpha, self.beta, self.cutoff_top_n, self.cutoff_prob, self.topk)
 		return ops.ctc_beam_search(log_probs, output_lengths, self.blank, self.beam_width, self.cutoff_top_n, self.cutoff_prob, self.topk)
 
 	def decode(self, log_probs, output_lengths = None):

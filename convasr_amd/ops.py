@@ -885,3 +885,36 @@ def ctc_beam_search(log_probs_bct, lengths, blank, beam_width, cutoff_top_n = 40
 	ws = torch.empty(nbytes, dtype = torch.uint8, device = dev)  # per call, not the grow-only cache: B x T x W nodes of 8 bytes (393 MB at 64 x 750 x 1024) go back to the allocator
 	call('convasr_ctc_beam_search', ptr(lp), ptr(lengths), ptr(tokens), ptr(offsets), ptr(out_lengths), ptr(log_prob), ptr(ws), B, T, C, int(blank), W, N, float(cutoff_prob), topk, stream_ptr())
 	return tokens, offsets, out_lengths, log_prob
+
+
+def ctc_beam_search_lm(log_probs_bct, lengths, blank, beam_width, lm, alpha, beta, cutoff_top_n = 40, cutoff_prob = 1.0, topk = 1):
+	"""CTC prefix beam search fused with an n-gram LM (include/convasr_hip.h: convasr_ctc_beam_search_lm).  lm: an lm.NgramLM built for
+	the C labels of log_probs_bct (its tables are uploaded to the device once and kept by the model); alpha / beta weigh the LM term.
+	Inputs and outputs as ctc_beam_search, except log_prob: (B, topk) fp64, the fused score lpb + lpnb + F (best first).  Outside the
+	kernel's envelope (that of ctc_beam_search plus C <= 256 and the LDS budget, see the header) it raises ConvasrHipError."""
+	require_cuda(log_probs_bct)
+	B, C, T = log_probs_bct.shape
+	if C != lm.num_classes:
+		raise ValueError(f'ctc_beam_search_lm: {C} classes, but the language model was built for {lm.num_classes} labels')
+	if lm.space == int(blank):
+		raise ValueError(f'ctc_beam_search_lm: the space class {lm.space} is the blank')
+	lp = as_cl(log_probs_bct, torch.float32)
+	dev = lp.device
+	lengths = torch.full((B,), T, dtype = torch.int64, device = dev) if lengths is None else torch.as_tensor(lengths).to(device = dev, dtype = torch.int64).contiguous()
+	if lengths.shape != (B,):
+		raise ValueError(f'ctc_beam_search_lm: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
+	N = C if cutoff_top_n is None else min(int(cutoff_top_n), C)
+	W, topk = int(beam_width), int(topk)
+	nbytes = _lib.load().convasr_ctc_beam_search_lm_workspace_bytes(B, T, C, W, N, topk)
+	if nbytes < 0:
+		raise _lib.ConvasrHipError(_lib.load().convasr_last_error().decode())
+	t = lm.device_tables(int(blank), dev)
+	tokens = torch.empty(B, topk, T, dtype = torch.int64, device = dev)
+	offsets = torch.empty(B, topk, T, dtype = torch.int32, device = dev)
+	out_lengths = torch.empty(B, topk, dtype = torch.int64, device = dev)
+	log_prob = torch.empty(B, topk, dtype = torch.float64, device = dev)
+	ws = torch.empty(nbytes, dtype = torch.uint8, device = dev)
+	call('convasr_ctc_beam_search_lm', ptr(lp), ptr(lengths), ptr(tokens), ptr(offsets), ptr(out_lengths), ptr(log_prob), ptr(ws), B, T, C, int(blank), W, N,
+	     float(cutoff_prob), topk, ptr(t['node_mask']), ptr(t['node_child']), ptr(t['node_word']), int(t['node_word'].numel()), ptr(t['ent_pb']), ptr(t['ent_sl']),
+	     int(t['ent_sl'].shape[0]), ptr(t['slots']), int(t['slots'].shape[0]), lm.space, lm.order, lm.start_state, float(alpha), float(beta), stream_ptr())
+	return tokens, offsets, out_lengths, log_prob

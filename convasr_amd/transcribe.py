@@ -3,7 +3,8 @@
 * setup(args) -> (text_pipeline, frontend, model, generator)                          transcribe.py:23-60
   checkpoint -> frontend + model (the reference's class names / state-dict keys) -> eval() -> fuse_conv_bn_eval() ->
   compute dtype from args.fp16 (None / 'O0': exact fp32; 'O1'..'O3': fp16 storage + MFMA as under apex.amp, or bf16 when models.AMP_DTYPE says so) -> greedy generator,
-  or with args.decoder = 'BeamSearchDecoder' the CTC prefix beam search (args.beam_width, args.decoder_topk; no language model).
+  or with args.decoder = 'BeamSearchDecoder' the CTC prefix beam search (args.beam_width, args.decoder_topk; args.lm an ARPA n-gram model
+  weighed by args.beam_alpha / args.beam_beta).
 * transcribe_batch(...)                                                                transcribe.py:140-200
   the per-batch body of transcribe.main: forward (every op a HIP kernel; the argmax of the greedy decode too), per-frame time
   stamps, GreedyCTCGenerator with time stamps (one segment per word), optional forced alignment of the reference text
@@ -72,8 +73,9 @@ def setup(args):
 			models.master_module(model).set_compute_dtype(level, inference = True)
 		else:
 			model, *_ = models.data_parallel_and_autocast(model, opt_level = level)
-	if getattr(args, 'decoder', None) == 'BeamSearchDecoder':  # transcribe.py:323-327: --decoder, --beam-width, --decoder-topk, --lm (no LM scorer here: --lm raises)
-		generator = BeamCTCGenerator(beam_width = args.beam_width, topk = getattr(args, 'decoder_topk', 1), lm_path = getattr(args, 'lm', None))
+	if getattr(args, 'decoder', None) == 'BeamSearchDecoder':  # transcribe.py:323-328: --decoder, --beam-width, --decoder-topk, --lm (an ARPA file), --beam-alpha, --beam-beta
+		generator = BeamCTCGenerator(beam_width = args.beam_width, topk = getattr(args, 'decoder_topk', 1), lm_path = getattr(args, 'lm', None),
+		                             beam_alpha = getattr(args, 'beam_alpha', 0), beam_beta = getattr(args, 'beam_beta', 0))
 	else:
 		generator = GreedyCTCGenerator()
 	return text_pipeline, frontend, model, generator

@@ -101,19 +101,33 @@ class GreedyCTCGenerator:
 
 class BeamCTCGenerator:
 	"""GreedyCTCGenerator's interface over the CTC prefix beam search (convasr_ctc_beam_search; the reference's transcribe.py
-	--decoder BeamSearchDecoder, without a language model).  Per utterance it returns topk alternatives, best first; each is a Transcript
+	--decoder BeamSearchDecoder; with lm_path an ARPA n-gram model fused as --lm / --beam-alpha / --beam-beta do, convasr_ctc_beam_search_lm,
+	the labels being the tokenizer's characters).  Per utterance it returns topk alternatives, best first; each is a Transcript
 	of word segments built from that beam's tokens: leading silence tokens are skipped, a new segment starts at every word-start token
 	when time stamps are given, and a token's time is begin + time_stamps[its frame offset].  GPU only: log_probs must be a CUDA tensor
 	(GreedyCTCGenerator also decodes CPU tensors); for the one-hot targets of --align, transcribe_batch uses a GreedyCTCGenerator."""
 
-	def __init__(self, beam_width = 64, topk = 1, cutoff_top_n = 40, cutoff_prob = 1.0, lm_path = None):
-		from . import decoders
+	def __init__(self, beam_width = 64, topk = 1, cutoff_top_n = 40, cutoff_prob = 1.0, lm_path = None, beam_alpha = 0, beam_beta = 0):
+		from . import decoders, lm
 		self.topk = int(topk)
-		self.decoder = lambda blank: decoders.BeamSearchDecoder(types.SimpleNamespace(blank_idx = blank), lm_path = lm_path, beam_width = beam_width, cutoff_top_n = cutoff_top_n, cutoff_prob = cutoff_prob, topk = topk)
-		self.decoder(0)  # (an lm_path raises here, at setup)
+		kw = dict(beam_width = beam_width, cutoff_top_n = cutoff_top_n, cutoff_prob = cutoff_prob, topk = topk)
+		if lm_path is None:
+			self.decoder = lambda tokenizer: decoders.BeamSearchDecoder(types.SimpleNamespace(blank_idx = tokenizer.eps_id), **kw)
+			self.decoder(types.SimpleNamespace(eps_id = 0))
+			return
+		model = lm_path if isinstance(lm_path, lm.NgramLM) else lm.read_arpa(lm_path)  # (a non-ARPA path raises here, at setup)
+		decs = {}
+
+		def decoder(tokenizer):  # one decoder (and one set of LM tables) per tokenizer alphabet
+			labels = ''.join(tokenizer.vocab)
+			if (labels, tokenizer.eps_id) not in decs:
+				decs[labels, tokenizer.eps_id] = decoders.BeamSearchDecoder(types.SimpleNamespace(eps_id = tokenizer.eps_id, idx2char = tokenizer.vocab), lm_path = model,
+				                                                            beam_alpha = beam_alpha, beam_beta = beam_beta, **kw)
+			return decs[labels, tokenizer.eps_id]
+		self.decoder = decoder
 
 	def generate(self, tokenizer, log_probs, begin, end, output_lengths = None, time_stamps = None, segment_text_key = 'hyp', segment_extra_info = None):
-		tokens, offsets, lengths, _ = self.decoder(tokenizer.eps_id).decode_with_scores(log_probs, output_lengths)
+		tokens, offsets, lengths, _ = self.decoder(tokenizer).decode_with_scores(log_probs, output_lengths)
 		tokens, offsets, lengths = tokens.cpu().tolist(), offsets.cpu().tolist(), lengths.cpu().tolist()
 		ts_all = time_stamps.cpu().tolist() if time_stamps is not None else None
 		begin = torch.clamp(begin, min = 0.0).cpu().tolist() if time_stamps is not None else begin.cpu().tolist()

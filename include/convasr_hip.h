@@ -537,6 +537,44 @@ int convasr_ctc_beam_search(const float* log_probs, const int64_t* lengths, int6
                             float* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
                             void* stream);
 
+/* ---- CTC prefix beam search with an n-gram language model: decoders.py:19-55 (BeamSearchDecoder, ctcdecode.CTCBeamDecoder with a KenLM
+ * Scorer), train.py:975-995 / transcribe.py:323-328 (--lm, --beam-alpha, --beam-beta).  The model comes from an ARPA text file; the
+ * tables are built on the host by convasr_amd/lm.py (NgramLM, which documents their layout) and the C side keeps no state.
+ * Everything not stated here is as in convasr_ctc_beam_search above: candidate rules, merging, tie keys, top-N / cutoff_prob, fp64
+ * scores, the output layout (log_prob is fp64 here).  The rules, modelled on ctcdecode's Scorer and PathTrie:
+ *   labels: one character per class, lowercased; the space class s is the one labelled ' ' (exactly one; s != blank).
+ *   ARPA: \data\ counts, \N-grams: sections, \end\; each entry log10 p, the n-gram, an optional log10 backoff weight (missing: 0);
+ *   order 1 <= N_lm <= 6.  An n-gram whose context (first N - 1 words) is not listed is refused (lm.py raises ValueError).
+ *   V: the unigrams other than <s>, </s>, <unk> whose characters all map to labels other than the blank and s.  Empty V: ValueError;
+ *   every word of V one character (ctcdecode's character-LM mode): NotImplementedError.
+ *   log10 P(w | h): the listed probability of (h, w) when the model lists it, otherwise bow(h) + log10 P(w | h[1:]) (bow = 0 when h is
+ *   not listed).  The context of a word = the words completed before it in the prefix, truncated to N_lm - 1; with fewer, one <s> in
+ *   front.  LM term = alpha * ln P(w | ctx) + beta, ln = log10 * ln 10.
+ *   cw(l) = the label characters after the last space of l.
+ *   Dictionary constraint: an extension l + c (c not blank / s; c != last(l), or c == last(l) from lpb(l)) exists only if cw(l) + labels[c]
+ *   is a prefix of a word in V; l + s exists only if cw(l) is non-empty and in V (no leading space, no two spaces in a row).
+ *   Fusion: every contribution to nnb(l + s) -- from lpb(l), from lpnb(l), and an extension folded into a beam already held -- gets
+ *   the LM term of cw(l) added (the stay nnb(l) += lp + lpnb(l) of a beam ending in s does not); selection ranks by lpb + lpnb as before.
+ *   End of utterance: the hypotheses are ranked by lpb + lpnb + F(l) (ties: rank), F = 0 for an empty l or one ending in s, the LM term
+ *   of cw(l) when cw(l) is in V, alpha * -1000 + beta otherwise (ctcdecode's OOV_SCORE, unconverted); log_prob returns that score.
+ *   alpha = beta = 0 still applies the dictionary constraint: it is NOT the LM-free search.
+ *   A frame that leaves no candidate (no allowed class and no blank among P_t) ends the search without a hypothesis: every slot of the
+ *   utterance has length 0 and log_prob -inf.
+ * Known divergences from ctcdecode (not compared against ctcdecode itself, which was not available):
+ *   - no min_cutoff early exit: selection stays the exact top W;
+ *   - scores are the fused log p, not ctcdecode's "approximate CTC" score with the LM removed and negated;
+ *   - no </s> term at the end of the utterance.
+ * Envelope, checked before any launch: that of convasr_ctc_beam_search, plus C <= 256, 1 <= order <= 6, s in [0, C) and s != blank,
+ * finite alpha and beta, n_nodes >= 1, n_ent >= 1, n_slots a power of two, -1 <= start_state < n_ent, and the beam state within
+ * 160 KiB of LDS: W = 1024 fits for every C <= 256 at N <= 64 and for C <= 160 at N = 128; at C = 256, N = 128 it would need 166,992
+ * bytes and the largest W is 1001.  Outside the envelope CONVASR_EINVAL / CONVASR_EUNSUPPORTED. */
+int64_t convasr_ctc_beam_search_lm_workspace_bytes(int B, int T, int C, int W, int N, int topk);
+int convasr_ctc_beam_search_lm(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                               double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                               const uint32_t* node_mask, const int32_t* node_child, const int32_t* node_word, int n_nodes,
+                               const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
+                               int space, int order, int start_state, double alpha, double beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
