@@ -1,6 +1,6 @@
 """bench.py -- BASELINE.json's headline metric on the MI355X-native path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload wav2letter|jasper_large] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload wav2letter|jasper_large] [--dump-outputs DIR] [--full]
 
 N > 1 without WORLD_SIZE in the environment: this process touches no GPU and starts its own N ranks as a CHILD
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`, the role of train.py:1057-1073's mp.spawn), relays rank 0's
@@ -18,7 +18,12 @@ dropout 0.2, SGD (--dtype f16: fp16 storage + MFMA under apex's dynamic loss sca
 residuals), 32 utterances of 5-20 s per batch from BucketingBatchSampler -> collate_gpu (mixed lengths, bucketed as
 train.py:597-601), fp16 under apex O2 loss scaling, NovoGrad.
 
-Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0; its `parity` object is the second half of
+Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps,
+writes --dump-outputs and prints the line: the headline (metric, value, unit, ms_per_step), the dominant kernel's roofline figures from the
+events inside the timed region, the device state over it and, with N > 1, the data-parallel figures.  Everything that takes runs of its
+own is measured only with --full: the second, event-timed pass (wgrad / conv_stack / hbm_kernels, ABI calls per step), the host enqueue
+time, the eager reference region of a graph-replayed step, roofline.traffic, the other compute types, the jasper_large leg, the CPU
+baseline and `parity`.  With --full the `parity` object is the second half of
 BASELINE's metric: the per-utterance CTC losses of every GPU compute type relative to the CPU oracle on BASELINE configs[2]'s own batch
 (64 x 15 s, lengths linspace(0.5, 1): the maximum over the 64 utterances) and on the 4-utterance sample the cpu_baseline leg runs anyway,
 plus, for a bf16 headline, short timed regions of the same workload in the other compute types on the same device: fp16 (apex O2;
@@ -69,6 +74,8 @@ def parse_args(argv = None):
 	ap.add_argument('--dropout', type = float, default = 0.2, help = 'the reference default (train.py:1033) is 0.2; other values are for experiments only')
 	ap.add_argument('--batch', type = int, default = None, help = 'TEST ONLY: utterances per GPU (a line measured with it is not the headline)')
 	ap.add_argument('--secs', type = int, default = None, help = 'TEST ONLY: seconds per utterance (wav2letter)')
+	ap.add_argument('--full', action = 'store_true', help = 'also measure what takes runs of its own: the second, event-timed pass and the host enqueue time, the eager reference region of '
+		'a graph-replayed step, roofline.traffic, the fp16 / bf16x3 / bf16x3f / fp32 legs, the jasper_large leg, cpu_baseline and parity (the --no-* options below leave parts of it out)')
 	ap.add_argument('--no-cpu-baseline', action = 'store_true')
 	ap.add_argument('--no-kernel-timer', action = 'store_true')
 	ap.add_argument('--no-f16-leg', action = 'store_true', help = 'skip the second timed region in fp16 (parity.f16_value)')
@@ -83,7 +90,7 @@ def parse_args(argv = None):
 			'ceiling (one shape per bucket).  auto: on for jasper_large with one rank (~530 launches and ~19 ms of Python per ~38 ms step; a replay costs the host ~0.4 ms, and the replayed step itself is ~2 %% slower than the eager one '
 			'with the wgrad side stream, whose time the line also reports), off for wav2letter (~110 launches, GPU-bound either way: +-0 measured, and the dominant kernel stays event-timed '
 			'inside the timed region) and for N > 1 (RCCL has not run under capture on this pool).  With graphs on, per-kernel HIP-event durations come from the second, eager pass')
-	ap.add_argument('--no-jasper-leg', action = 'store_true', help = 'skip the bounded BASELINE configs[4] leg (extra.jasper_large) of the default line')
+	ap.add_argument('--no-jasper-leg', action = 'store_true', help = 'skip the bounded BASELINE configs[4] leg (extra.jasper_large) of the --full line')
 	ap.add_argument('--dump-outputs', metavar = 'DIR', default = None, help = 'after the timed steps, write what the last timed step computed as DIR/<name>.npy: its scalars (loss, loss_cur, entropy, grad_norm, skipped; '
 		'float64) and a fixed, seeded sample of the updated fp32 parameter arena (float32, with its indices in float64); under 64 MB in all.  Rank 0 only')
 	ap.add_argument('--launcher-dry-run', action = 'store_true', help = 'test hook: ranks only rendezvous (gloo, CPU tensors) and rank 0 prints a line; exercises the self-launch path without a GPU')
@@ -519,7 +526,7 @@ def measure_traffic(args, sequence, steps):
 		try:
 			cmd = [exe, '--kernel-trace', '--pmc', counter, '--output-format', 'csv', '-d', d, '--', sys.executable, os.path.abspath(__file__),
 				'--steps', '1', '--warmup', '1', '--workload', args.workload, '--dtype', args.dtype, '--dropout', str(args.dropout),
-				'--no-cpu-baseline', '--no-kernel-timer', '--no-traffic', '--no-f16-leg', '--no-parity-legs', '--no-jasper-leg', '--graph', 'off', '--side-stream', 'off']
+				'--full', '--no-cpu-baseline', '--no-kernel-timer', '--no-traffic', '--no-f16-leg', '--no-parity-legs', '--no-jasper-leg', '--graph', 'off', '--side-stream', 'off']
 			r = subprocess.run(cmd, cwd = '/tmp', env = env, stdout = subprocess.PIPE, stderr = subprocess.PIPE, text = True, timeout = 600)
 			files = glob.glob(os.path.join(d, '**', '*counter_collection.csv'), recursive = True)
 			if r.returncode != 0 or not files:
@@ -572,7 +579,7 @@ def dry_run_rank(args):
 
 def roofline_of(args, wl, kt, kt2, steps2, value, world, graphed = False):
 	"""The `roofline` object: the dominant kernel from the HIP events of the timed region (kt), every other family from the second
-	pass (kt2, steps2 steps), all from algorithmic FLOPs / bytes booked per launch by convasr_amd.ops."""
+	pass (kt2, steps2 steps; none without --full), all from algorithmic FLOPs / bytes booked per launch by convasr_amd.ops."""
 	main_name, fused_name = MAIN_FAMILY, MAIN_FAMILY + '+bn_bwd'
 	split = wl.dtype in SPLIT_DTYPES
 	half = wl.dtype in ('bf16', 'f16') or split  # (priced against the 16-bit dense MFMA peak)
@@ -615,7 +622,8 @@ def roofline_of(args, wl, kt, kt2, steps2, value, world, graphed = False):
 		algorithmic_mb_per_launch = round(k['bytes'] / k['launches'] / 1e6, 1), launches_per_step = k['launches'] // args.steps, avg_launch_us = round(k['avg_us'], 2),
 		ms_per_step = round(k['total_ms'] / args.steps, 3),
 		timing = (f'HIP events on the launching stream around every launch, in a second pass of {steps2} steps right after the timed region (the timed region ' + ('replays the step from HIP graphs' if graphed else 'runs wgrad on a side stream') + ': no launch of it can be bracketed, and overlapped launches would inflate each other\'s durations; the second pass launches the same kernels eagerly on one stream)'
-			if second_pass_main else f'HIP events on the launching stream around every launch of this kernel inside the timed region ({args.steps} steps); wgrad / conv_stack / hbm_kernels: the same way in a second pass of {steps2} steps right after it'))
+			if second_pass_main else f'HIP events on the launching stream around every launch of this kernel inside the timed region ({args.steps} steps); ' +
+			(f'wgrad / conv_stack / hbm_kernels: the same way in a second pass of {steps2} steps right after it' if steps2 else 'wgrad / conv_stack / hbm_kernels: measured with --full only')))
 	hbm = {name[4:]: v for name, v in kt.items() if name.startswith('hbm:')}
 	kt = {name: v for name, v in kt.items() if not name.startswith('hbm:')}
 	if plain is not None and plain is not k:
@@ -631,13 +639,15 @@ def roofline_of(args, wl, kt, kt2, steps2, value, world, graphed = False):
 		w = kt[wname]
 		roof['wgrad'] = dict(kernel = 'conv1d_wgrad_v2_kernel incl. its split-K combine' + (' over the hi plane of the saved planes, read in place (frames 3 Cin elements apart), x the 16-bit dy: one product' if hi_bwd else ' over the planes read as 3 T frames (three MFMAs per product: executed = 3 x achieved)' if split else ' (+ general wgrad kernel on small layers)'), achieved = round(tf(w), 2), frac = round(tf(w) / peak, 4),
 			launches_per_step = w['launches'] // args.steps, avg_launch_us = round(w['avg_us'], 2), ms_per_step = round(w['total_ms'] / args.steps, 3))
+	roof['whole_step_frac'] = round(value / world / (peak * 1e12), 4)  # (value here: algorithmic conv FLOP/s of the whole job)
+	if not steps2:  # (no second pass: the dominant kernel alone was timed)
+		return roof
 	allc = list(kt.values())
 	stack = sum(v['work'] for v in allc) / (sum(v['total_ms'] for v in allc) * 1e-3) / 1e12
 	roof['conv_stack'] = dict(achieved = round(stack, 2), ms_per_step = round(sum(v['total_ms'] for v in allc) / args.steps, 3), frac = round(stack / peak, 4))
 	if split:  # the MFMA work the stack EXECUTES: three products per algorithmic FLOP in the split-operand launches, one in the others ('...x3f': the backward)
 		executed = sum(v['work'] * (3.0 if name in (SPLIT_FAMILY, SPLIT_WGRAD_FAMILY) else 1.0) for name, v in kt.items())
 		roof['conv_stack']['executed_mfma_frac'] = round(executed / (sum(v['total_ms'] for v in allc) * 1e-3) / 1e12 / peak, 4)
-	roof['whole_step_frac'] = round(value / world / (peak * 1e12), 4)  # (value here: algorithmic conv FLOP/s of the whole job)
 	# the HBM-bound kernels of the path (frontend, BN + activation passes): algorithmic bytes / HIP-event time against 8 TB/s
 	gbs = lambda v: v['bytes'] / (v['total_ms'] * 1e-3) / 1e9
 	roof['hbm_kernels'] = {name: dict(achieved = round(gbs(v), 1), peak = PEAK_HBM_GBS, unit = 'GB/s', frac = round(gbs(v) / PEAK_HBM_GBS, 4),
@@ -771,8 +781,8 @@ def dump_outputs(out_dir, res, flat):
 
 
 def measure(args, device, rank, world, use_dist, dist_info, fence, probe = None, dump_dir = None):
-	"""One workload on this rank: W warm-up steps (+ the untimed priming of the step graphs), K timed steps between two fences, the
-	second (event-timed, eager) pass.  dump_dir: --dump-outputs of the timed region's last step (taken before the second pass steps on).  Returns (the JSON line as a dict -- rank 0 only, else None --, rank 0's launch sequence of one step)."""
+	"""One workload on this rank: W warm-up steps (+ the untimed priming of the step graphs), K timed steps between two fences and, with
+	--full, the host-time steps and the second (event-timed, eager) pass.  dump_dir: --dump-outputs of the timed region's last step (taken before the second pass steps on).  Returns (the JSON line as a dict -- rank 0 only, else None --, rank 0's launch sequence of one step)."""
 	import torch
 	import torch.distributed as dist
 	import convasr_amd as ca
@@ -806,16 +816,17 @@ def measure(args, device, rank, world, use_dist, dist_info, fence, probe = None,
 			note = 'every timed step is one hipGraphLaunch of the whole iteration (forward, CTC, backward, clip, optimizer), one graph per batch shape; the per-step inputs are copied into the graph\'s static buffers inside the timed region')
 	# host time of a step with the GPU drained first (the enqueue never waits for queue space): how far ahead of the GPU the Python side
 	# can run.  Eagerly the Wav2Letter step needs ~4 ms of it for 16 ms of GPU work and a JasperNetLarge step ~20 ms for ~44 (1,200 launches:
-	# one busy neighbour away from host-bound); replayed from a graph a step is a handful of calls.
+	# one busy neighbour away from host-bound); replayed from a graph a step is a handful of calls.  This and every other step after the
+	# timed region run with --full only.
 	host_ms = []
-	for i in range(3):
+	for i in range(3 if args.full else 0):
 		torch.cuda.synchronize()
 		h0 = time.perf_counter()
 		step(args.warmup + args.steps + i)
 		host_ms.append((time.perf_counter() - h0) * 1e3)
 	fence()
 	eager_info = None
-	if graphed:
+	if graphed and args.full:
 		# the same steps launched eagerly with the weight gradients on the side stream (what --graph off times): a short reference region
 		wl.stepper.enabled = False
 		ca.functional.enable_side_stream_wgrad(device, True)
@@ -837,7 +848,7 @@ def measure(args, device, rank, world, use_dist, dist_info, fence, probe = None,
 	ca.functional.enable_side_stream_wgrad(device, False)  # the event-timed pass below runs every kernel alone on the main stream, eagerly
 	if wl.stepper is not None:
 		wl.stepper.enabled = False
-	if not args.no_kernel_timer:
+	if args.full and not args.no_kernel_timer:
 		steps2 = min(args.steps, 5)
 		if rank == 0:
 			_lib.timer = _lib.KernelTimer()
@@ -882,7 +893,7 @@ def measure(args, device, rank, world, use_dist, dist_info, fence, probe = None,
 		line = dict(metric = metric, value = round(value, 1), unit = 'audio-seconds/sec', n_gpus = world, steps = args.steps, warmup = args.warmup,
 			ms_per_step = round(1e3 * elapsed / args.steps, 3), higher_is_better = True, scaling = 'weak', vs_baseline = None, dtype = args.dtype, data = 'synthetic',
 			config = dict(workload = wl.name, global_batch = wl.batch * world, parallelism = f'dp{world}', side_stream_wgrad = bool(args.side_stream), step_graphs = graph_info,
-				host_enqueue_ms_per_step = round(sorted(host_ms)[1], 2), abi_calls_per_eager_step = None if calls2 is None else round(calls2, 1),
+				host_enqueue_ms_per_step = round(sorted(host_ms)[1], 2) if host_ms else None, abi_calls_per_eager_step = None if calls2 is None else round(calls2, 1),
 				whole_step_frac = round(conv_flops_per_s / world / (PEAK_F32_MFMA if args.dtype == 'f32' else PEAK_BF16_DENSE), 4), whole_step_tflops = round(conv_flops_per_s / world / 1e12, 1), eager_side_stream = eager_info, device_state = device_state,
 				peak_hbm_gib = round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 2)),  # (this measure()'s allocations: parameters, arena, activations, workspaces, graph pool -- of the card's 288)
 			loss = round(float(last['loss']), 4), loss_scaler = scaler_info, dist = dist_info, roofline = roof, parity = None)
@@ -962,13 +973,13 @@ def main(argv = None):
 	if use_dist:
 		dist.destroy_process_group()
 	if rank == 0:
-		# the legs below start child processes / use the host cores (measure() released model, optimizer state and workspaces)
+		# the legs below (--full only) start child processes / use the host cores (measure() released model, optimizer state and workspaces)
 		roof = line['roofline']
-		if world == 1 and roof is not None and args.dtype in ('bf16', 'f16') and not args.no_traffic:
+		if args.full and world == 1 and roof is not None and args.dtype in ('bf16', 'f16') and not args.no_traffic:
 			roof['traffic'], roof['traffic_source'] = measure_traffic(args, sequence, args.steps)  # (None + the reason when the counters could not be collected: no stale fallback)
 		f16_leg = None
 		headline_run = args.workload == 'wav2letter' and args.batch is None and args.secs is None and args.dtype == 'bf16'
-		if world == 1 and args.dtype == 'bf16' and not args.no_f16_leg and args.workload == 'wav2letter':
+		if args.full and world == 1 and args.dtype == 'bf16' and not args.no_f16_leg and args.workload == 'wav2letter':
 			# the same workload in fp16 (what the reference's apex O1-O3 levels compute in; 2.0e-4 in the CTC loss at 64 x 15 s, above north_star's 1e-4: parity.ctc_loss_rel_err): its own model / arena / optimizer / loss scaler
 			# (at least 8 warm-up steps here: apex's dynamic scale starts at 2^16 and halves once per overflowed step until the gradients
 			# of this random-data workload fit -- that search belongs to the warm-up, not to the timed region)
@@ -986,7 +997,7 @@ def main(argv = None):
 				torch.cuda.synchronize()
 				torch.cuda.empty_cache()
 		parity_legs = {}
-		if world == 1 and headline_run and not args.no_parity_legs:
+		if args.full and world == 1 and headline_run and not args.no_parity_legs:
 			# the same workload on the two paths that meet north_star's 1e-4, each its own model / arena / optimizer, right after the headline on the
 			# same device: bf16x3 (split-operand convs at MFMA rate) and exact fp32 (v_mfma_f32: ~0.2 s per step, three timed steps)
 			for name, steps, warmup, timer_off in (('bf16x3', min(args.steps, 10), 2, False), ('bf16x3f', min(args.steps, 10), 2, False), ('f32', min(args.steps, 3), 1, True)):
@@ -1015,7 +1026,7 @@ def main(argv = None):
 					_lib.timer = None
 					torch.cuda.synchronize()
 					torch.cuda.empty_cache()
-		if world == 1 and headline_run and not args.no_jasper_leg:
+		if args.full and world == 1 and headline_run and not args.no_jasper_leg:
 			# BASELINE configs[4] in the driver's record: `bench.py --workload jasper_large --steps 12 --warmup 3` as a bounded leg (the step's efficiency depends on the mix of bucket lengths: the same 12 batches as the stand-alone line)
 			argsj = argparse.Namespace(**dict(vars(args), workload = 'jasper_large', dtype = 'f16', steps = 12, warmup = 3, side_stream = True, no_kernel_timer = False, graph = graph_policy(args.graph_opt, 'jasper_large', args.gpus)))
 			# (a leg must never cost the headline its line: a failure -- e.g. a runtime that cannot capture the step -- is recorded, and the replayed leg falls back to the eager step)
@@ -1049,8 +1060,8 @@ def main(argv = None):
 					host_enqueue_ms_per_step = lj['config']['host_enqueue_ms_per_step'], eager_side_stream = lj['config']['eager_side_stream'], abi_calls_per_eager_step = lj['config']['abi_calls_per_eager_step'], step_graphs = lj['config']['step_graphs'],
 					side_stream_wgrad = True, batch_shapes_in_timed_region = lj['config'].get('batch_shapes_in_timed_region'), padding_overhead = lj['config'].get('padding_overhead'),
 					loss_scaler = lj['loss_scaler'], device_state = lj['config']['device_state'], peak_hbm_gib = lj['config'].get('peak_hbm_gib'), workload = lj['config']['workload'],
-						note = 'BASELINE configs[4] (JasperNetLarge, 32 x 5-20 s bucketed, fp16, NovoGrad) as a bounded leg of the default line: the same 12 batches as python bench.py --workload jasper_large --steps 12 --warmup 3' + (' -- ' + leg_note if leg_note else '')))
-		if world == 1 and not args.no_cpu_baseline:
+						note = 'BASELINE configs[4] (JasperNetLarge, 32 x 5-20 s bucketed, fp16, NovoGrad) as a bounded leg of the --full line: the same 12 batches as python bench.py --workload jasper_large --steps 12 --warmup 3' + (' -- ' + leg_note if leg_note else '')))
+		if args.full and world == 1 and not args.no_cpu_baseline:
 			ref = {}
 			line['cpu_baseline'] = cpu_baseline(keep = ref)
 			line['parity'] = gpu_parity(ref, device, ref_full = parity_reference() if headline_run else None)

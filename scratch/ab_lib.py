@@ -11,7 +11,7 @@ res = {n: [] for n in names}
 for r in range(rounds):
 	for n in names:
 		env = dict(os.environ, CONVASR_HIP_LIB = lib(n))
-		out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline', '--no-traffic', '--steps', '20', '--warmup', '5', *extra], env = env, stdout = subprocess.PIPE, stderr = subprocess.DEVNULL, text = True).stdout
+		out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline', '--no-traffic', '--steps', '20', '--warmup', '5', *extra], env = env, stdout = subprocess.PIPE, stderr = subprocess.DEVNULL, text = True).stdout
 		j = json.loads(out.strip().splitlines()[-1])
 		roof = j['roofline']
 		res[n].append(dict(ms = j['ms_per_step'], conv_us = roof['avg_launch_us'], conv_frac = roof['frac'], wgrad_ms = roof['wgrad']['ms_per_step'], wgrad_frac = roof['wgrad']['frac'], fwd_ms = roof['hbm_kernels']['bn_act_fwd_kernel']['ms_per_step'], apply_ms = roof['hbm_kernels']['bn_act_bwd_apply_kernel']['ms_per_step'], stack_ms = roof['conv_stack']['ms_per_step']))

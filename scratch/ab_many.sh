@@ -5,7 +5,7 @@ for r in $(seq $rounds); do for n in "$@"; do
   lib=convasr_amd/libconvasr_hip.$n.so; nf=0
   if [ "$n" = main ]; then lib=convasr_amd/libconvasr_hip.so; fi
   if [ "$n" = nofuse ]; then lib=convasr_amd/libconvasr_hip.so; nf=1; fi
-  CONVASR_NO_BWD_FUSION=$nf CONVASR_HIP_LIB=$PWD/$lib python bench.py --no-cpu-baseline --no-traffic --steps 20 --warmup 5 2>/dev/null | python -c "
+  CONVASR_NO_BWD_FUSION=$nf CONVASR_HIP_LIB=$PWD/$lib python bench.py --full --no-cpu-baseline --no-traffic --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j['roofline']; pl=r.get('plain_launches')
 n=r['launches_per_step']; tot=r['avg_launch_us']*n

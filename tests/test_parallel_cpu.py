@@ -277,6 +277,28 @@ def test_bench_dump_outputs_writes_the_step_result_and_a_fixed_parameter_sample(
 	np.testing.assert_array_equal(np.load(str(tmp_path / 'again' / 'params_sample_index.npy')), got['params_sample_index'])
 
 
+def test_bench_full_option_and_the_roofline_of_a_plain_run():
+	"""bench.py --full (off by default) gates everything that takes runs of its own; a plain run's roofline holds the dominant kernel,
+	timed inside the timed region, and whole_step_frac, and no figure of the second pass (wgrad / conv_stack / hbm_kernels)."""
+	import types
+	set_by_bench = 'HSA_ENABLE_IPC_MODE_LEGACY' not in os.environ
+	import bench
+	if set_by_bench:
+		os.environ.pop('HSA_ENABLE_IPC_MODE_LEGACY', None)
+	assert bench.parse_args([]).full is False and bench.parse_args(['--full']).full is True
+	args = bench.parse_args(['--steps', '4'])
+	wl = types.SimpleNamespace(dtype = 'bf16')
+	rec = lambda n, ms, work, nbytes: dict(launches = n, total_ms = ms, avg_us = 1e3 * ms / n, work = work, bytes = nbytes)
+	kt = {bench.MAIN_FAMILY: rec(40, 20.0, 2e13, 4e9), bench.MAIN_FAMILY + '+bn_bwd': rec(32, 18.0, 1.6e13, 3e9)}
+	plain = bench.roofline_of(args, wl, dict(kt), {}, 0, 1e15, 1)
+	assert plain['launches_per_step'] == 18 and plain['achieved'] == round(3.6e13 / 38e-3 / 1e12, 2) and plain['whole_step_frac'] == 0.4
+	assert not {'wgrad', 'conv_stack', 'hbm_kernels'} & set(plain) and '--full' in plain['timing']
+	kt2 = {'conv1d_wgrad': rec(5 * 18, 10.0, 1e13, 1e9), 'hbm:bn_act_fwd_kernel': rec(5 * 16, 2.0, 0.0, 8e9)}
+	full = bench.roofline_of(args, wl, dict(kt), kt2, 5, 1e15, 1)
+	assert {'wgrad', 'conv_stack', 'hbm_kernels'} <= set(full) and full['achieved'] == plain['achieved'] and full['whole_step_frac'] == 0.4
+	assert full['hbm_kernels']['bn_act_fwd_kernel']['launches_per_step'] == 16
+
+
 def test_bench_launcher_propagates_a_rank_failure():
 	r = _run_bench(dict(CONVASR_DRY_RUN_FAIL_RANK = '1'), '--gpus', '2', '--launcher-dry-run')
 	assert r.returncode != 0
