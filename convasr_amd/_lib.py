@@ -100,6 +100,11 @@ _SIGNATURES = dict(
 	convasr_ctc_beam_search_lm_workspace_bytes = (c_i64, [c_int] * 6),
 	convasr_ctc_beam_search_lm = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int,
 	                                      c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p]),
+	convasr_ctc_beam_search_wide_workspace_bytes = (c_i64, [c_int] * 6),
+	convasr_ctc_beam_search_wide = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int, c_p]),
+	convasr_ctc_beam_search_lm_wide_workspace_bytes = (c_i64, [c_int] * 6),
+	convasr_ctc_beam_search_lm_wide = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int,
+	                                           c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p]),
 )
 
 _lib = None

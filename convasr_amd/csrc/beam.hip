@@ -21,15 +21,21 @@
 // longest listed suffix of its word history), the mask of the classes it may be extended by (the trie node's children, plus the space
 // when the current word is a word of V), and the fp64 LM term of a space extension.  All four are set once when the beam is created
 // (step 4: one trie step, and for a word that ends there the n-gram lookups of its score), so the frame loop only tests mask bits and
-// adds the cached term.  bs_body<false> is the LM-free kernel: every LM statement sits under `if constexpr (LM)`.
+// adds the cached term.  bs_body<false, *> is the LM-free kernel: every LM statement sits under `if constexpr (LM)`.
+//
+// The wide form (convasr_ctc_beam_search_wide / _lm_wide, W <= 8192) is bs_body<LM, true>: the same body, with the per-beam arrays in
+// the utterance's region of the workspace instead of LDS (bs_wide_layout).  LDS keeps the sort buffer and the per-frame
+// class arrays.  A thread makes up to W / 1024 beams in step 4, so the beam state is double-buffered there, and the tie pass of the radix
+// select covers the 27-bit candidate key.  Every difference sits under `if constexpr (WIDE)`: the LDS kernels are unchanged.
 #include <cmath>
 
 #include "common.h"
 
 #define BS_MAX_W 1024
+#define BS_WIDE_MAX_W 8192
 #define BS_MAX_N 128
 #define BS_MAX_C 8192
-#define BS_KEY_C_BITS 14  // candidate key = rank << 14 | (c + 1): c + 1 <= 8192 < 2^14, rank < 1024 -> 24 bits
+#define BS_KEY_C_BITS 14  // candidate key = rank << 14 | (c + 1): c + 1 <= 8192 < 2^14, rank < 1024 -> 24 bits (wide form: rank < 8192 -> 27 bits)
 #define BS_LM_MAX_C 256
 #define BS_LM_MAX_ORDER 6
 #define BS_LM_EMPTY_KEY (-2)
@@ -63,7 +69,8 @@ struct BsLayout {
 	size_t last, node, len, fold, sk, htab, pc, hist, pos;                   // 4- / 2-byte arrays
 	size_t lmsp, lnode, lstate, lmask;                                       // LM only: fp64 term, trie node, LM state, MW mask words
 	int MW;
-	size_t bytes;
+	size_t bytes;               // LDS
+	size_t dbl, gbytes;         // wide form: the distance between the two copies of the beam state / the workspace bytes per utterance
 };
 
 __host__ __device__ static inline BsLayout bs_layout(int W, int N, int C, bool lm = false) {
@@ -102,6 +109,50 @@ __host__ __device__ static inline BsLayout bs_layout(int W, int N, int C, bool l
 		L.lmask = o; o += 4 * (size_t)W * L.MW;
 	}
 	L.bytes = (o + 15) & ~(size_t)15;
+	L.dbl = L.gbytes = 0;
+	return L;
+}
+
+// The wide form.  LDS: the sort buffer (pow2(W) entries), the selection state and the per-frame class arrays, 117,328 bytes at most
+// (W = 8192, C = 8192).  Workspace, per utterance, at offsets from its region: the beam state written in step 4, twice (copy 1 at +dbl),
+// then own_*, fold and the hash table, rebuilt every frame.
+__host__ __device__ static inline BsLayout bs_wide_layout(int W, int N, int C, bool lm = false) {
+	BsLayout L;
+	L.W = W; L.NW = (N + 31) / 32; L.C = C;
+	L.S = bs_pow2(W > BS_MAX_N ? W : BS_MAX_N);
+	L.TB = bs_pow2(2 * W > 64 ? 2 * W : 64);
+	L.MW = lm ? (C + 31) / 32 : 0;
+	size_t o = 0;
+	L.su = o; o += 8 * (size_t)L.S;
+	L.plp = o; o += 8 * (size_t)BS_MAX_N;
+	L.sel = o; o += (sizeof(BsSel) + 15) & ~(size_t)15;
+	L.sk = o; o += 4 * (size_t)L.S;
+	L.pc = o; o += 4 * (size_t)BS_MAX_N;
+	L.hist = o; o += 4 * 256;
+	L.pos = o; o += 2 * (size_t)C;
+	L.bytes = (o + 15) & ~(size_t)15;
+	o = 0;
+	L.lpb = o; o += 8 * (size_t)W;
+	L.lpnb = o; o += 8 * (size_t)W;
+	L.tot = o; o += 8 * (size_t)W;
+	L.hash = o; o += 8 * (size_t)W;
+	L.phash = o; o += 8 * (size_t)W;
+	L.lmsp = o; if (lm) o += 8 * (size_t)W;
+	L.last = o; o += 4 * (size_t)W;
+	L.node = o; o += 4 * (size_t)W;
+	L.len = o; o += 4 * (size_t)W;
+	L.lnode = o; if (lm) o += 4 * (size_t)W;
+	L.lstate = o; if (lm) o += 4 * (size_t)W;
+	L.lmask = o; o += 4 * (size_t)W * L.MW;
+	if (!lm) L.lmsp = L.lnode = L.lstate = L.lmask = 0;
+	L.dbl = (o + 15) & ~(size_t)15;
+	o = 2 * L.dbl;
+	L.own_nb = o; o += 8 * (size_t)W;
+	L.own_nnb = o; o += 8 * (size_t)W;
+	L.own_s = o; o += 8 * (size_t)W;
+	L.fold = o; o += 4 * (size_t)W * L.NW;
+	L.htab = o; o += 4 * (size_t)L.TB;
+	L.gbytes = (o + 255) & ~(size_t)255;
 	return L;
 }
 
@@ -180,8 +231,8 @@ __device__ __forceinline__ void bs_pick(const int* hist, BsSel* s) {
 }
 
 // Radix select of the k best (smallest (u, key)) among the candidates `enumerate` visits; afterwards bs_selected() tells them apart.
-// Every thread of the workgroup calls it.
-template <class E>
+// Every thread of the workgroup calls it.  The tie passes cover key bits 0-23, or 0-31 in the wide form (keys of 27 bits).
+template <bool WIDE, class E>
 __device__ void bs_radix_select(E enumerate, int k, int* hist, BsSel* s) {
 	const int tid = threadIdx.x, nth = blockDim.x;
 	if (tid == 0) { s->P = 0; s->M = 0; s->KP = 0; s->KM = 0; s->need = k; s->full = 0; s->all = 0; s->tie = 0; }
@@ -204,7 +255,7 @@ __device__ void bs_radix_select(E enumerate, int k, int* hist, BsSel* s) {
 	}
 	// more candidates than needed share the boundary score exactly: the smallest keys among them
 	if (tid == 0) s->tie = 1;
-	for (int shift = 16; shift >= 0; shift -= 8) {
+	for (int shift = WIDE ? 24 : 16; shift >= 0; shift -= 8) {
 		for (int i = tid; i < 256; i += nth) hist[i] = 0;
 		__syncthreads();
 		const uint64_t P = s->P;
@@ -292,36 +343,40 @@ __device__ int bs_lm_advance(const BsLm& lm, int s, int word) {
 	return word;
 }
 
-template <bool LM>
+template <bool LM, bool WIDE>
 __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths, int64_t* __restrict__ out_tokens,
                                         int* __restrict__ out_offsets, int64_t* __restrict__ out_lengths, void* __restrict__ out_logp,
-                                        int2* __restrict__ arena_all, int T, int C, int blank, int W, int N, float cutoff_prob, int topk, const BsLm& lm) {
+                                        int2* __restrict__ arena_all, unsigned char* __restrict__ state_all, int T, int C, int blank, int W, int N,
+                                        float cutoff_prob, int topk, const BsLm& lm) {
 	extern __shared__ __align__(16) unsigned char bs_smem[];
-	const BsLayout Ly = bs_layout(W, N, C, LM);
+	const BsLayout Ly = WIDE ? bs_wide_layout(W, N, C, LM) : bs_layout(W, N, C, LM);
+	unsigned char* bm = bs_smem;  // the per-beam arrays: LDS, or in the wide form the utterance's region of the workspace
+	if constexpr (WIDE) bm = state_all + (int64_t)blockIdx.x * Ly.gbytes;
 	BsSel& s = *(BsSel*)(bs_smem + Ly.sel);  // (dynamic: static LDS would stop the 160 KiB opt-in)
-	double* lpb = (double*)(bs_smem + Ly.lpb);
-	double* lpnb = (double*)(bs_smem + Ly.lpnb);
-	double* tot = (double*)(bs_smem + Ly.tot);
-	double* own_nb = (double*)(bs_smem + Ly.own_nb);
-	double* own_nnb = (double*)(bs_smem + Ly.own_nnb);
-	double* own_s = (double*)(bs_smem + Ly.own_s);
-	uint64_t* hash = (uint64_t*)(bs_smem + Ly.hash);
-	uint64_t* phash = (uint64_t*)(bs_smem + Ly.phash);
+	double* lpb = (double*)(bm + Ly.lpb);
+	double* lpnb = (double*)(bm + Ly.lpnb);
+	double* tot = (double*)(bm + Ly.tot);
+	double* own_nb = (double*)(bm + Ly.own_nb);
+	double* own_nnb = (double*)(bm + Ly.own_nnb);
+	double* own_s = (double*)(bm + Ly.own_s);
+	uint64_t* hash = (uint64_t*)(bm + Ly.hash);
+	uint64_t* phash = (uint64_t*)(bm + Ly.phash);
 	uint64_t* su = (uint64_t*)(bs_smem + Ly.su);
 	double* plp = (double*)(bs_smem + Ly.plp);
-	int* last = (int*)(bs_smem + Ly.last);
-	int* node = (int*)(bs_smem + Ly.node);
-	int* len = (int*)(bs_smem + Ly.len);
-	unsigned* fold = (unsigned*)(bs_smem + Ly.fold);
+	int* last = (int*)(bm + Ly.last);
+	int* node = (int*)(bm + Ly.node);
+	int* len = (int*)(bm + Ly.len);
+	unsigned* fold = (unsigned*)(bm + Ly.fold);
 	int* sk = (int*)(bs_smem + Ly.sk);
-	int* htab = (int*)(bs_smem + Ly.htab);
+	int* htab = (int*)(bm + Ly.htab);
 	int* pc = (int*)(bs_smem + Ly.pc);
 	int* hist = (int*)(bs_smem + Ly.hist);
 	short* pos = (short*)(bs_smem + Ly.pos);
-	double* lmsp = (double*)(bs_smem + Ly.lmsp);
-	int* lnode = (int*)(bs_smem + Ly.lnode);
-	int* lstate = (int*)(bs_smem + Ly.lstate);
-	unsigned* lmask = (unsigned*)(bs_smem + Ly.lmask);
+	double* lmsp = (double*)(bm + Ly.lmsp);
+	int* lnode = (int*)(bm + Ly.lnode);
+	int* lstate = (int*)(bm + Ly.lstate);
+	unsigned* lmask = (unsigned*)(bm + Ly.lmask);
+	int64_t dbl = (int64_t)Ly.dbl;  // wide form: from the copy of the beam state being read to the one step 4 writes
 	const int MW = LM ? Ly.MW : 0;
 	const int space = LM ? lm.space : -1;
 	const double LN10 = 2.302585092994045684;
@@ -355,7 +410,7 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 			np = C;
 		} else {
 			auto classes = [&](auto&& fn) { for (int c = tid; c < C; c += nth) fn(((uint64_t)bs_desc32(row[c]) << 32) | (unsigned)c, 0u); };
-			bs_radix_select(classes, N, hist, &s);
+			bs_radix_select<WIDE>(classes, N, hist, &s);
 			const BsSel sel = s;
 			for (int c = tid; c < C; c += nth)
 				if (bs_selected(sel, ((uint64_t)bs_desc32(row[c]) << 32) | (unsigned)c, 0u)) pc[atomicAdd(&s.m, 1)] = c;
@@ -457,7 +512,7 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 				if (q >= S) { q -= S; ++i; }
 			}
 		};
-		bs_radix_select(candidates, W, hist, &s);
+		bs_radix_select<WIDE>(candidates, W, hist, &s);
 		{
 			const BsSel sel = s;
 			candidates([&](uint64_t u, unsigned key) {
@@ -469,69 +524,138 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 		for (int r = m + tid; r < Sm; r += nth) { su[r] = ~0ull; sk[r] = 0x7fffffff; }
 		__syncthreads();
 		bs_sort(su, sk, Sm);
-		// ---- 4. the next beams, in rank order (one per thread: nth >= W >= m)
-		double nlpb = 0, nlpnb = 0, ntot = 0;
-		uint64_t nh = 0, nph = 0;
-		int nlast = 0, nnode = 0, nlen = 0;
-		double nlmsp = 0.0;
-		int nlnode = 0, nlstate = 0;
-		unsigned nmask[BS_LM_MAX_C / 32];
-		if (tid < m) {
-			const unsigned key = (unsigned)sk[tid];
-			const int i = (int)(key >> BS_KEY_C_BITS), c = (int)(key & ((1u << BS_KEY_C_BITS) - 1)) - 1;
-			ntot = bs_undesc64(su[tid]);
-			if (c < 0) {
-				nlpb = own_nb[i]; nlpnb = own_nnb[i]; nh = hash[i]; nph = phash[i]; nlast = last[i]; nnode = node[i]; nlen = len[i];
-				if constexpr (LM) {
-					nlmsp = lmsp[i]; nlnode = lnode[i]; nlstate = lstate[i];
+		// ---- 4. the next beams, in rank order.  The LDS form makes one per thread (nth >= W >= m); the wide form up to W / nth per thread, and
+		// a beam made there may be the parent another thread still reads: it writes the other copy of the beam state, then swaps.
+		if constexpr (WIDE) {
+			auto nx = [&](auto* p) { return (decltype(p))((unsigned char*)p + dbl); };
+			for (int r = tid; r < m; r += nth) {
+				double nlpb = 0, nlpnb = 0, ntot = 0;
+				uint64_t nh = 0, nph = 0;
+				int nlast = 0, nnode = 0, nlen = 0;
+				double nlmsp = 0.0;
+				int nlnode = 0, nlstate = 0;
+				unsigned nmask[BS_LM_MAX_C / 32];
+				const unsigned key = (unsigned)sk[r];
+				const int i = (int)(key >> BS_KEY_C_BITS), c = (int)(key & ((1u << BS_KEY_C_BITS) - 1)) - 1;
+				ntot = bs_undesc64(su[r]);
+				if (c < 0) {
+					nlpb = own_nb[i]; nlpnb = own_nnb[i]; nh = hash[i]; nph = phash[i]; nlast = last[i]; nnode = node[i]; nlen = len[i];
+					if constexpr (LM) {
+						nlmsp = lmsp[i]; nlnode = lnode[i]; nlstate = lstate[i];
 #pragma unroll
-					for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nmask[k] = k < MW ? lmask[i * MW + k] : 0u;
-				}
-			} else {
-				nlpb = NEG; nlpnb = ntot; nh = bs_extend_hash(hash[i], c); nph = hash[i]; nlast = c; nlen = len[i] + 1;
-				nnode = t * W + tid;
-				arena[nnode] = make_int2(node[i], c);
-				if constexpr (LM) {
-					nlstate = lstate[i];
-					int word;
-					if (c == space) {  // the current word ends: the next one starts at the root, in the state after it
-						word = lm.node_word[lnode[i]];
-						nlstate = bs_lm_advance(lm, nlstate, word);
-						nlnode = 0;
-						word = -1;
-					} else {  // one trie step: the child's index among its siblings = the parent's children below c
-						const int pn = lnode[i];
-						int below = 0;
-#pragma unroll
-						for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
-							if (k < MW) {
-								unsigned bits = lm.node_mask[(int64_t)pn * MW + k];
-								if (32 * k + 32 <= c) below += __popc(bits);
-								else if (32 * k <= c) below += __popc(bits & ((1u << (c & 31)) - 1u));
-							}
-						nlnode = lm.node_child[pn] + below;
-						word = lm.node_word[nlnode];
+						for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nmask[k] = k < MW ? lmask[i * MW + k] : 0u;
 					}
+				} else {
+					nlpb = NEG; nlpnb = ntot; nh = bs_extend_hash(hash[i], c); nph = hash[i]; nlast = c; nlen = len[i] + 1;
+					nnode = t * W + r;
+					arena[nnode] = make_int2(node[i], c);
+					if constexpr (LM) {
+						nlstate = lstate[i];
+						int word;
+						if (c == space) {  // the current word ends: the next one starts at the root, in the state after it
+							word = lm.node_word[lnode[i]];
+							nlstate = bs_lm_advance(lm, nlstate, word);
+							nlnode = 0;
+							word = -1;
+						} else {  // one trie step: the child's index among its siblings = the parent's children below c
+							const int pn = lnode[i];
+							int below = 0;
 #pragma unroll
-					for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nmask[k] = k < MW ? lm.node_mask[(int64_t)nlnode * MW + k] : 0u;
-					nlmsp = 0.0;
-					if (word >= 0) {  // the current word is in V: the space may follow, with this LM term
-						nlmsp = lm.alpha * (bs_lm_log10(lm, nlstate, word) * LN10) + lm.beta;
+							for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+								if (k < MW) {
+									unsigned bits = lm.node_mask[(int64_t)pn * MW + k];
+									if (32 * k + 32 <= c) below += __popc(bits);
+									else if (32 * k <= c) below += __popc(bits & ((1u << (c & 31)) - 1u));
+								}
+							nlnode = lm.node_child[pn] + below;
+							word = lm.node_word[nlnode];
+						}
 #pragma unroll
-						for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
-							if (k == (space >> 5)) nmask[k] |= 1u << (space & 31);
+						for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nmask[k] = k < MW ? lm.node_mask[(int64_t)nlnode * MW + k] : 0u;
+						nlmsp = 0.0;
+						if (word >= 0) {  // the current word is in V: the space may follow, with this LM term
+							nlmsp = lm.alpha * (bs_lm_log10(lm, nlstate, word) * LN10) + lm.beta;
+#pragma unroll
+							for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+								if (k == (space >> 5)) nmask[k] |= 1u << (space & 31);
+						}
+					}
+				}
+				nx(lpb)[r] = nlpb; nx(lpnb)[r] = nlpnb; nx(tot)[r] = ntot; nx(hash)[r] = nh; nx(phash)[r] = nph; nx(last)[r] = nlast; nx(node)[r] = nnode; nx(len)[r] = nlen;
+				if constexpr (LM) {
+					nx(lmsp)[r] = nlmsp; nx(lnode)[r] = nlnode; nx(lstate)[r] = nlstate;
+#pragma unroll
+					for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+						if (k < MW) nx(lmask)[r * MW + k] = nmask[k];
+				}
+			}
+			lpb = nx(lpb); lpnb = nx(lpnb); tot = nx(tot); hash = nx(hash); phash = nx(phash); last = nx(last); node = nx(node); len = nx(len);
+			if constexpr (LM) { lmsp = nx(lmsp); lnode = nx(lnode); lstate = nx(lstate); lmask = nx(lmask); }
+			dbl = -dbl;
+		} else {
+			double nlpb = 0, nlpnb = 0, ntot = 0;
+			uint64_t nh = 0, nph = 0;
+			int nlast = 0, nnode = 0, nlen = 0;
+			double nlmsp = 0.0;
+			int nlnode = 0, nlstate = 0;
+			unsigned nmask[BS_LM_MAX_C / 32];
+			if (tid < m) {
+				const unsigned key = (unsigned)sk[tid];
+				const int i = (int)(key >> BS_KEY_C_BITS), c = (int)(key & ((1u << BS_KEY_C_BITS) - 1)) - 1;
+				ntot = bs_undesc64(su[tid]);
+				if (c < 0) {
+					nlpb = own_nb[i]; nlpnb = own_nnb[i]; nh = hash[i]; nph = phash[i]; nlast = last[i]; nnode = node[i]; nlen = len[i];
+					if constexpr (LM) {
+						nlmsp = lmsp[i]; nlnode = lnode[i]; nlstate = lstate[i];
+#pragma unroll
+						for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nmask[k] = k < MW ? lmask[i * MW + k] : 0u;
+					}
+				} else {
+					nlpb = NEG; nlpnb = ntot; nh = bs_extend_hash(hash[i], c); nph = hash[i]; nlast = c; nlen = len[i] + 1;
+					nnode = t * W + tid;
+					arena[nnode] = make_int2(node[i], c);
+					if constexpr (LM) {
+						nlstate = lstate[i];
+						int word;
+						if (c == space) {  // the current word ends: the next one starts at the root, in the state after it
+							word = lm.node_word[lnode[i]];
+							nlstate = bs_lm_advance(lm, nlstate, word);
+							nlnode = 0;
+							word = -1;
+						} else {  // one trie step: the child's index among its siblings = the parent's children below c
+							const int pn = lnode[i];
+							int below = 0;
+#pragma unroll
+							for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+								if (k < MW) {
+									unsigned bits = lm.node_mask[(int64_t)pn * MW + k];
+									if (32 * k + 32 <= c) below += __popc(bits);
+									else if (32 * k <= c) below += __popc(bits & ((1u << (c & 31)) - 1u));
+								}
+							nlnode = lm.node_child[pn] + below;
+							word = lm.node_word[nlnode];
+						}
+#pragma unroll
+						for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nmask[k] = k < MW ? lm.node_mask[(int64_t)nlnode * MW + k] : 0u;
+						nlmsp = 0.0;
+						if (word >= 0) {  // the current word is in V: the space may follow, with this LM term
+							nlmsp = lm.alpha * (bs_lm_log10(lm, nlstate, word) * LN10) + lm.beta;
+#pragma unroll
+							for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+								if (k == (space >> 5)) nmask[k] |= 1u << (space & 31);
+						}
 					}
 				}
 			}
-		}
-		__syncthreads();
-		if (tid < m) { lpb[tid] = nlpb; lpnb[tid] = nlpnb; tot[tid] = ntot; hash[tid] = nh; phash[tid] = nph; last[tid] = nlast; node[tid] = nnode; len[tid] = nlen; }
-		if constexpr (LM) {
-			if (tid < m) {
-				lmsp[tid] = nlmsp; lnode[tid] = nlnode; lstate[tid] = nlstate;
+			__syncthreads();
+			if (tid < m) { lpb[tid] = nlpb; lpnb[tid] = nlpnb; tot[tid] = ntot; hash[tid] = nh; phash[tid] = nph; last[tid] = nlast; node[tid] = nnode; len[tid] = nlen; }
+			if constexpr (LM) {
+				if (tid < m) {
+					lmsp[tid] = nlmsp; lnode[tid] = nlnode; lstate[tid] = nlstate;
 #pragma unroll
-				for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
-					if (k < MW) lmask[tid * MW + k] = nmask[k];
+					for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+						if (k < MW) lmask[tid * MW + k] = nmask[k];
+				}
 			}
 		}
 		if (tid == 0) s.n = m;
@@ -588,7 +712,7 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __re
                                                                 int2* __restrict__ arena_all, int T, int C, int blank, int W, int N,
                                                                 float cutoff_prob, int topk) {
 	const BsLm none{};
-	bs_body<false>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, T, C, blank, W, N, cutoff_prob, topk, none);
+	bs_body<false, false>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, nullptr, T, C, blank, W, N, cutoff_prob, topk, none);
 }
 
 __global__ __launch_bounds__(1024) void ctc_beam_search_lm_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
@@ -596,10 +720,27 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_lm_kernel(const float* _
                                                                    int64_t* __restrict__ out_lengths, double* __restrict__ out_logp,
                                                                    int2* __restrict__ arena_all, int T, int C, int blank, int W, int N,
                                                                    float cutoff_prob, int topk, BsLm lm) {
-	bs_body<true>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, T, C, blank, W, N, cutoff_prob, topk, lm);
+	bs_body<true, false>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, nullptr, T, C, blank, W, N, cutoff_prob, topk, lm);
 }
 
-static const char* bs_envelope(int B, int T, int C, int W, int N, int topk, int* code) {
+__global__ __launch_bounds__(1024) void ctc_beam_search_wide_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
+                                                                     int64_t* __restrict__ out_tokens, int* __restrict__ out_offsets,
+                                                                     int64_t* __restrict__ out_lengths, float* __restrict__ out_logp,
+                                                                     int2* __restrict__ arena_all, unsigned char* __restrict__ state_all, int T, int C,
+                                                                     int blank, int W, int N, float cutoff_prob, int topk) {
+	const BsLm none{};
+	bs_body<false, true>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, state_all, T, C, blank, W, N, cutoff_prob, topk, none);
+}
+
+__global__ __launch_bounds__(1024) void ctc_beam_search_lm_wide_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
+                                                                        int64_t* __restrict__ out_tokens, int* __restrict__ out_offsets,
+                                                                        int64_t* __restrict__ out_lengths, double* __restrict__ out_logp,
+                                                                        int2* __restrict__ arena_all, unsigned char* __restrict__ state_all, int T,
+                                                                        int C, int blank, int W, int N, float cutoff_prob, int topk, BsLm lm) {
+	bs_body<true, true>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, state_all, T, C, blank, W, N, cutoff_prob, topk, lm);
+}
+
+static const char* bs_envelope(int B, int T, int C, int W, int N, int topk, int* code, bool wide = false) {
 	*code = CONVASR_EINVAL;
 	if (B < 1 || T < 1) return "B and T must be >= 1";
 	if (W < 1) return "beam width must be >= 1";
@@ -607,7 +748,8 @@ static const char* bs_envelope(int B, int T, int C, int W, int N, int topk, int*
 	if (N < 1 || N > C) return "cutoff_top_n must be in [1, C]";
 	if (topk < 1 || topk > W) return "topk must be in [1, beam width]";
 	*code = CONVASR_EUNSUPPORTED;
-	if (W > BS_MAX_W) return "beam width > 1024 is outside the supported envelope";
+	if (!wide && W > BS_MAX_W) return "beam width > 1024 is outside the supported envelope";
+	if (wide && W > BS_WIDE_MAX_W) return "beam width > 8192 is outside the supported envelope";
 	if (N > BS_MAX_N) return "cutoff_top_n > 128 is outside the supported envelope";
 	if (C > BS_MAX_C) return "C > 8192 is outside the supported envelope";
 	if ((int64_t)B * T * W >= (1ll << 31)) return "B * T * beam width >= 2^31 (workspace arena)";
@@ -650,6 +792,24 @@ static const char* bs_lm_envelope(int B, int T, int C, int W, int N, int topk, i
 	return nullptr;
 }
 
+// the LM entry points' checks after the envelope; fills *lm
+static int bs_lm_args(const char* fn, int C, int blank, float cutoff_prob, const uint32_t* node_mask, const int32_t* node_child, const int32_t* node_word,
+                      int n_nodes, const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots, int space, int order,
+                      int start_state, double alpha, double beta, BsLm* lm) {
+	CONVASR_CHECK_ARG(blank >= 0 && blank < C, "%s: blank %d outside [0, %d)", fn, blank, C);
+	CONVASR_CHECK_ARG(cutoff_prob > 0.f && cutoff_prob <= 1.f, "%s: cutoff_prob must be in (0, 1]", fn);
+	CONVASR_CHECK_ARG(space >= 0 && space < C && space != blank, "%s: space class %d must be in [0, %d) and differ from the blank %d", fn, space, C, blank);
+	CONVASR_CHECK_ARG(order >= 1 && order <= BS_LM_MAX_ORDER, "%s: LM order %d outside [1, %d]", fn, order, BS_LM_MAX_ORDER);
+	CONVASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "%s: alpha and beta must be finite", fn);
+	CONVASR_CHECK_ARG(n_nodes >= 1 && n_ent >= 1, "%s: empty LM tables (%d trie nodes, %d n-gram entries)", fn, n_nodes, n_ent);
+	CONVASR_CHECK_ARG(n_slots >= 1 && (n_slots & (n_slots - 1)) == 0, "%s: n_slots %d is not a power of two", fn, n_slots);
+	CONVASR_CHECK_ARG(start_state >= -1 && start_state < n_ent, "%s: start state %d outside [-1, %d)", fn, start_state, n_ent);
+	lm->node_mask = node_mask; lm->node_child = node_child; lm->node_word = node_word;
+	lm->ent_pb = (const double2*)ent_pb; lm->ent_sl = (const int2*)ent_sl; lm->slots = (const int4*)slots;
+	lm->n_slots = n_slots; lm->space = space; lm->order = order; lm->start = start_state; lm->alpha = alpha; lm->beta = beta;
+	return 0;
+}
+
 extern "C" int64_t convasr_ctc_beam_search_lm_workspace_bytes(int B, int T, int C, int W, int N, int topk) {
 	int code;
 	if (const char* why = bs_lm_envelope(B, T, C, W, N, topk, &code))
@@ -667,24 +827,88 @@ extern "C" int convasr_ctc_beam_search_lm(const float* log_probs, const int64_t*
 	int code;
 	if (const char* why = bs_lm_envelope(B, T, C, W, N, topk, &code))
 		return convasr_fail(code, "ctc_beam_search_lm: %s (B %d T %d C %d W %d N %d topk %d; %zu bytes of LDS)", why, B, T, C, W, N, topk, bs_layout(W, N, C, true).bytes);
-	CONVASR_CHECK_ARG(blank >= 0 && blank < C, "ctc_beam_search_lm: blank %d outside [0, %d)", blank, C);
-	CONVASR_CHECK_ARG(cutoff_prob > 0.f && cutoff_prob <= 1.f, "ctc_beam_search_lm: cutoff_prob must be in (0, 1]");
-	CONVASR_CHECK_ARG(space >= 0 && space < C && space != blank, "ctc_beam_search_lm: space class %d must be in [0, %d) and differ from the blank %d", space, C, blank);
-	CONVASR_CHECK_ARG(order >= 1 && order <= BS_LM_MAX_ORDER, "ctc_beam_search_lm: LM order %d outside [1, %d]", order, BS_LM_MAX_ORDER);
-	CONVASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "ctc_beam_search_lm: alpha and beta must be finite");
-	CONVASR_CHECK_ARG(n_nodes >= 1 && n_ent >= 1, "ctc_beam_search_lm: empty LM tables (%d trie nodes, %d n-gram entries)", n_nodes, n_ent);
-	CONVASR_CHECK_ARG(n_slots >= 1 && (n_slots & (n_slots - 1)) == 0, "ctc_beam_search_lm: n_slots %d is not a power of two", n_slots);
-	CONVASR_CHECK_ARG(start_state >= -1 && start_state < n_ent, "ctc_beam_search_lm: start state %d outside [-1, %d)", start_state, n_ent);
+	BsLm lm;
+	if (int rc = bs_lm_args("ctc_beam_search_lm", C, blank, cutoff_prob, node_mask, node_child, node_word, n_nodes, ent_pb, ent_sl, n_ent, slots, n_slots, space, order,
+	                        start_state, alpha, beta, &lm))
+		return rc;
 	const BsLayout Ly = bs_layout(W, N, C, true);
 	const int threads = W <= 256 ? 256 : 1024;
 	static unsigned long long set = 0;
 	convasr_allow_160k_lds(reinterpret_cast<const void*>(ctc_beam_search_lm_kernel), set);
-	BsLm lm;
-	lm.node_mask = node_mask; lm.node_child = node_child; lm.node_word = node_word;
-	lm.ent_pb = (const double2*)ent_pb; lm.ent_sl = (const int2*)ent_sl; lm.slots = (const int4*)slots;
-	lm.n_slots = n_slots; lm.space = space; lm.order = order; lm.start = start_state; lm.alpha = alpha; lm.beta = beta;
 	hipLaunchKernelGGL(ctc_beam_search_lm_kernel, dim3(B), dim3(threads), Ly.bytes, (hipStream_t)stream, log_probs, lengths, tokens, offsets, out_lengths,
 	                   log_prob, (int2*)workspace, T, C, blank, W, N, cutoff_prob, topk, lm);
 	CONVASR_CHECK_LAUNCH("ctc_beam_search_lm");
+	return 0;
+}
+
+// ---- the wide form: W <= 8192, the beam state in the workspace (bs_wide_layout)
+static const char* bs_wide_envelope(int B, int T, int C, int W, int N, int topk, bool lm, int* code) {
+	if (const char* why = bs_envelope(B, T, C, W, N, topk, code, true)) return why;
+	*code = CONVASR_EUNSUPPORTED;
+	if (lm && C > BS_LM_MAX_C) return "C > 256 is outside the envelope of the LM search";
+	if (bs_wide_layout(W, N, C, lm).bytes > 160 * 1024) return "the sort buffer and class arrays exceed 160 KiB of LDS";  // (never within the checks above)
+	return nullptr;
+}
+
+// the arena (B * T * W nodes), rounded up to 256 bytes, then B regions of beam state
+static int64_t bs_wide_arena_bytes(int B, int T, int W) { return ((int64_t)B * T * W * (int64_t)sizeof(int2) + 255) & ~(int64_t)255; }
+static int64_t bs_wide_workspace(int B, int T, int C, int W, int N, bool lm) { return bs_wide_arena_bytes(B, T, W) + (int64_t)B * (int64_t)bs_wide_layout(W, N, C, lm).gbytes; }
+
+extern "C" int64_t convasr_ctc_beam_search_wide_workspace_bytes(int B, int T, int C, int W, int N, int topk) {
+	int code;
+	if (const char* why = bs_wide_envelope(B, T, C, W, N, topk, false, &code))
+		return convasr_fail(code, "ctc_beam_search_wide: %s (B %d T %d C %d W %d N %d topk %d)", why, B, T, C, W, N, topk);
+	return bs_wide_workspace(B, T, C, W, N, false);
+}
+
+extern "C" int convasr_ctc_beam_search_wide(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                            float* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob,
+                                            int topk, void* stream) {
+	CONVASR_CHECK_ARG(log_probs && lengths && tokens && offsets && out_lengths && log_prob && workspace, "ctc_beam_search_wide: NULL pointer");
+	int code;
+	if (const char* why = bs_wide_envelope(B, T, C, W, N, topk, false, &code))
+		return convasr_fail(code, "ctc_beam_search_wide: %s (B %d T %d C %d W %d N %d topk %d)", why, B, T, C, W, N, topk);
+	CONVASR_CHECK_ARG(blank >= 0 && blank < C, "ctc_beam_search_wide: blank %d outside [0, %d)", blank, C);
+	CONVASR_CHECK_ARG(cutoff_prob > 0.f && cutoff_prob <= 1.f, "ctc_beam_search_wide: cutoff_prob must be in (0, 1]");
+	const BsLayout Ly = bs_wide_layout(W, N, C);
+	const int threads = W <= 256 ? 256 : 1024;
+	static unsigned long long set = 0;
+	convasr_allow_160k_lds(reinterpret_cast<const void*>(ctc_beam_search_wide_kernel), set);
+	unsigned char* state = (unsigned char*)workspace + bs_wide_arena_bytes(B, T, W);
+	hipLaunchKernelGGL(ctc_beam_search_wide_kernel, dim3(B), dim3(threads), Ly.bytes, (hipStream_t)stream, log_probs, lengths, tokens, offsets, out_lengths,
+	                   log_prob, (int2*)workspace, state, T, C, blank, W, N, cutoff_prob, topk);
+	CONVASR_CHECK_LAUNCH("ctc_beam_search_wide");
+	return 0;
+}
+
+extern "C" int64_t convasr_ctc_beam_search_lm_wide_workspace_bytes(int B, int T, int C, int W, int N, int topk) {
+	int code;
+	if (const char* why = bs_wide_envelope(B, T, C, W, N, topk, true, &code))
+		return convasr_fail(code, "ctc_beam_search_lm_wide: %s (B %d T %d C %d W %d N %d topk %d)", why, B, T, C, W, N, topk);
+	return bs_wide_workspace(B, T, C, W, N, true);
+}
+
+extern "C" int convasr_ctc_beam_search_lm_wide(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                               double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                                               const uint32_t* node_mask, const int32_t* node_child, const int32_t* node_word, int n_nodes,
+                                               const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
+                                               int space, int order, int start_state, double alpha, double beta, void* stream) {
+	CONVASR_CHECK_ARG(log_probs && lengths && tokens && offsets && out_lengths && log_prob && workspace, "ctc_beam_search_lm_wide: NULL pointer");
+	CONVASR_CHECK_ARG(node_mask && node_child && node_word && ent_pb && ent_sl && slots, "ctc_beam_search_lm_wide: NULL LM table");
+	int code;
+	if (const char* why = bs_wide_envelope(B, T, C, W, N, topk, true, &code))
+		return convasr_fail(code, "ctc_beam_search_lm_wide: %s (B %d T %d C %d W %d N %d topk %d)", why, B, T, C, W, N, topk);
+	BsLm lm;
+	if (int rc = bs_lm_args("ctc_beam_search_lm_wide", C, blank, cutoff_prob, node_mask, node_child, node_word, n_nodes, ent_pb, ent_sl, n_ent, slots, n_slots,
+	                        space, order, start_state, alpha, beta, &lm))
+		return rc;
+	const BsLayout Ly = bs_wide_layout(W, N, C, true);
+	const int threads = W <= 256 ? 256 : 1024;
+	static unsigned long long set = 0;
+	convasr_allow_160k_lds(reinterpret_cast<const void*>(ctc_beam_search_lm_wide_kernel), set);
+	unsigned char* state = (unsigned char*)workspace + bs_wide_arena_bytes(B, T, W);
+	hipLaunchKernelGGL(ctc_beam_search_lm_wide_kernel, dim3(B), dim3(threads), Ly.bytes, (hipStream_t)stream, log_probs, lengths, tokens, offsets, out_lengths,
+	                   log_prob, (int2*)workspace, state, T, C, blank, W, N, cutoff_prob, topk, lm);
+	CONVASR_CHECK_LAUNCH("ctc_beam_search_lm_wide");
 	return 0;
 }

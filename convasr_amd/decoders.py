@@ -53,8 +53,9 @@ class GreedyDecoder:
 
 
 class BeamSearchDecoder:
-	"""decoders.BeamSearchDecoder.  beam_width <= 1024, cutoff_top_n <= 128 (None or more than C: C), C <= 8192; outside that envelope decode()
-	raises (the reference transcribe.py's default --beam-width 5000 among them).  num_workers is the reference's CPU thread count and has no
+	"""decoders.BeamSearchDecoder.  beam_width <= 8192, cutoff_top_n <= 128 (None or more than C: C), C <= 8192; outside that envelope decode()
+	raises.  Widths up to 1024 run the LDS kernel, wider ones (the reference transcribe.py's default --beam-width 5000 among them) the
+	wide kernel with the beam state in global memory: the same search, the same results (ops.ctc_beam_search).  num_workers is the reference's CPU thread count and has no
 	meaning here.  beam_width is required, as in the reference (it is a keyword here only because lm_path got a default).  The search runs on
 	the GPU only: log_probs must be a CUDA tensor.
 

@@ -860,12 +860,32 @@ def ctc_alignment(log_probs_btc, targets, input_lengths, target_lengths, blank):
 	return out
 
 
-def ctc_beam_search(log_probs_bct, lengths, blank, beam_width, cutoff_top_n = 40, cutoff_prob = 1.0, topk = 1):
+def _beam_route(name, args, wide):
+	"""(entry point, workspace bytes): the LDS kernel whenever its workspace query accepts the arguments (wide None), otherwise -- or with
+	wide True -- the wide one (beam state in the workspace, beam_width <= 8192); wide False keeps the LDS kernel.  Raises ConvasrHipError
+	with the refusing query's message."""
+	lib = _lib.load()
+	if not wide:
+		nbytes = getattr(lib, f'convasr_{name}_workspace_bytes')(*args)
+		if nbytes >= 0 or wide is False:
+			if nbytes < 0:
+				raise _lib.ConvasrHipError(lib.convasr_last_error().decode())
+			return f'convasr_{name}', nbytes
+	nbytes = getattr(lib, f'convasr_{name}_wide_workspace_bytes')(*args)
+	if nbytes < 0:
+		raise _lib.ConvasrHipError(lib.convasr_last_error().decode())
+	return f'convasr_{name}_wide', nbytes
+
+
+def ctc_beam_search(log_probs_bct, lengths, blank, beam_width, cutoff_top_n = 40, cutoff_prob = 1.0, topk = 1, *, wide = None):
 	"""CTC prefix beam search without a language model (include/convasr_hip.h: convasr_ctc_beam_search).  log_probs_bct: (B, C, T) log-probs
 	on the GPU (the model's channels-last fp32 is read in place, anything else is converted); lengths (B,) frames per utterance or None (all T).
 	Returns (tokens (B, topk, T) int64, offsets (B, topk, T) int32, out_lengths (B, topk) int64, log_prob (B, topk) fp32), best first.
-	The kernel's prefix-node arena is allocated for the call: B x T x beam_width x 8 bytes.
-	cutoff_top_n above C means C.  Outside the kernel's envelope (beam_width <= 1024, cutoff_top_n <= 128, C <= 8192, ...) it raises ConvasrHipError."""
+	cutoff_top_n above C means C.  beam_width <= 1024 (and the LDS budget) runs the LDS kernel; wider beams, up to 8192, run the wide one
+	(convasr_ctc_beam_search_wide: the same search, the beam state in the workspace).  wide: None chooses so, True forces the wide kernel,
+	False the LDS one.  The workspace is allocated for the call: B x T x beam_width x 8 bytes of prefix-node arena, plus the wide kernel's
+	beam state (1.9 GB in all at 64 x 750 x 5000).  Outside the envelope (beam_width <= 8192, cutoff_top_n <= 128, C <= 8192, ...) it
+	raises ConvasrHipError."""
 	require_cuda(log_probs_bct)
 	B, C, T = log_probs_bct.shape
 	lp = as_cl(log_probs_bct, torch.float32)
@@ -875,23 +895,22 @@ def ctc_beam_search(log_probs_bct, lengths, blank, beam_width, cutoff_top_n = 40
 		raise ValueError(f'ctc_beam_search: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
 	N = C if cutoff_top_n is None else min(int(cutoff_top_n), C)  # (ctcdecode's pruning takes min(cutoff_top_n, C) too: the reference's default 40 over its 38 classes)
 	W, topk = int(beam_width), int(topk)
-	nbytes = _lib.load().convasr_ctc_beam_search_workspace_bytes(B, T, C, W, N, topk)
-	if nbytes < 0:
-		raise _lib.ConvasrHipError(_lib.load().convasr_last_error().decode())
+	fn, nbytes = _beam_route('ctc_beam_search', (B, T, C, W, N, topk), wide)
 	tokens = torch.empty(B, topk, T, dtype = torch.int64, device = dev)
 	offsets = torch.empty(B, topk, T, dtype = torch.int32, device = dev)
 	out_lengths = torch.empty(B, topk, dtype = torch.int64, device = dev)
 	log_prob = torch.empty(B, topk, dtype = torch.float32, device = dev)
 	ws = torch.empty(nbytes, dtype = torch.uint8, device = dev)  # per call, not the grow-only cache: B x T x W nodes of 8 bytes (393 MB at 64 x 750 x 1024) go back to the allocator
-	call('convasr_ctc_beam_search', ptr(lp), ptr(lengths), ptr(tokens), ptr(offsets), ptr(out_lengths), ptr(log_prob), ptr(ws), B, T, C, int(blank), W, N, float(cutoff_prob), topk, stream_ptr())
+	call(fn, ptr(lp), ptr(lengths), ptr(tokens), ptr(offsets), ptr(out_lengths), ptr(log_prob), ptr(ws), B, T, C, int(blank), W, N, float(cutoff_prob), topk, stream_ptr())
 	return tokens, offsets, out_lengths, log_prob
 
 
-def ctc_beam_search_lm(log_probs_bct, lengths, blank, beam_width, lm, alpha, beta, cutoff_top_n = 40, cutoff_prob = 1.0, topk = 1):
+def ctc_beam_search_lm(log_probs_bct, lengths, blank, beam_width, lm, alpha, beta, cutoff_top_n = 40, cutoff_prob = 1.0, topk = 1, *, wide = None):
 	"""CTC prefix beam search fused with an n-gram LM (include/convasr_hip.h: convasr_ctc_beam_search_lm).  lm: an lm.NgramLM built for
 	the C labels of log_probs_bct (its tables are uploaded to the device once and kept by the model); alpha / beta weigh the LM term.
-	Inputs and outputs as ctc_beam_search, except log_prob: (B, topk) fp64, the fused score lpb + lpnb + F (best first).  Outside the
-	kernel's envelope (that of ctc_beam_search plus C <= 256 and the LDS budget, see the header) it raises ConvasrHipError."""
+	Inputs, outputs and `wide` as ctc_beam_search, except log_prob: (B, topk) fp64, the fused score lpb + lpnb + F (best first).  A width
+	the LDS kernel's budget refuses runs the wide kernel (convasr_ctc_beam_search_lm_wide).  Outside the envelope (that of ctc_beam_search
+	plus C <= 256, see the header) it raises ConvasrHipError."""
 	require_cuda(log_probs_bct)
 	B, C, T = log_probs_bct.shape
 	if C != lm.num_classes:
@@ -905,16 +924,14 @@ def ctc_beam_search_lm(log_probs_bct, lengths, blank, beam_width, lm, alpha, bet
 		raise ValueError(f'ctc_beam_search_lm: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
 	N = C if cutoff_top_n is None else min(int(cutoff_top_n), C)
 	W, topk = int(beam_width), int(topk)
-	nbytes = _lib.load().convasr_ctc_beam_search_lm_workspace_bytes(B, T, C, W, N, topk)
-	if nbytes < 0:
-		raise _lib.ConvasrHipError(_lib.load().convasr_last_error().decode())
+	fn, nbytes = _beam_route('ctc_beam_search_lm', (B, T, C, W, N, topk), wide)
 	t = lm.device_tables(int(blank), dev)
 	tokens = torch.empty(B, topk, T, dtype = torch.int64, device = dev)
 	offsets = torch.empty(B, topk, T, dtype = torch.int32, device = dev)
 	out_lengths = torch.empty(B, topk, dtype = torch.int64, device = dev)
 	log_prob = torch.empty(B, topk, dtype = torch.float64, device = dev)
 	ws = torch.empty(nbytes, dtype = torch.uint8, device = dev)
-	call('convasr_ctc_beam_search_lm', ptr(lp), ptr(lengths), ptr(tokens), ptr(offsets), ptr(out_lengths), ptr(log_prob), ptr(ws), B, T, C, int(blank), W, N,
+	call(fn, ptr(lp), ptr(lengths), ptr(tokens), ptr(offsets), ptr(out_lengths), ptr(log_prob), ptr(ws), B, T, C, int(blank), W, N,
 	     float(cutoff_prob), topk, ptr(t['node_mask']), ptr(t['node_child']), ptr(t['node_word']), int(t['node_word'].numel()), ptr(t['ent_pb']), ptr(t['ent_sl']),
 	     int(t['ent_sl'].shape[0]), ptr(t['slots']), int(t['slots'].shape[0]), lm.space, lm.order, lm.start_state, float(alpha), float(beta), stream_ptr())
 	return tokens, offsets, out_lengths, log_prob

@@ -105,7 +105,8 @@ class BeamCTCGenerator:
 	the labels being the tokenizer's characters).  Per utterance it returns topk alternatives, best first; each is a Transcript
 	of word segments built from that beam's tokens: leading silence tokens are skipped, a new segment starts at every word-start token
 	when time stamps are given, and a token's time is begin + time_stamps[its frame offset].  GPU only: log_probs must be a CUDA tensor
-	(GreedyCTCGenerator also decodes CPU tensors); for the one-hot targets of --align, transcribe_batch uses a GreedyCTCGenerator."""
+	(GreedyCTCGenerator also decodes CPU tensors); for the one-hot targets of --align, transcribe_batch uses a GreedyCTCGenerator.
+	beam_width up to 8192 (the reference's default --beam-width 5000 runs the wide kernel: decoders.BeamSearchDecoder)."""
 
 	def __init__(self, beam_width = 64, topk = 1, cutoff_top_n = 40, cutoff_prob = 1.0, lm_path = None, beam_alpha = 0, beam_beta = 0):
 		from . import decoders, lm

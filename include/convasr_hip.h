@@ -532,7 +532,7 @@ int64_t convasr_ctc_beam_search_workspace_bytes(int B, int T, int C, int W, int 
  * (the MOST probable hypotheses; a slot the search could not fill has length 0 and -inf).  lengths[b] = 0: one empty hypothesis, 0.
  * Envelope, checked before any launch: 1 <= W <= 1024, 1 <= N <= min(C, 128), 1 <= topk <= W, 2 <= C <= 8192, 0 <= blank < C,
  * 0 < cutoff_prob <= 1, B * T * W < 2^31; outside it CONVASR_EINVAL / CONVASR_EUNSUPPORTED (the reference's default
- * --beam-width 5000 among them). */
+ * --beam-width 5000 among them: convasr_ctc_beam_search_wide below takes it). */
 int convasr_ctc_beam_search(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
                             float* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
                             void* stream);
@@ -574,6 +574,30 @@ int convasr_ctc_beam_search_lm(const float* log_probs, const int64_t* lengths, i
                                const uint32_t* node_mask, const int32_t* node_child, const int32_t* node_word, int n_nodes,
                                const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
                                int space, int order, int start_state, double alpha, double beta, void* stream);
+
+/* ---- The wide CTC prefix beam search: beam widths up to 8192 (the reference transcribe.py's default --beam-width 5000) ---------------
+ * convasr_ctc_beam_search_wide and convasr_ctc_beam_search_lm_wide take the arguments of convasr_ctc_beam_search and
+ * convasr_ctc_beam_search_lm and compute the same search, word for word: candidates, merging, tie keys, top-N / cutoff_prob, fp64 scores,
+ * the LM rules and the output layout.  At a width both forms accept they return the same bits.  They keep the beam state in the workspace
+ * instead of LDS; as before the workspace needs no initialisation and the call can be captured into a graph.  Only these differ:
+ *   Envelope, checked before any launch: 1 <= W <= 8192, 1 <= N <= min(C, 128), 1 <= topk <= W, 2 <= C <= 8192, 0 <= blank < C,
+ *   0 < cutoff_prob <= 1, B * T * W < 2^31, B * topk * T < 2^31; for the LM form also everything convasr_ctc_beam_search_lm checks except
+ *   its LDS budget (C <= 256 stays).  LDS use stays within 160 KiB over the whole envelope (117,328 bytes at W = C = 8192).  Outside it
+ *   CONVASR_EINVAL / CONVASR_EUNSUPPORTED.
+ *   Workspace bytes: up256(8 * B * T * W) + B * S, up_k(x) = x rounded up to a multiple of k, with
+ *     A = up16(52 * W) (LM form: up16(68 * W + 4 * W * MW), MW = ceil(C / 32)),
+ *     S = up256(2 * A + 24 * W + 4 * W * NW + 4 * TB), NW = ceil(N / 32), TB = the smallest power of two >= max(2 * W, 64):
+ *   the prefix-node arena, then per utterance two copies of the beam state and the per-frame candidate state and hash table. */
+int64_t convasr_ctc_beam_search_wide_workspace_bytes(int B, int T, int C, int W, int N, int topk);
+int convasr_ctc_beam_search_wide(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                 float* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                                 void* stream);
+int64_t convasr_ctc_beam_search_lm_wide_workspace_bytes(int B, int T, int C, int W, int N, int topk);
+int convasr_ctc_beam_search_lm_wide(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                    double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                                    const uint32_t* node_mask, const int32_t* node_child, const int32_t* node_word, int n_nodes,
+                                    const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
+                                    int space, int order, int start_state, double alpha, double beta, void* stream);
 
 #ifdef __cplusplus
 }
