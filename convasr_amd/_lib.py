@@ -16,6 +16,8 @@ LOSS_SCALER_FLOATS = 8  # include/convasr_hip.h: CONVASR_LOSS_SCALER_FLOATS
 ACT_NONE, ACT_RELU, ACT_HARDTANH, ACT_LEAKY_RELU = 0, 1, 2, 3
 PACK_FWD, PACK_DGRAD = 0, 1
 W_REFERENCE, W_KMAJOR = 0, 1  # include/convasr_hip.h: memory layout of a (Cout, Cin, K) parameter / gradient
+METRIC_CHARS, METRIC_WORDS = 0, 1  # include/convasr_hip.h: CONVASR_METRIC_CHARS / CONVASR_METRIC_WORDS
+METRIC_MAX_LEN = 16383  # CONVASR_METRIC_MAX_LEN
 
 c_int, c_i64, c_u64, c_f32, c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
 
@@ -105,6 +107,8 @@ _SIGNATURES = dict(
 	convasr_ctc_beam_search_lm_wide_workspace_bytes = (c_i64, [c_int] * 6),
 	convasr_ctc_beam_search_lm_wide = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int,
 	                                           c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p]),
+	convasr_edit_distance = (c_int, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_i64, c_p]),
+	convasr_ctc_greedy_collapse = (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
 )
 
 _lib = None

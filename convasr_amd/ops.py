@@ -935,3 +935,58 @@ def ctc_beam_search_lm(log_probs_bct, lengths, blank, beam_width, lm, alpha, bet
 	     float(cutoff_prob), topk, ptr(t['node_mask']), ptr(t['node_child']), ptr(t['node_word']), int(t['node_word'].numel()), ptr(t['ent_pb']), ptr(t['ent_sl']),
 	     int(t['ent_sl'].shape[0]), ptr(t['slots']), int(t['slots'].shape[0]), lm.space, lm.order, lm.start_state, float(alpha), float(beta), stream_ptr())
 	return tokens, offsets, out_lengths, log_prob
+
+
+# ------------------------------------------------------------------------------------------------ validation metrics
+
+def edit_distance(hyp, hyp_lengths, ref, ref_lengths, mode = _lib.METRIC_CHARS, space = -1):
+	"""Levenshtein distances of hypotheses against references (include/convasr_hip.h: convasr_edit_distance).  hyp: (B, K, Lh) or (B, Lh)
+	int64 tokens with hyp_lengths (B, K) / (B,); ref: (B, Lr) int64, rows read in place through their stride (y[:, 0] of a (B, n, Lpad)
+	batch needs no copy), ref_lengths (B,) read through its stride as well (ylen[:, 0]).  mode: _lib.METRIC_CHARS (units = the tokens that
+	are not `space`; space < 0: every token) or _lib.METRIC_WORDS (units = maximal runs of non-space tokens, space >= 0).
+	Returns (distance (B, K) int32 -- (B,) for a (B, Lh) hyp -- , ref_units (B,) int32).  Outside the envelope (Lh, Lr <= 16383,
+	B * K < 2^20, ...) it raises ConvasrHipError."""
+	require_cuda(hyp, ref)
+	squeeze = hyp.ndim == 2
+	if squeeze:
+		hyp, hyp_lengths = hyp.unsqueeze(1), torch.as_tensor(hyp_lengths).unsqueeze(1)
+	if hyp.ndim != 3 or ref.ndim != 2 or hyp.shape[0] != ref.shape[0]:
+		raise ValueError(f'edit_distance: hyp {tuple(hyp.shape)} and ref {tuple(ref.shape)} are not (B, K, Lh) and (B, Lr)')
+	B, K, Lh = hyp.shape
+	Lr = ref.shape[1]
+	dev = hyp.device
+	if hyp.dtype != torch.int64 or ref.dtype != torch.int64:
+		raise ValueError('edit_distance: hyp and ref must be int64 tokens')
+	hyp = hyp.contiguous()
+	if Lh == 0:  # (a zero-size tensor has no storage to point at; no token is read past a length anyway)
+		hyp = torch.zeros(B, K, 1, dtype = torch.int64, device = dev)
+	if Lr == 0 or ref.stride(1) != 1:
+		ref = torch.zeros(B, 1, dtype = torch.int64, device = dev) if Lr == 0 else ref.contiguous()
+	hyp_lengths = torch.as_tensor(hyp_lengths).to(device = dev, dtype = torch.int64).reshape(B, K).contiguous()
+	ref_lengths = torch.as_tensor(ref_lengths).to(device = dev, dtype = torch.int64)
+	if ref_lengths.shape != (B,):
+		raise ValueError(f'edit_distance: ref_lengths of shape {tuple(ref_lengths.shape)} for a batch of {B}')
+	distance = torch.empty(B, K, dtype = torch.int32, device = dev)
+	ref_units = torch.empty(B, dtype = torch.int32, device = dev)
+	call('convasr_edit_distance', ptr(hyp), ptr(hyp_lengths), ptr(ref), ref.stride(0), ptr(ref_lengths), ref_lengths.stride(0), ptr(distance), ptr(ref_units),
+	     B, K, Lh, Lr, int(mode), int(space), stream_ptr())
+	return (distance[:, 0] if squeeze else distance), ref_units
+
+
+def ctc_greedy_collapse(path, lengths, eps, space, blank_amount_to_space = 10):
+	"""GreedyCTCGenerator.generate's collapse (time_stamps None, silence = {eps, space}, word start = space) on the device
+	(include/convasr_hip.h: convasr_ctc_greedy_collapse).  path: (B, T) int64 per-frame argmax (ops.argmax); lengths (B,) frames, or None
+	(all T).  Returns (tokens (B, T) int64, 0 past the length; out_lengths (B,) int64).  Outside the envelope it raises ConvasrHipError."""
+	require_cuda(path)
+	if path.ndim != 2 or path.dtype != torch.int64:
+		raise ValueError(f'ctc_greedy_collapse: path must be a (B, T) int64 tensor, got {tuple(path.shape)} {path.dtype}')
+	B, T = path.shape
+	dev = path.device
+	path = path.contiguous()
+	lengths = torch.full((B,), T, dtype = torch.int64, device = dev) if lengths is None else torch.as_tensor(lengths).to(device = dev, dtype = torch.int64).contiguous()
+	if lengths.shape != (B,):
+		raise ValueError(f'ctc_greedy_collapse: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
+	tokens = torch.empty(B, T, dtype = torch.int64, device = dev)
+	out_lengths = torch.empty(B, dtype = torch.int64, device = dev)
+	call('convasr_ctc_greedy_collapse', ptr(path), ptr(lengths), ptr(tokens), ptr(out_lengths), B, T, int(eps), int(space), int(blank_amount_to_space), stream_ptr())
+	return tokens, out_lengths

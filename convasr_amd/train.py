@@ -10,6 +10,7 @@ Conv weights live in the arena TAP-MAJOR ([K][Cout][Cin], include/convasr_hip.h 
 That is the element order of the packed MFMA operand and of the weight-gradient slabs, so (a) the optimizer kernel also writes a
 bf16 mirror of the arena whose conv segments ARE the packed forward weights (no packing launches per step), and (b) the split-K
 combine of the weight gradient is a streaming sum instead of a transpose."""
+import math
 import os
 
 import torch
@@ -528,3 +529,85 @@ def train_epoch(model, optimizer, batches, sampler = None, scheduler = None, ite
 		if max_iterations is not None and iteration >= max_iterations:
 			break
 	return iteration
+
+
+def _finite_mean(values):
+	"""metrics.nanmean (metrics.py:247-253) over one CPU tensor: the mean of the finite values, summed in order as Python floats, -1.0 when
+	there are none."""
+	vals = [v for v in values.tolist() if math.isfinite(v)]
+	return sum(vals) / len(vals) if vals else -1.0
+
+
+def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_space = 10, return_text = False):
+	"""One validation set through the reference's apply_model + evaluate_model (train.py:119-300), for the first target head.
+
+	batches yields (meta, s, x, xlen, y, ylen) with the tensors on the device, as for train_epoch.  Per batch, under no_grad with the model
+	in evaluation mode: the forward with y / ylen (the per-utterance CTC loss), models.entropy and models.weighted_mean_entropy of
+	log_probs[0] / olen[0], the hypotheses -- ops.argmax + ops.ctc_greedy_collapse (GreedyCTCGenerator's rules, blank_amount_to_space) when
+	decoder is None, else the topk hypotheses of a decoders.BeamSearchDecoder -- and their CER / WER against y[:, 0] / ylen[:, 0] through
+	metrics.token_cer_wer (tokenizer: CharTokenizerLegacy or another one-character lowercase tokenizer; tokenizer.eps_id / space_id).  With
+	topk > 1 also cer_oracle / wer_oracle, the minimum over the hypotheses the search filled.
+
+	The score is against the ENCODED targets y, which is what the model is trained on; the reference scores against
+	pipeline.preprocess(meta['ref']).  The two differ only where the tokenizer maps a character to '*' (unk).  For the reference's string
+	semantics, decode and use metrics.cer_wer.
+
+	Returns dict(loss, entropy, cer, wer[, cer_oracle, wer_oracle]) of aggregates -- the mean over the finite per-utterance values, -1.0
+	when there are none (metrics.nanmean) -- and `utterances`: per-utterance CPU tensors in batch order (loss, entropy, uncertainty, cer,
+	wer[, cer_oracle, wer_oracle]); with return_text also `hyp`, the best hypothesis of every utterance as transcribe.join would give it.
+	Everything reaches the host in one copy at the end.  The hypotheses are scored as (B, K, T) token rows, T the batch's output frames, so T
+	is bound by ops.edit_distance's envelope: a batch of more than 16,383 output frames raises ConvasrHipError.  model.training is restored on return; parameters, batch-norm statistics, torch's
+	RNG and the dropout generator's offsets are left as they were."""
+	from . import metrics
+	training, drop_offset = model.training, Fn._DropoutState.offset
+	cols, hyp_tokens, n_batches = [], [], 0
+	model.eval()
+	try:
+		with torch.no_grad():
+			for meta, s, x, xlen, y, ylen in batches:
+				out = model(x, xlen, y = y, ylen = ylen)
+				lp, olen = out['log_probs'][0], out['olen'][0]
+				ent, unc = M.entropy(lp, olen, dim = 1), M.weighted_mean_entropy(lp, olen)
+				if decoder is None:
+					tokens, lengths = ops.ctc_greedy_collapse(ops.argmax(lp), olen, tokenizer.eps_id, tokenizer.space_id, blank_amount_to_space)
+					tokens, lengths, filled = tokens.unsqueeze(1), lengths.unsqueeze(1), None
+				else:
+					tokens, _, lengths, log_prob = decoder.decode_with_scores(lp, olen)
+					filled = torch.isfinite(log_prob)
+				c, w = metrics.token_cer_wer(tokens, lengths, y[:, 0], ylen[:, 0], tokenizer.space_id)
+				col = [out['loss'].double(), ent.double(), unc.double(), c[:, 0], w[:, 0]]
+				if tokens.shape[1] > 1:
+					inf = torch.full_like(c, float('inf'))
+					col += [torch.where(filled, c, inf).amin(dim = 1), torch.where(filled, w, inf).amin(dim = 1)]
+				cols.append(torch.stack(col))
+				if return_text:
+					hyp_tokens.append((tokens[:, 0], lengths[:, 0]))
+				n_batches += 1
+			if not n_batches:
+				raise ValueError('evaluate_model: no batches')
+			table = torch.cat(cols, dim = 1)
+			# one device-to-host copy: the per-utterance table (fp64 bits) and, for the text, the best hypotheses' lengths and tokens
+			parts = [table.contiguous().view(torch.int64).flatten()]
+			for t, l in hyp_tokens:
+				parts += [l, t.flatten()]
+			host = torch.cat(parts).cpu()
+	finally:
+		model.train(training)
+		Fn._DropoutState.offset = drop_offset
+	n_rows = table.shape[0]
+	table = host[:table.numel()].view(torch.float64).view(n_rows, -1)
+	names = ['loss', 'entropy', 'uncertainty', 'cer', 'wer'] + (['cer_oracle', 'wer_oracle'] if n_rows > 5 else [])
+	utt = {k: table[i].clone() for i, k in enumerate(names)}
+	utt['loss'], utt['entropy'], utt['uncertainty'] = utt['loss'].float(), utt['entropy'].float(), utt['uncertainty'].float()
+	res = {k: _finite_mean(utt[k]) for k in names if k != 'uncertainty'}
+	res['utterances'] = utt
+	if return_text:
+		hyp, pos = [], table.numel()
+		for t, l in hyp_tokens:
+			B, T = t.shape
+			lens = host[pos:pos + B].tolist()
+			toks = host[pos + B:pos + B + B * T].view(B, T).tolist()
+			pos += B + B * T
+			hyp += [tokenizer.decode([row[:n]])[0].strip() for row, n in zip(toks, lens)]
+		res['hyp'] = hyp
+	return res

@@ -599,6 +599,43 @@ int convasr_ctc_beam_search_lm_wide(const float* log_probs, const int64_t* lengt
                                     const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
                                     int space, int order, int start_state, double alpha, double beta, void* stream);
 
+/* ---- Validation metrics: metrics.py:409-421 (cer / wer, the edit distances train.py:evaluate_model scores every validation utterance
+ * with), transcript_generators.py:8-93 (the greedy collapse of GreedyCTCGenerator.generate) -------------------------------------------- */
+
+enum { CONVASR_METRIC_CHARS = 0, CONVASR_METRIC_WORDS = 1 };
+#define CONVASR_METRIC_MAX_LEN 16383
+
+/* Levenshtein distances of B x K hypotheses against B references, one launch.
+ * hyp (B, K, Lh) int64, contiguous; hyp_lengths (B, K) int64.  Reference b is ref[b * ref_stride + t], its length
+ * ref_lengths[b * ref_lengths_stride] (so y[:, 0] / ylen[:, 0] of a (B, n_targets, Lpad) batch are read in place).  Only tokens below each
+ * length are read; the lengths are clamped to [0, Lh] / [0, Lr] on the device.
+ * Units, with `space` a token id:
+ *   CONVASR_METRIC_CHARS: the tokens that are not `space` (str.replace(' ', '') over tokens); space < 0: every token is a unit.
+ *   CONVASR_METRIC_WORDS: the maximal runs of tokens that are not `space` (str.split() over tokens): leading, trailing and repeated spaces
+ *   make no empty words.  Two words are equal exactly when they have the same length and the same tokens (compared in full, never by hash).
+ * distance (B, K) int32 = the exact Levenshtein distance between the two unit sequences (unit cost for an insertion, a deletion and a
+ * substitution); ref_units (B,) int32 = the number of units of reference b (not clamped to 1).
+ * One 64-thread workgroup per pair; no workspace, no initialised memory, no memset or copy: the call can be captured into a graph.
+ * Envelope, checked before any launch: B >= 1, K >= 1, B * K < 2^20, 0 <= Lh, Lr <= CONVASR_METRIC_MAX_LEN, strides >= 0, a valid mode,
+ * space >= 0 in WORDS mode, no NULL pointer; outside it CONVASR_EINVAL. */
+int convasr_edit_distance(const int64_t* hyp, const int64_t* hyp_lengths, const int64_t* ref, int64_t ref_stride,
+                          const int64_t* ref_lengths, int64_t ref_lengths_stride, int32_t* distance, int32_t* ref_units, int B, int K,
+                          int Lh, int Lr, int mode, int64_t space, void* stream);
+
+/* The greedy CTC collapse of GreedyCTCGenerator.generate with time_stamps = None and a tokenizer whose silence tokens are {eps, space}
+ * and whose word-start token is space (CharTokenizerLegacy).  path (B, T) int64: the per-frame argmax (convasr_argmax); frames
+ * t < lengths[b] are read (clamped to [0, T]).  Per utterance, with `last` = eps, blanks = 0, repeat_ok = false:
+ *   frames before the first one that is neither eps nor space are skipped (when there is none, nothing is emitted);
+ *   then per frame c: c == eps: if last == space nothing happens; otherwise repeat_ok = true, ++blanks, and when
+ *   blanks >= blank_amount_to_space, space is emitted.  c != eps: if c == last and not repeat_ok nothing happens; otherwise c is
+ *   emitted, repeat_ok = false, blanks = 0.  `last` is the token emitted last (blanks is not reset by a suppressed repeat; a space
+ *   can be emitted twice in a row or at the end).
+ * tokens (B, T) int64 = the emitted tokens, 0 past out_lengths[b]; out_lengths (B,) int64.  One workgroup per utterance; no workspace,
+ * no memset or copy: the call can be captured into a graph.  Envelope, checked before any launch: B >= 1, T >= 1, B * T < 2^31,
+ * eps != space, both >= 0, blank_amount_to_space >= 0, no NULL pointer; outside it CONVASR_EINVAL. */
+int convasr_ctc_greedy_collapse(const int64_t* path, const int64_t* lengths, int64_t* tokens, int64_t* out_lengths, int B, int T,
+                                int eps, int space, int blank_amount_to_space, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
