@@ -354,11 +354,11 @@ template <typename T, int MODE, int SPLIT = 0> __global__ __launch_bounds__(256)
 						for (int k = 0; k < 8; ++k) out[k] *= keep[k];
 						if (GATE) {
 #pragma unroll
-							for (int k = 0; k < 8; ++k) gate |= (act_grad(pre[k], ac) != 0.f && keep[k] != 0.f) ? (1u << k) : 0u;
+							for (int k = 0; k < 8; ++k) gate |= (act_passes(pre[k], ac) && keep[k] != 0.f) ? (1u << k) : 0u;
 						}
 					} else if (GATE) {
 #pragma unroll
-						for (int k = 0; k < 8; ++k) gate |= act_grad(pre[k], ac) != 0.f ? (1u << k) : 0u;
+						for (int k = 0; k < 8; ++k) gate |= act_passes(pre[k], ac) ? (1u << k) : 0u;
 					}
 				}
 				if constexpr (SPLIT == 0) store8<T>(reinterpret_cast<T*>(p.out) + w.idx, out);

@@ -174,25 +174,33 @@ __device__ __forceinline__ int valid_len(const float* xlen, int b, int T) {
 // element (the activation kind is wave-uniform, so hipcc branches instead of selecting): the conv epilogue spent ~9,000 cycles per
 // tile staging 64 accumulators per lane that way (in-kernel stamps).  The kind is folded ONCE into four constants:
 //   value:    leaky ? (v > 0 ? v : v * slope) : min(max(v, lo), hi)        none: (-inf, +inf), relu: (0, +inf), hardtanh: (lo, hi)
-//   gradient: (pre > lo && pre < hi) ? 1 : gelse                            relu / hardtanh: 0, leaky: slope, none: 1
-// (strict inequalities, matching ATen's backward formulas).
-struct ActConst { float lo, hi, slope, gelse; int leaky; };
+//   gradient: (pre <= glo || pre >= ghi) ? gelse : 1                        relu / hardtanh: 0, leaky: slope, none: 1
+// The gradient is ATen's: zeroed (leaky-relu: scaled) exactly where the pre-activation COMPARES <= lo or >= the upper bound -- 0 at both
+// ends of hardtanh and at relu's 0, the slope at leaky-relu's 0.  glo / ghi are the bounds that exist and NaN (never compares) for those
+// that do not -- relu's and leaky-relu's upper one, both of the identity -- so that the gradient passes at +inf (identity: -inf too)
+// like at any other value.
+// NaN: the value of every kind is NaN (torch propagates it; v_med3_f32 / v_max_f32 alone would return lo and hide a diverged step from
+// the non-finite-loss check and the fp16 loss scaler); in the gradient a NaN pre-activation compares with nothing, so it PASSES the
+// gradient unchanged, gate bit 1 -- what ATen's relu / hardtanh backward do (its leaky-relu backward would scale by the slope there).
+struct ActConst { float lo, hi, slope, gelse, glo, ghi; int leaky; };
 __host__ __device__ __forceinline__ ActConst act_const(int act, float lo, float hi) {
 	ActConst c;
-	c.lo = -INFINITY; c.hi = INFINITY; c.slope = 1.f; c.gelse = 1.f; c.leaky = 0;
-	if (act == CONVASR_ACT_RELU) { c.lo = 0.f; c.gelse = 0.f; }
-	else if (act == CONVASR_ACT_HARDTANH) { c.lo = lo; c.hi = hi; c.gelse = 0.f; }
-	else if (act == CONVASR_ACT_LEAKY_RELU) { c.lo = 0.f; c.slope = lo; c.gelse = lo; c.leaky = 1; }
+	c.lo = -INFINITY; c.hi = INFINITY; c.slope = 1.f; c.gelse = 1.f; c.leaky = 0; c.glo = c.ghi = __builtin_nanf("");
+	if (act == CONVASR_ACT_RELU) { c.lo = c.glo = 0.f; c.gelse = 0.f; }
+	else if (act == CONVASR_ACT_HARDTANH) { c.lo = c.glo = lo; c.hi = c.ghi = hi; c.gelse = 0.f; }
+	else if (act == CONVASR_ACT_LEAKY_RELU) { c.lo = c.glo = 0.f; c.slope = lo; c.gelse = lo; c.leaky = 1; }
 	return c;
 }
 __device__ __forceinline__ float apply_act(float v, const ActConst& c) {
 	const float clamped = fminf(fmaxf(v, c.lo), c.hi), lk = v > 0.f ? v : v * c.slope;
-	return c.leaky ? lk : clamped;
+	return (c.leaky || v != v) ? lk : clamped;  // (lk of a NaN is NaN)
 }
-// the same for callers that know at compile time that the kind is not leaky-relu: one v_med3_f32 instead of six instructions
-__device__ __forceinline__ float apply_clamp(float v, const ActConst& c) { return __builtin_amdgcn_fmed3f(v, c.lo, c.hi); }
+// the same for callers that know at compile time that the kind is not leaky-relu: one v_med3_f32 (+ the NaN select) instead of six instructions
+__device__ __forceinline__ float apply_clamp(float v, const ActConst& c) { return v != v ? v : __builtin_amdgcn_fmed3f(v, c.lo, c.hi); }
+// does the gradient pass unchanged?  (negated comparisons: true for a NaN)
+__device__ __forceinline__ bool act_passes(float pre, const ActConst& c) { return !(pre <= c.glo) && !(pre >= c.ghi); }
 // derivative w.r.t. the pre-activation value
-__device__ __forceinline__ float act_grad(float pre, const ActConst& c) { return (pre > c.lo && pre < c.hi) ? 1.f : c.gelse; }
+__device__ __forceinline__ float act_grad(float pre, const ActConst& c) { return act_passes(pre, c) ? 1.f : c.gelse; }
 
 // Philox4x32-10 (Salmon et al. 2011): counter = element index / 4, key = seed; returns 4 uniforms in [0,1)
 template <int ROUNDS> __device__ __forceinline__ void philox4x32(uint64_t seed, uint64_t ctr, unsigned (&r)[4]) {

@@ -303,6 +303,47 @@ def test_conv1d_epilogue_stats_scale_act_mask():
 
 
 @gpu
+@pytest.mark.parametrize('dtype', ['f32', 'bf16', 'f16'])
+def test_conv1d_epilogue_stats_of_channels_far_from_zero_mean(dtype):
+	"""Per-channel output means of 0, 10 and 100 standard deviations (a large bias, which the epilogue adds before the statistics), several
+	m-tiles: mean and invstd out of bn_finalize against float64.  The kernels form E[x^2] - m^2 from fp32 per-lane partial sums that are
+	carried to fp64 per tile.  L = the addends of one fp32 chain: csrc/conv.hip's epilogue adds 2 x 16 values per lane and one cross-lane
+	term (33); csrc/conv_v2s.hip's at most 4 x 4 and two (18).  With u = 2^-24: the variance is off by at most L u (1 + m^2 / var) relative,
+	invstd by half of that plus its own three fp32 roundings (cast, sqrt, divide); the mean by (L + 1) u (|m| + std).  Asserted at 0 and 10
+	standard deviations, recorded at 100 (printed; profiles/NOTEBOOK.md), next to the error of fp32 F.batch_norm on the CPU on the same data."""
+	from convasr_amd import ops, _lib
+	torch.manual_seed(5)
+	dt = torch.float32 if dtype == 'f32' else HALF[dtype][0]
+	B, Cin, Cout, T, K, eps = 3, 64, 192, 700, 5, 1e-5
+	x, w = torch.randn(B, Cin, T).to(dt).float(), (torch.randn(Cout, Cin, K) / (Cin * K) ** 0.5).to(dt).float()
+	raw = F.conv1d(x.double(), w.double(), padding = K // 2)
+	sigmas = torch.tensor([0.0, 10.0, 100.0]).repeat(Cout // 3)
+	bias = (sigmas * raw.std(dim = (0, 2)) - raw.mean(dim = (0, 2))).float()
+	out = raw + bias.double()[None, :, None]
+	n = B * T
+	m64, var64 = out.mean(dim = (0, 2)), out.var(dim = (0, 2), unbiased = False)
+	invstd64 = 1.0 / torch.sqrt(var64 + eps)
+	d = dev()
+	stats = ops.ConvStats(Cout, B, T, d)
+	ops.conv1d(ops.as_cl(x.to(d), dt), ops.pack_weight(w.to(d), dt, _lib.PACK_FWD), Cout, K, 1, 1, K // 2, bias = bias.to(d), stats = stats)
+	assert stats.rows >= 2 * B, stats.rows
+	mean, invstd = (t.double().cpu() for t in ops.bn_finalize(stats, n, None, None, None, None, 0.1, eps)[:2])
+	# the reference's own arithmetic: fp32 F.batch_norm on the CPU (momentum 1: the running statistics are this batch's)
+	rm, rv = torch.zeros(Cout), torch.ones(Cout)
+	F.batch_norm(out.float(), rm, rv, None, None, True, 1.0, eps)
+	invstd_cpu = 1.0 / torch.sqrt(rv.double() * (n - 1) / n + eps)
+	L, u = 33, 2.0 ** -24
+	ratio = m64 ** 2 / var64
+	bar_invstd, bar_mean = 0.5 * L * u * (1 + ratio) + 3 * u, (L + 1) * u * (m64.abs() + var64.sqrt())
+	err_invstd, err_mean, err_cpu = (invstd - invstd64).abs() / invstd64, (mean - m64).abs(), (invstd_cpu - invstd64).abs() / invstd64
+	for i, s in enumerate((0, 10, 100)):
+		print(f'    {dtype}, mean at {s} std: invstd rel err {float(err_invstd[i::3].max()):.2e} (bar {float(bar_invstd[i::3].max()):.2e}; fp32 F.batch_norm on the CPU: {float(err_cpu[i::3].max()):.2e}), mean abs err {float(err_mean[i::3].max()):.2e} (bar {float(bar_mean[i::3].max()):.2e})')
+	held = sigmas <= 10
+	assert bool((err_invstd[held] <= bar_invstd[held]).all()) and bool((err_mean[held] <= bar_mean[held]).all())
+	assert bool(torch.isfinite(invstd).all())
+
+
+@gpu
 @pytest.mark.parametrize('case', [c for c in CONV_CASES if c[5] == 1])
 @pytest.mark.parametrize('dtype', ['f32', 'bf16', 'f16'])
 def test_conv1d_dgrad(case, dtype):
