@@ -11,6 +11,9 @@ Two paths:
   tokenizer in which every class decodes to one character c with c.lower() == c and only the space class decodes to whitespace
   (CharTokenizerLegacy with the Russian alphabet is one): there it equals the string path applied to tokenizer.decode of the same tokens.
   For any other tokenizer (BPE) decode the tokens and use the string path."""
+import collections
+import math
+
 import numpy as np
 import torch
 
@@ -88,3 +91,413 @@ def token_cer_wer(tokens, lengths, ref, ref_lengths, space):
 	wd, words = ops.edit_distance(tokens, lengths, ref, ref_lengths, _lib.METRIC_WORDS, int(space))
 	shape = (-1, ) + (1, ) * (cd.ndim - 1)
 	return cd.double() / units.clamp(min = 1).double().view(shape), wd.double() / words.clamp(min = 1).double().view(shape)
+
+
+# ------------------------------------------------------------------------------------------------ alignment and error analysis
+#
+# The reference's align_strings / align_words / ErrorTagger / WordTagger / ErrorAnalyzer (metrics.py:17-232, 261-407) with its names, keyword
+# arguments and result keys, so that configurations written for it work unchanged.  The quadratic part, the Needleman-Wunsch alignment, runs
+# on the GPU (ops.nw_align); everything else is host string code that CONSUMES alignment results and scores: every function below takes an
+# `aligner` and, where it needs error rates, a `scorer`, and defaults them to the GPU ones.
+#   aligner(a_seqs, b_seqs, scores) -> per pair (a_index, b_index): lists of ints, one entry per alignment column, -1 for a gap
+#   scorer(hyps, refs) -> (cers, wers): cer_wer's contract
+
+placeholder = '|'
+space = ' '
+silence = placeholder + space
+
+WORD_ALIGN_SCORES = (100, -6, -8, -3)  # (match, sub, del, ins), see align_strings
+CHAR_ALIGN_SCORES = (5, -3, -4, -3)
+
+
+def replace_placeholder(s, rep = ''):
+	return s.replace(placeholder, rep)
+
+
+def gpu_aligner(a_seqs, b_seqs, scores, device = None):
+	"""The default aligner: all pairs in one ops.nw_align call, the index rows back in one device-to-host copy."""
+	if not a_seqs:
+		return []
+	device = _device(device)
+	N = len(a_seqs)
+	La, Lb = max(map(len, a_seqs)), max(map(len, b_seqs))
+	a, b = np.zeros((N, max(La, 1)), dtype = np.int32), np.zeros((N, max(Lb, 1)), dtype = np.int32)
+	for i, (s, t) in enumerate(zip(a_seqs, b_seqs)):
+		a[i, :len(s)], b[i, :len(t)] = s, t
+	lengths = torch.from_numpy(np.array([[len(s) for s in a_seqs], [len(t) for t in b_seqs]], dtype = np.int32)).to(device)
+	ai, bi, n, _ = ops.nw_align(torch.from_numpy(a).to(device)[:, :La], lengths[0], torch.from_numpy(b).to(device)[:, :Lb], lengths[1], scores)
+	host = torch.cat([n, ai.flatten(), bi.flatten()]).cpu().numpy()
+	W = La + Lb
+	n, ai, bi = host[:N], host[N:N + N * W].reshape(N, W), host[N + N * W:].reshape(N, W)
+	return [(ai[p, :n[p]].tolist(), bi[p, :n[p]].tolist()) for p in range(N)]
+
+
+def _aligned_units(index_a, index_b, a, b, unit_gap):
+	"""The aligner's aligned sequences as the reference builds them: against a unit u the gap is placeholder * len(u) where the walk
+	emitted it (unit_gap) and one placeholder in the leading / trailing runs that are emitted without walking."""
+	n = len(index_a)
+	gap_side = lambda k: 0 if index_a[k] < 0 else 1 if index_b[k] < 0 else None
+	lead = 0  # a leading run of gaps on one side is the prefix: a walked gap is followed, further left, by a unit of that side
+	while lead < n and gap_side(lead) is not None and gap_side(lead) == gap_side(0):
+		lead += 1
+	trail, tail_side = n, 0 if len(a) < len(b) else 1  # the tail pads the hypothesis when it is the shorter side, else the reference
+	while trail > lead and gap_side(trail - 1) == tail_side:
+		trail -= 1
+	out_a, out_b = [], []
+	for k, (i, j) in enumerate(zip(index_a, index_b)):
+		walked = unit_gap and lead <= k < trail
+		out_a.append(a[i] if i >= 0 else placeholder * (len(b[j]) if walked else 1))
+		out_b.append(b[j] if j >= 0 else placeholder * (len(a[i]) if walked else 1))
+	return out_a, out_b
+
+
+def align_strings_batch(hyps, refs, aligner = None):
+	"""align_strings over lists: [( _hyp_, _ref_ )] per pair.  Two aligner calls for the whole batch -- one over the word ids of every pair,
+	one over the characters of every span of non-equal words of every pair -- so on the GPU two launches and two device-to-host copies,
+	whatever the batch size (while the batch fits under ops.nw_align's workspace cap; a batch it has to split adds one launch per split)."""
+	aligner = aligner or gpu_aligner
+	hyps, refs = list(hyps), list(refs)
+	if len(hyps) != len(refs):
+		raise ValueError(f'align_strings_batch: {len(hyps)} hypotheses for {len(refs)} references')
+	hyp_words, ref_words = [h.split() for h in hyps], [r.split() for r in refs]
+	ids = {}
+	word_ids = lambda words: [[ids.setdefault(w, len(ids)) for w in ws] for ws in words]
+	word_level = aligner(word_ids(hyp_words), word_ids(ref_words), WORD_ALIGN_SCORES)
+	# per pair: pieces that are either an equal word (a string) or the number of a span to be aligned character by character
+	pieces, span_hyp, span_ref = [], [], []
+	for (index_a, index_b), hw, rw in zip(word_level, hyp_words, ref_words):
+		cur, hyp_buffer, ref_buffer = [], [], []
+
+		def flush():
+			if hyp_buffer or ref_buffer:
+				cur.append(len(span_hyp))
+				span_hyp.append(space.join(hyp_buffer))
+				span_ref.append(space.join(ref_buffer))
+				hyp_buffer.clear()
+				ref_buffer.clear()
+
+		for h, r in zip(*_aligned_units(index_a, index_b, hw, rw, unit_gap = True)):
+			if h == r:
+				flush()
+				cur.append(h)
+			elif placeholder in h:
+				ref_buffer.append(r)
+			elif placeholder in r:
+				hyp_buffer.append(h)
+			else:
+				ref_buffer.append(r)
+				hyp_buffer.append(h)
+		flush()
+		pieces.append(cur)
+	char_level = aligner([[ord(c) for c in s] for s in span_hyp], [[ord(c) for c in s] for s in span_ref], CHAR_ALIGN_SCORES)
+	spans = [tuple(''.join(u) for u in _aligned_units(ia, ib, sh, sr, unit_gap = False)) for (ia, ib), sh, sr in zip(char_level, span_hyp, span_ref)]
+	out = []
+	for cur in pieces:
+		_hyp_ = space.join(p if isinstance(p, str) else spans[p][0] for p in cur)
+		_ref_ = space.join(p if isinstance(p, str) else spans[p][1] for p in cur)
+		assert len(_hyp_) == len(_ref_)
+		out.append((_hyp_, _ref_))
+	return out
+
+
+def align_strings(*, hyp, ref, aligner = None):
+	"""metrics.align_strings (metrics.py:365-407): two strings of equal length, the hypothesis and the reference with placeholder '|' where
+	the other side has a character the first lacks.  Two levels: (1) the word ids of hyp.split() / ref.split() are aligned (equal words,
+	equal ids); (2) every maximal run of aligned words that are not equal is joined by spaces and aligned again character by character;
+	(3) equal words and aligned runs are joined by spaces.  The aligned reference can gain spaces the input did not have
+	(hyp 'б б', ref 'б' gives ('б б', 'б |')): the reference's behaviour, kept.
+
+	Scores (match, sub, del, ins): (100, -6, -8, -3) for words and (5, -3, -4, -3) for characters.  These are what the reference RUNS
+	with, not the tuples its signature shows ((100, -2, -8, -6) and (5, -2, -4, -3)): its unpacking assigns the fourth number to the
+	substitution score and leaves the insertion score at the aligner's default -3.  A property of the reference, kept for parity.
+	One departure: a word made only of two or more '|' characters is not told apart from a gap the way the reference would."""
+	return align_strings_batch([hyp], [ref], aligner)[0]
+
+
+def _split_word_pairs(_hyp_, _ref_, copy_space = False):
+	"""Cuts a pair of aligned strings at the reference's spaces into (hyp word, ref word) pairs of equal length."""
+	assert len(_hyp_) == len(_ref_)
+	hyp, ref = list(_hyp_), list(_ref_)
+	ref_chars = [i for i, c in enumerate(ref) if c != placeholder]
+	first, last = (ref_chars[0], ref_chars[-1]) if ref_chars else (len(ref), -1)
+	for i in range(len(ref)):  # the hypothesis' spaces outside the reference's extent become spaces of the reference
+		if (i < first or i > last) and hyp[i] == space and ref[i] == placeholder:
+			ref[i] = space
+	if copy_space and ref_chars:  # a reference word glued to the start / the end of a longer hypothesis word is cut off it
+		hyp_plain, ref_plain = replace_placeholder(''.join(hyp)), replace_placeholder(''.join(ref))
+		if hyp_plain.endswith(ref_plain) and first - 1 >= 0 and hyp[first - 1] not in silence:
+			ref[first - 1] = space
+		if hyp_plain.startswith(ref_plain) and last + 1 < len(hyp) and hyp[last + 1] not in silence:
+			ref[last + 1] = space
+	ref.append(space)
+	hyp.append(space)
+	start, words = 0, []
+	for i in range(len(ref)):
+		if ref[i] != space:
+			continue
+		if hyp[i] in silence:
+			stop, resume = i, i + 1
+		else:  # the hypothesis runs on through this space: the space is undone; left of the reference's extent it stays with the word before it
+			stop = resume = i + 1 if (ref_chars and i < first) else i
+			ref[i] = placeholder
+		if start != stop:
+			words.append((''.join(hyp[start:stop]), ''.join(ref[start:stop])))
+		start = resume
+	return words
+
+
+def _prefer_replacement(hyp, ref):
+	"""An insertion next to a deletion becomes one replacement; columns that are gaps on both sides afterwards are dropped."""
+	hyp, ref = list(hyp), list(ref)
+	for k in range(len(ref) - 1):
+		if ref[k] == placeholder and hyp[k] != placeholder and ref[k + 1] != placeholder and hyp[k + 1] == placeholder:
+			ref[k], ref[k + 1] = ref[k + 1], placeholder
+		elif hyp[k] == placeholder and ref[k] != placeholder and hyp[k + 1] != placeholder and ref[k + 1] == placeholder:
+			hyp[k], hyp[k + 1] = hyp[k + 1], placeholder
+	keep = [k for k in range(len(ref)) if not (hyp[k] == ref[k] == placeholder)]
+	return ''.join(hyp[k] for k in keep), ''.join(ref[k] for k in keep)
+
+
+class ErrorTagger:
+	"""metrics.ErrorTagger (metrics.py:17-56): one tag per aligned word pair -- ok, typo_easy, typo_hard, missing, missing_ref."""
+	typo_easy = 'typo_easy'
+	typo_hard = 'typo_hard'
+	missing = 'missing'
+	missing_ref = 'missing_ref'
+	ok = 'ok'
+
+	error_tags = [typo_easy, typo_hard, missing, missing_ref]
+
+	def tag(self, *, hyp, ref, hyp_tags = (), ref_tags = (), p = 0.5, L = 3, clamp = False):
+		pairs = list(zip(hyp, ref))
+		errors = sum(h != r for h, r in pairs if not (h == space and r == placeholder))
+		errors_on_characters = sum(h != r for h, r in pairs if h not in silence and r not in silence)
+		ok_except_end = all(h == r or k >= len(ref) - 2 or (h == space and r == placeholder) for k, (h, r) in enumerate(pairs))
+		ref_gaps = ref.count(placeholder)
+		ref_chars = len(ref) - ref_gaps
+		hyp_empty, ref_empty = hyp.count(placeholder) == len(hyp), ref_gaps == len(ref)
+		hyp_known = WordTagger.vocab_hit in hyp_tags or WordTagger.stop in hyp_tags
+		vocab_typo_easy = (ref_empty and hyp_known) or (hyp_empty and WordTagger.stop in ref_tags)
+		short_typo = len(ref) == 1 or (ref_chars == 0 and len(hyp) < L) or (0 < ref_chars < L and len(hyp) <= L)
+		short_few_replacements = ref_chars < L and errors_on_characters <= 1
+		is_typo = vocab_typo_easy or short_typo or (errors >= 0 and hyp.count(placeholder) < p * len(ref) and ref_gaps < p * len(ref))
+		if hyp == ref:
+			error_tag = self.ok
+		elif is_typo:
+			easy = vocab_typo_easy or short_few_replacements or errors <= 1 or (len(ref) > 2 and errors == 2 and ok_except_end) or (len(ref) >= 5 and errors <= 2)
+			error_tag = self.typo_easy if easy else self.typo_hard
+		else:
+			error_tag = self.missing_ref if ref_gaps >= p * len(ref) else self.missing
+		if clamp:
+			errors = errors if error_tag in (self.typo_easy, self.ok) else -1 if error_tag == self.typo_hard else -2
+		return error_tag, errors
+
+
+class WordTagger(dict):
+	"""metrics.WordTagger (metrics.py:59-76): vocab_hit / vocab_miss by membership in `vocab`, plus the tag of word_tags whose word list
+	holds the word's stem (e.g. 'stop').  The default stemmer is the identity."""
+	vocab_hit = 'vocab_hit'
+	vocab_miss = 'vocab_miss'
+	stop = 'stop'
+
+	def __init__(self, stemmer = None, word_tags = {}, vocab = set()):
+		super().__init__()
+		self.stemmer = stemmer if stemmer is not None else (lambda word: word)
+		self.vocab = vocab
+		self.stem2tag = {self.stemmer(word): tag for tag, words in word_tags.items() for word in words}
+
+	def __missing__(self, word):
+		self[word] = self.stem2tag.get(self.stemmer(word))
+		return self[word]
+
+	def tag(self, word):
+		word_tag = self[word]
+		return [self.vocab_hit if word in self.vocab else self.vocab_miss] + ([word_tag] if word_tag else [])
+
+
+def _word_alignment(_hyp_, _ref_, word_tagger, error_tagger, postproc):
+	"""align_words without the per-word CER."""
+	word_pairs = _split_word_pairs(_hyp_, _ref_)
+	if postproc:
+		word_pairs = [pair for hw, rw in word_pairs for pair in _split_word_pairs(*_prefer_replacement(hw, rw), copy_space = True)]
+	words = []
+	for hyp_word, ref_word in word_pairs:
+		assert len(hyp_word) == len(ref_word)
+		w = dict(_hyp_ = hyp_word, _ref_ = ref_word, hyp = replace_placeholder(hyp_word), ref = replace_placeholder(ref_word))
+		w['ref_tags'] = word_tagger.tag(w['ref'])
+		w['hyp_tags'] = word_tagger.tag(w['hyp'])
+		w['error_tags'] = [error_tagger.tag(hyp = w['hyp'], ref = w['ref'], hyp_tags = w['hyp_tags'], ref_tags = w['ref_tags'])[0]]
+		w['error_tag'] = w['error_tags'][0]
+		w['len'] = len(w['ref'])
+		words.append(w)
+	return words
+
+
+def _add_word_cer(alignments, scorer):
+	"""w['cer'] for every word of every alignment, one scorer call."""
+	words = [w for alignment in alignments for w in alignment]
+	for w, c in zip(words, scorer([w['hyp'] for w in words], [w['ref'] for w in words])[0]):
+		w['cer'] = c
+
+
+def align_words(_hyp_, _ref_, word_tagger = None, error_tagger = None, postproc = False, compute_cer = False, scorer = None):
+	"""metrics.align_words (metrics.py:261-362): the word pairs of a pair of aligned strings (align_strings' result), each a dict with
+	_hyp_ / _ref_ (aligned), hyp / ref (placeholders removed), ref_tags / hyp_tags (word_tagger), error_tags / error_tag (error_tagger), len
+	and, with compute_cer, cer (all words in one scorer call; default cer_wer on the GPU).  postproc: adjacent insertion + deletion become a
+	replacement and a reference word glued to an end of a longer hypothesis word is cut off."""
+	words = _word_alignment(_hyp_, _ref_, WordTagger() if word_tagger is None else word_tagger, error_tagger or ErrorTagger(), postproc)  # (an unused WordTagger is an empty dict: falsy)
+	if compute_cer:
+		_add_word_cer([words], scorer or cer_wer)
+	return words
+
+
+def extract_metric_value(analysis_result, key, sep = '.', missing = None):
+	keys = key.split(sep)
+	assert len(keys) <= 2
+	value = analysis_result
+	for k in keys:
+		if not isinstance(value, dict):
+			return missing
+		value = value.get(k, missing)
+	return value
+
+
+def nanmean(list_of_dicts, key, sep = '.', missing = -1.0):
+	"""metrics.nanmean (metrics.py:247-253): the mean of the finite values under `key`, summed in order; `missing` when there are none."""
+	vals = [v for v in (extract_metric_value(d, key, sep) for d in list_of_dicts) if v is not None and math.isfinite(v)]
+	return sum(vals) / len(vals) if vals else missing
+
+
+class ErrorAnalyzer:
+	"""metrics.ErrorAnalyzer (metrics.py:78-232).  configs: name -> dict of filter_words' keyword arguments (word_include_tags,
+	word_exclude_tags, error_include_tags, error_exclude_tags) and optionally 'postprocessor', a key of `postprocessors`; empty configs mean
+	dict(default = {}).  aligner / scorer: see the section comment; None = the GPU."""
+
+	def __init__(self, word_tagger = None, error_tagger = None, configs = {}, postprocessors = {}, aligner = None, scorer = None):
+		self.word_tagger = word_tagger if word_tagger is not None else WordTagger()
+		self.error_tagger = error_tagger if error_tagger is not None else ErrorTagger()
+		self.configs = configs or dict(default = {})
+		self.postprocessors = postprocessors
+		self.aligner = aligner
+		self.scorer = scorer
+
+	def aggregate(self, analyzed, sep = '__', defaults = {}):
+		"""The validation line's numbers: nanmean of every numeric key of the analyses (config keys as config__key, the default config's
+		also bare), and errors = dict(distribution: clamped error count -> words, words: the word pairs that are not ok)."""
+		numeric = lambda d: [k for k, v in d.items() if isinstance(v, (float, int))]
+		keys = numeric(analyzed[0])
+		for c in self.configs:
+			keys += [c + sep + k for k in numeric(analyzed[0].get(c, {}))]
+		stats = dict(defaults)
+		stats.update({k: nanmean(analyzed, k, sep = sep) for k in keys})
+		prefix = 'default' + sep
+		stats.update({name[len(prefix):]: value for name, value in list(stats.items()) if name.startswith(prefix)})
+		distribution, error_words = collections.defaultdict(int), []
+		for a in analyzed:
+			for w in a.get('alignment', []):
+				error_tag, errors = self.error_tagger.tag(hyp = w['hyp'], ref = w['ref'], clamp = True)
+				distribution[errors] += 1
+				if error_tag != ErrorTagger.ok:
+					error_words.append(w)
+		stats['errors'] = dict(distribution = dict(sorted(distribution.items())), words = error_words)
+		return stats
+
+	def filter_words(self, word_alignment, word_include_tags = [], word_exclude_tags = [], error_include_tags = [], error_exclude_tags = [], **kwargs):
+		word_include_tags, word_exclude_tags, error_include_tags, error_exclude_tags = map(set, [word_include_tags, word_exclude_tags, error_include_tags, error_exclude_tags])
+		res = []
+		for w in word_alignment:
+			ref_tags, error_tags = set(w['ref_tags']), set(w['error_tags'])
+			if ref_tags & word_exclude_tags or error_tags & error_exclude_tags:
+				continue
+			if (word_include_tags and not ref_tags & word_include_tags) or (error_include_tags and not error_tags & error_include_tags):
+				continue
+			res.append(w)
+		return res
+
+	def compute_wordwise_metrics(self, filtered_alignment):
+		n = len(filtered_alignment)
+		n_ok = sum(ErrorTagger.ok in w['error_tags'] for w in filtered_alignment)
+		n_missing = sum(ErrorTagger.missing in w['error_tags'] for w in filtered_alignment)
+		return dict(
+			num_words = n, num_words_ok = n_ok, num_words_missing = n_missing,
+			mer_wordwise = n_missing / n if n != 0 else 0,
+			wer_wordwise = 1.0 - n_ok / n if n != 0 else 0,
+			cer_wordwise = sum(w['cer'] for w in filtered_alignment) / n if n != 0 else 0)
+
+	def compute_vocabness_metrics(self, word_alignment, filtered_alignment, postprocess_transcript = None, **kwargs):
+		n = len(filtered_alignment)
+		hit = lambda k: sum(self.word_tagger.vocab_hit in w[k] for w in filtered_alignment) / n if n != 0 else 0
+		return dict(ref_vocabness = hit('ref_tags'), hyp_vocabness = hit('hyp_tags'))
+
+	@staticmethod
+	def _corrected(word_alignment, filtered_alignment, postprocess_transcript, correct_filtered):
+		"""(hyp, ref) texts in which the FILTERED words (correct_filtered) or all the OTHER words are replaced by the ground truth; a word
+		counts as filtered when it equals a filtered one, as the reference's `w in filtered_alignment` does."""
+		chosen = {(w['_hyp_'], w['_ref_']) for w in filtered_alignment}
+		hyp = space.join(w['ref'] if ((w['_hyp_'], w['_ref_']) in chosen) == correct_filtered else w['hyp'] for w in word_alignment)
+		return postprocess_transcript(hyp), postprocess_transcript(space.join(w['ref'] for w in word_alignment))
+
+	def compute_pseudo_metrics(self, word_alignment, filtered_alignment, postprocess_transcript = None, **kwargs):
+		"""What CER / WER would be if the filtered words were right."""
+		c, w = (self.scorer or cer_wer)(*[[s] for s in self._corrected(word_alignment, filtered_alignment, postprocess_transcript or (lambda s: s), True)])
+		return dict(cer_pseudo = c[0], wer_pseudo = w[0])
+
+	def compute_filtered_metrics(self, word_alignment, filtered_alignment, postprocess_transcript = None, **kwargs):
+		"""What CER / WER would be if all but the filtered words were right."""
+		c, w = (self.scorer or cer_wer)(*[[s] for s in self._corrected(word_alignment, filtered_alignment, postprocess_transcript or (lambda s: s), False)])
+		return dict(cer_filtered = c[0], wer_filtered = w[0])
+
+	def analyze_batch(self, hyps, refs, postprocess_fn = None, detailed = False, extra = None, split_candidates = None):
+		"""analyze over lists, with a constant number of aligner and scorer calls for the whole batch (on the GPU: two alignment launches
+		and two launches per scorer call, of which there are at most four -- split candidates, the utterances, the words, the corrected
+		texts of every config).  extra: one dict per utterance, or None."""
+		hyps, refs = list(hyps), list(refs)
+		if len(hyps) != len(refs):
+			raise ValueError(f'analyze_batch: {len(hyps)} hypotheses for {len(refs)} references')
+		scorer = self.scorer or cer_wer
+		if split_candidates is not None:  # per utterance the (hyp, ref) candidate pair of least CER, ties by the strings
+			cands = [[(h, r) for r in split_candidates(ref) for h in split_candidates(hyp)] for hyp, ref in zip(hyps, refs)]
+			flat = [p for c in cands for p in c]
+			cers = iter(scorer([h for h, r in flat], [r for h, r in flat])[0])
+			chosen = [min((next(cers), p) for p in c)[1] for c in cands]
+			hyps, refs = [h for h, r in chosen], [r for h, r in chosen]
+		post = postprocess_fn if postprocess_fn is not None else (lambda s: s)
+		post_hyps, post_refs = [post(h) for h in hyps], [post(r) for r in refs]
+		cers, wers = scorer(post_hyps, post_refs)
+		results = [dict(ref = pr, hyp = ph, ref_orig = r, hyp_orig = h, cer = c, wer = w, **(extra[k] if extra is not None else {}))
+		           for k, (h, r, ph, pr, c, w) in enumerate(zip(hyps, refs, post_hyps, post_refs, cers, wers))]
+		if not detailed:
+			return results
+		aligned = align_strings_batch(post_hyps, post_refs, self.aligner)
+		alignments = [_word_alignment(_hyp_, _ref_, self.word_tagger, self.error_tagger, postproc = False) for _hyp_, _ref_ in aligned]
+		_add_word_cer(alignments, scorer)
+		corrected = []  # (result, config name, key stem, hyp text, ref text), scored in one call below
+		for res, (_hyp_, _ref_), word_alignment in zip(results, aligned, alignments):
+			res['alignment'] = word_alignment
+			stats = dict(ok = 0, replace = 0, delete = 0, insert = 0, delete_spaces = 0, insert_spaces = 0, total_spaces = 0)
+			for ch, cr in zip(_hyp_, _ref_):
+				stats['ok'] += cr == ch
+				stats['replace'] += cr != placeholder and cr != ch and ch != placeholder
+				stats['delete'] += cr != placeholder and cr != ch and ch == placeholder
+				stats['insert'] += cr == placeholder and ch != placeholder
+				stats['delete_spaces'] += cr == space and ch != space
+				stats['insert_spaces'] += ch == space and cr != space
+				stats['total_spaces'] += cr == space
+			res['char_stats'] = stats
+			for name, config in self.configs.items():
+				postprocess = self.postprocessors[config['postprocessor']] if 'postprocessor' in config else (lambda s: s)
+				filtered = self.filter_words(word_alignment, **config)
+				res[name] = self.compute_wordwise_metrics(filtered)
+				corrected.append((res, name, 'filtered', *self._corrected(word_alignment, filtered, postprocess, False)))
+				corrected.append((res, name, 'pseudo', *self._corrected(word_alignment, filtered, postprocess, True)))
+		cers, wers = scorer([c[3] for c in corrected], [c[4] for c in corrected])
+		for (res, name, stem, _, _), c, w in zip(corrected, cers, wers):
+			res[name]['cer_' + stem], res[name]['wer_' + stem] = c, w
+		for res in results:
+			for name, config in self.configs.items():
+				res[name].update(self.compute_vocabness_metrics(res['alignment'], self.filter_words(res['alignment'], **config)))
+		return results
+
+	def analyze(self, hyp, ref, postprocess_fn = None, detailed = False, extra = {}, split_candidates = None):
+		"""metrics.ErrorAnalyzer.analyze (metrics.py:184-232) for one pair: the batch of one."""
+		return self.analyze_batch([hyp], [ref], postprocess_fn = postprocess_fn, detailed = detailed, extra = [extra], split_candidates = split_candidates)[0]

@@ -990,3 +990,85 @@ def ctc_greedy_collapse(path, lengths, eps, space, blank_amount_to_space = 10):
 	out_lengths = torch.empty(B, dtype = torch.int64, device = dev)
 	call('convasr_ctc_greedy_collapse', ptr(path), ptr(lengths), ptr(tokens), ptr(out_lengths), B, T, int(eps), int(space), int(blank_amount_to_space), stream_ptr())
 	return tokens, out_lengths
+
+
+# ------------------------------------------------------------------------------------------------ alignment
+
+NW_WORKSPACE_CAP = 1 << 30  # bytes of direction workspace one convasr_nw_align launch may take; a resource bound, not a measurement
+
+
+def nw_align_workspace_bytes(N, La, Lb):
+	"""convasr_nw_align_workspace_bytes: N * La * ceil(Lb / 64) * 16 + N * (La + Lb) * 4."""
+	n = _lib.load().convasr_nw_align_workspace_bytes(int(N), int(La), int(Lb))
+	if n < 0:
+		raise _lib.ConvasrHipError(f'convasr_nw_align_workspace_bytes failed: {_lib.load().convasr_last_error().decode()}')
+	return n
+
+
+def _nw_launch(a, al, b, bl, scores):
+	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
+	dev = a.device
+	W = max(La + Lb, 1)
+	a_index = torch.empty(N, W, dtype = torch.int32, device = dev)
+	b_index = torch.empty(N, W, dtype = torch.int32, device = dev)
+	n_cols = torch.empty(N, dtype = torch.int32, device = dev)
+	score = torch.empty(N, dtype = torch.int32, device = dev)
+	nbytes = nw_align_workspace_bytes(N, La, Lb)
+	ws = torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)
+	if La == 0:  # (a zero-size tensor has no storage to point at; no unit is read past a length anyway)
+		a = torch.zeros(N, 1, dtype = torch.int32, device = dev)
+	if Lb == 0:
+		b = torch.zeros(N, 1, dtype = torch.int32, device = dev)
+	call('convasr_nw_align', ptr(a), ptr(al), ptr(b), ptr(bl), ptr(a_index), ptr(b_index), ptr(n_cols), ptr(score), ptr(ws), nbytes, N, La, Lb,
+	     *scores, stream_ptr())
+	return a_index[:, :La + Lb], b_index[:, :La + Lb], n_cols, score
+
+
+def nw_align(a, a_lengths, b, b_lengths, scores, workspace_cap = NW_WORKSPACE_CAP):
+	"""Semi-global Needleman-Wunsch alignment with traceback of N pairs (include/convasr_hip.h: convasr_nw_align).  a (N, La) / b (N, Lb):
+	integer ids of the hypothesis / reference units (made int32), a_lengths / b_lengths (N,); scores = (match, sub, del, ins), integers in
+	[-32768, 32768].  Returns (a_index (N, La + Lb) int32, b_index (N, La + Lb) int32, n_cols (N,) int32, score (N,) int32): per alignment
+	column the 0-based unit of a / b or -1 for a gap, -1 past column n_cols; score is the end cell's.
+
+	One launch takes N * La * ceil(Lb / 64) * 16 + N * (La + Lb) * 4 bytes of workspace.  While that is at most workspace_cap (default
+	NW_WORKSPACE_CAP = 1 GiB, a resource bound) the whole batch is one launch and nothing is copied to the host.  A larger batch is split:
+	the lengths come to the host once, the pairs are ordered by size and cut into the fewest groups that each fit under the cap at their
+	own largest lengths, one launch per group.  A single pair over the cap, or anything outside the envelope (N < 2^20, La, Lb <= 16383),
+	raises ConvasrHipError."""
+	require_cuda(a, b)
+	if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
+		raise ValueError(f'nw_align: a {tuple(a.shape)} and b {tuple(b.shape)} are not (N, La) and (N, Lb)')
+	scores = tuple(int(s) for s in scores)
+	if len(scores) != 4:
+		raise ValueError('nw_align: scores = (match, sub, del, ins)')
+	dev = a.device
+	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
+	a, b = a.to(torch.int32).contiguous(), b.to(device = dev, dtype = torch.int32).contiguous()
+	al = torch.as_tensor(a_lengths).to(device = dev, dtype = torch.int32).contiguous()
+	bl = torch.as_tensor(b_lengths).to(device = dev, dtype = torch.int32).contiguous()
+	if al.shape != (N,) or bl.shape != (N,):
+		raise ValueError(f'nw_align: lengths of shapes {tuple(al.shape)}, {tuple(bl.shape)} for a batch of {N}')
+	if nw_align_workspace_bytes(N, La, Lb) <= workspace_cap:
+		return _nw_launch(a, al, b, bl, scores)
+	need = lambda n, la, lb: n * (la * ((lb + 63) // 64) * 16 + (la + lb) * 4)
+	lens = torch.stack([al.clamp(0, La), bl.clamp(0, Lb)]).cpu().tolist()
+	order = sorted(range(N), key = lambda p: -need(1, lens[0][p], lens[1][p]))
+	groups, cur, ga, gb = [], [], 0, 0
+	for p in order:
+		na, nb = max(ga, lens[0][p]), max(gb, lens[1][p])
+		if cur and need(len(cur) + 1, na, nb) > workspace_cap:
+			groups.append((cur, ga, gb))
+			cur, na, nb = [], lens[0][p], lens[1][p]
+		cur, ga, gb = cur + [p], na, nb
+	groups.append((cur, ga, gb))
+	if need(1, groups[0][1], groups[0][2]) > workspace_cap:
+		raise _lib.ConvasrHipError(f'nw_align: one pair of {groups[0][1]} x {groups[0][2]} units needs {need(1, groups[0][1], groups[0][2])} bytes of workspace, over the cap of {workspace_cap}')
+	a_index = torch.full((N, La + Lb), -1, dtype = torch.int32, device = dev)
+	b_index = torch.full((N, La + Lb), -1, dtype = torch.int32, device = dev)
+	n_cols = torch.empty(N, dtype = torch.int32, device = dev)
+	score = torch.empty(N, dtype = torch.int32, device = dev)
+	for members, ga, gb in groups:
+		idx = torch.tensor(members, dtype = torch.int64, device = dev)
+		ai, bi, nc, sc = _nw_launch(a[idx, :ga].contiguous(), al[idx], b[idx, :gb].contiguous(), bl[idx], scores)
+		a_index[idx, :ga + gb], b_index[idx, :ga + gb], n_cols[idx], score[idx] = ai, bi, nc, sc
+	return a_index, b_index, n_cols, score

@@ -538,7 +538,7 @@ def _finite_mean(values):
 	return sum(vals) / len(vals) if vals else -1.0
 
 
-def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_space = 10, return_text = False):
+def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_space = 10, return_text = False, error_analyzer = None):
 	"""One validation set through the reference's apply_model + evaluate_model (train.py:119-300), for the first target head.
 
 	batches yields (meta, s, x, xlen, y, ylen) with the tensors on the device, as for train_epoch.  Per batch, under no_grad with the model
@@ -557,10 +557,16 @@ def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_sp
 	wer[, cer_oracle, wer_oracle]); with return_text also `hyp`, the best hypothesis of every utterance as transcribe.join would give it.
 	Everything reaches the host in one copy at the end.  The hypotheses are scored as (B, K, T) token rows, T the batch's output frames, so T
 	is bound by ops.edit_distance's envelope: a batch of more than 16,383 output frames raises ConvasrHipError.  model.training is restored on return; parameters, batch-norm statistics, torch's
-	RNG and the dropout generator's offsets are left as they were."""
+	RNG and the dropout generator's offsets are left as they were.
+
+	error_analyzer: a metrics.ErrorAnalyzer, or None.  With one, the best hypothesis and the decoded target y[:, 0] of every utterance (their
+	tokens ride in the same single copy) go through error_analyzer.analyze_batch(detailed = True) -- the reference's validation analysis
+	(train.py:239-300 there: alignment, word error tags, wordwise / filtered / pseudo / vocabness metrics per config), a constant number of
+	launches for the whole set.  The result gains `analysis`, error_analyzer.aggregate of the per-utterance dicts, and
+	utterances['analysis'], those dicts; with return_text also `ref`, the decoded targets.  Without one the result is what it was."""
 	from . import metrics
 	training, drop_offset = model.training, Fn._DropoutState.offset
-	cols, hyp_tokens, n_batches = [], [], 0
+	cols, hyp_tokens, ref_tokens, n_batches = [], [], [], 0
 	model.eval()
 	try:
 		with torch.no_grad():
@@ -580,15 +586,17 @@ def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_sp
 					inf = torch.full_like(c, float('inf'))
 					col += [torch.where(filled, c, inf).amin(dim = 1), torch.where(filled, w, inf).amin(dim = 1)]
 				cols.append(torch.stack(col))
-				if return_text:
+				if return_text or error_analyzer is not None:
 					hyp_tokens.append((tokens[:, 0], lengths[:, 0]))
+				if error_analyzer is not None:
+					ref_tokens.append((y[:, 0], ylen[:, 0].to(torch.int64)))
 				n_batches += 1
 			if not n_batches:
 				raise ValueError('evaluate_model: no batches')
 			table = torch.cat(cols, dim = 1)
 			# one device-to-host copy: the per-utterance table (fp64 bits) and, for the text, the best hypotheses' lengths and tokens
 			parts = [table.contiguous().view(torch.int64).flatten()]
-			for t, l in hyp_tokens:
+			for t, l in hyp_tokens + ref_tokens:
 				parts += [l, t.flatten()]
 			host = torch.cat(parts).cpu()
 	finally:
@@ -601,13 +609,21 @@ def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_sp
 	utt['loss'], utt['entropy'], utt['uncertainty'] = utt['loss'].float(), utt['entropy'].float(), utt['uncertainty'].float()
 	res = {k: _finite_mean(utt[k]) for k in names if k != 'uncertainty'}
 	res['utterances'] = utt
-	if return_text:
-		hyp, pos = [], table.numel()
-		for t, l in hyp_tokens:
+	if return_text or error_analyzer is not None:
+		texts, pos = [], table.numel()
+		for t, l in hyp_tokens + ref_tokens:
 			B, T = t.shape
 			lens = host[pos:pos + B].tolist()
 			toks = host[pos + B:pos + B + B * T].view(B, T).tolist()
 			pos += B + B * T
-			hyp += [tokenizer.decode([row[:n]])[0].strip() for row, n in zip(toks, lens)]
-		res['hyp'] = hyp
+			texts += [tokenizer.decode([row[:n]])[0].strip() for row, n in zip(toks, lens)]
+		hyp, ref = texts[:table.shape[1]], texts[table.shape[1]:]
+		if return_text:
+			res['hyp'] = hyp
+		if error_analyzer is not None:
+			analysis = error_analyzer.analyze_batch(hyp, ref, detailed = True)
+			res['analysis'] = error_analyzer.aggregate(analysis)
+			utt['analysis'] = analysis
+			if return_text:
+				res['ref'] = ref
 	return res

@@ -11,7 +11,7 @@
   (ctc.alignment on the GPU) -> ref segments.
 
 Out of scope: file discovery, audio decoding, the dataset, text pre/post-processing pipelines (regexes, number
-normalisation), CER / error analysis and the json / html / csv / txt writers around this body.  A TextPipeline here is the tokenizer
+normalisation) and the json / html / csv / txt writers around this body (CER and the error analysis live in metrics).  A TextPipeline here is the tokenizer
 plus identity pre/post-processing; pass the reference's own pipeline object as args.text_pipeline to get its text handling."""
 import types
 
@@ -85,7 +85,10 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 	"""One iteration of transcribe.main's loop (transcribe.py:140-200) on a collated batch: x (B, 1, T) or (B, T) waveform,
 	xlen (B,) fractions, begin / end (B,) seconds, optional targets y (B, L, S) / ylen (B, L) for --align.
 	Returns a namespace: log_probs, logits, olen, ts (per-frame time stamps), hyp_segments (per utterance: list of word segments with
-	begin / end / hyp), hyp (joined strings) and, when args.align and targets are given, alignment (B, S), ref_segments."""
+	begin / end / hyp), hyp (joined strings) and, when args.align and targets are given, alignment (B, S), ref_segments.
+	When args.align_words is set and targets are given, also ref (the decoded, postprocessed targets) and words: per utterance
+	metrics.align_words(*metrics.align_strings(hyp = hyp, ref = ref)) (transcribe.py:235), the strings of the whole batch aligned in two
+	GPU launches; words is None otherwise."""
 	device = torch.device(args.device)
 	x = x.squeeze(1) if x.ndim == 3 else x
 	log_probs, logits, olen = model(x.to(device), xlen.to(device))
@@ -95,7 +98,7 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 	tokenizer = text_pipeline.tokenizer
 	hyp_segments = [alternatives[0] for alternatives in generator.generate(tokenizer = tokenizer, log_probs = log_probs, begin = begin, end = end, output_lengths = olen, time_stamps = ts, segment_text_key = 'hyp', segment_extra_info = segment_extra_info)]
 	hyp_segments = [map_text(text_pipeline.postprocess, hyp = hyp) for hyp in hyp_segments]
-	out = types.SimpleNamespace(log_probs = log_probs, logits = logits, olen = olen, ts = ts, hyp_segments = hyp_segments, hyp = [join(hyp = h) for h in hyp_segments], alignment = None, ref_segments = None)
+	out = types.SimpleNamespace(log_probs = log_probs, logits = logits, olen = olen, ts = ts, hyp_segments = hyp_segments, hyp = [join(hyp = h) for h in hyp_segments], alignment = None, ref_segments = None, ref = None, words = None)
 	if getattr(args, 'align', False) and y is not None and y.numel() > 0:
 		y, ylen = y.to(device), ylen.to(device)
 		out.alignment = ctc.alignment_bct(log_probs, y[:, 0, :], olen, ylen[:, 0], blank = tokenizer.eps_id)
@@ -104,4 +107,9 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 		ref_generator = generator if isinstance(generator, GreedyCTCGenerator) else GreedyCTCGenerator()  # one-hot targets: the argmax collapse gives back y; a beam search over 0 / 1 "log-probs" would not
 		ref_segments = [alternatives[0] for alternatives in ref_generator.generate(tokenizer = tokenizer, log_probs = one_hot, begin = begin, end = end, output_lengths = ylen[:, 0], time_stamps = aligned_ts, segment_text_key = 'ref', segment_extra_info = segment_extra_info)]
 		out.ref_segments = [map_text(text_pipeline.postprocess, ref = ref) for ref in ref_segments]
+	if getattr(args, 'align_words', False) and y is not None and y.numel() > 0:
+		from . import metrics
+		out.ref = [text_pipeline.postprocess(tokenizer.decode([row[:n]])[0].strip()) for row, n in zip(y[:, 0].tolist(), ylen[:, 0].tolist())]
+		aligned = metrics.align_strings_batch(out.hyp, out.ref)
+		out.words = [metrics.align_words(_hyp_, _ref_) for _hyp_, _ref_ in aligned]
 	return out

@@ -636,6 +636,36 @@ int convasr_edit_distance(const int64_t* hyp, const int64_t* hyp_lengths, const 
 int convasr_ctc_greedy_collapse(const int64_t* path, const int64_t* lengths, int64_t* tokens, int64_t* out_lengths, int B, int T,
                                 int eps, int space, int blank_amount_to_space, void* stream);
 
+/* ---- Alignment: metrics.py:365-407 (align_strings) and its aligner (metrics.py:447-645), the step every error analysis of the reference
+ * starts with (ErrorAnalyzer.analyze, transcribe.py --align-words) ------------------------------------------------------------------------ */
+
+/* Semi-global Needleman-Wunsch alignment with traceback of N pairs of integer sequences, one launch.
+ * a (N, La) int32: the hypothesis units of every pair, a_lengths (N,) int32; b (N, Lb) int32: the reference units, b_lengths (N,) int32.
+ * Only units below a length are read; the lengths are clamped to [0, La] / [0, Lb] on the device.  Two units match when their ids are equal.
+ * Per pair, with la / lb the lengths and four integer scores match, sub, del, ins:
+ *   Matrix.  M has (la + 1) x (lb + 1) cells.  M[i][0] = M[0][j] = 0 (leading units of either side cost nothing: the semi-global part).
+ *     M[i][j] = max(M[i-1][j-1] + (a[i-1] == b[j-1] ? match : sub), M[i-1][j] + del, M[i][j-1] + ins).
+ *   End cell.  If la < lb: i = la and j = the LOWEST column that maximises M[la][j] over 0..lb; the units b[j:] are emitted against gaps.
+ *     Otherwise: j = lb and i = the lowest row that maximises M[i][lb] over 0..la; the units a[i:] are emitted against gaps.
+ *   Walk back from the end cell while i > 0 or j > 0:
+ *     1. if i == 0 or j == 0, the remaining prefix of the other sequence is emitted against gaps and the walk stops;
+ *     2. otherwise, if M[i][j] == M[i][j-1] + ins: the column (gap, b[j-1]) and j -= 1;
+ *     3. else if M[i][j] == M[i-1][j] + del: the column (a[i-1], gap) and i -= 1;
+ *     4. else the column (a[i-1], b[j-1]) and both decrease.
+ *     The priority ins, del, diagonal makes the alignment unique.
+ * Output per pair, rows of La + Lb entries: a_index / b_index (N, La + Lb) int32 = per alignment column, in forward order, the 0-based
+ * unit of a / of b, or -1 for a gap; -1 past the last column.  n_cols (N,) int32 = the number of columns (max(la, lb) <= n_cols <= la + lb).
+ * score (N,) int32 = M at the end cell.  Empty sequences are legal: an empty side gives gaps only, two empty sides no column.
+ * One 64-thread workgroup per pair.  workspace: at least convasr_nw_align_workspace_bytes(N, La, Lb) =
+ * N * La * ceil(Lb / 64) * 16 + N * (La + Lb) * 4 bytes (2 direction bits per cell, then the walked columns), 16-byte aligned,
+ * uninitialised; no memset or copy: the call can be captured into a graph.  The query returns -1 outside the envelope of N, La, Lb.
+ * Envelope, checked before any launch: 1 <= N < 2^20, 0 <= La, Lb <= CONVASR_METRIC_MAX_LEN, every score in [-32768, 32768] (so that no
+ * cell leaves int32), no NULL pointer, workspace_bytes at least the query's answer; outside it CONVASR_EINVAL. */
+int64_t convasr_nw_align_workspace_bytes(int N, int La, int Lb);
+int convasr_nw_align(const int32_t* a, const int32_t* a_lengths, const int32_t* b, const int32_t* b_lengths, int32_t* a_index,
+                     int32_t* b_index, int32_t* n_cols, int32_t* score, void* workspace, int64_t workspace_bytes, int N, int La, int Lb,
+                     int match, int sub, int del, int ins, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
