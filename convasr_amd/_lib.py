@@ -111,7 +111,26 @@ _SIGNATURES = dict(
 	convasr_ctc_greedy_collapse = (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_nw_align_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
 	convasr_nw_align = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_sliding_max_out_len = (c_i64, [c_i64, c_int]),
+	convasr_sliding_max_tile = (c_int, [c_int]),
+	convasr_sliding_max = (c_int, [c_p, c_p, c_int, c_i64, c_int, c_int, c_p]),
+	convasr_kth_value_workspace_bytes = (c_i64, [c_int]),
+	convasr_kth_value = (c_int, [c_p, c_p, c_p, c_i64, c_int, c_i64, c_i64, c_p]),
+	convasr_scan_tile = (c_int, []),
+	convasr_sign_prefix_sum_workspace_bytes = (c_i64, [c_i64]),
+	convasr_sign_prefix_sum = (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p]),
+	convasr_select_speaker_out_len = (c_i64, [c_i64, c_int, c_int, c_int]),
+	convasr_select_speaker_workspace_bytes = (c_i64, [c_i64, c_int, c_int, c_int]),
+	convasr_select_speaker = (c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_f32, c_i64, c_p]),
+	convasr_rle1d_workspace_bytes = (c_i64, [c_i64]),
+	convasr_rle1d_count_offset = (c_i64, [c_i64]),
+	convasr_rle1d_count = (c_int, [c_p, c_int, c_int, c_i64, c_p, c_i64, c_p]),
+	convasr_rle1d_write = (c_int, [c_p, c_int, c_int, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p]),
+	convasr_speaker_error_counts_workspace_bytes = (c_i64, [c_i64]),
+	convasr_speaker_error_counts = (c_int, [c_p, c_p, ctypes.POINTER(ctypes.c_int32), c_int, c_i64, c_p, c_p, c_i64, c_p]),
 )
+SLIDE_ABS, SLIDE_NEG = 1, 2  # include/convasr_hip.h: CONVASR_SLIDE_ABS / CONVASR_SLIDE_NEG
+DIAR_MAX_LEN, DIAR_MAX_KERNEL, RLE_MAX_LEN, SPEAKER_MAX_PERMS = 1 << 28, 16384, 1 << 30, 8  # CONVASR_DIAR_MAX_LEN, ..._MAX_KERNEL, CONVASR_RLE_MAX_LEN, CONVASR_SPEAKER_MAX_PERMS
 
 _lib = None
 

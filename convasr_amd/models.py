@@ -49,6 +49,12 @@ def entropy(log_probs, lengths = None, dim = 1, eps = 1e-9, sum = True, keepdim 
 	return ops.entropy(log_probs, lengths, eps)
 
 
+def rle1d(tensor):
+	"""models.py:777-785: run-length encoding of a 1-D tensor -> (starts, lengths, values), on the device (ops.rle1d: boundary flags, a
+	multi-workgroup scan, compaction; the run count comes to the host once).  A CPU tensor raises ConvasrHipError: there is no host path."""
+	return ops.rle1d(tensor)
+
+
 def unpad(x, lens):
 	return [e[..., :l] for e, l in zip(x, lens)]
 

@@ -1072,3 +1072,121 @@ def nw_align(a, a_lengths, b, b_lengths, scores, workspace_cap = NW_WORKSPACE_CA
 		ai, bi, nc, sc = _nw_launch(a[idx, :ga].contiguous(), al[idx], b[idx, :gb].contiguous(), bl[idx], scores)
 		a_index[idx, :ga + gb], b_index[idx, :ga + gb], n_cols[idx], score[idx] = ai, bi, nc, sc
 	return a_index, b_index, n_cols, score
+
+
+# ------------------------------------------------------------------------------------------------ diarization
+
+def _query(name, *args):
+	n = getattr(_lib.load(), name)(*args)
+	if n < 0:
+		raise _lib.ConvasrHipError(f'{name} failed: {_lib.load().convasr_last_error().decode()}')
+	return n
+
+
+def sliding_max_tile(kernel_size):
+	"""Outputs one workgroup of convasr_sliding_max produces at this window (tests straddle it)."""
+	return _query('convasr_sliding_max_tile', int(kernel_size))
+
+
+def scan_tile():
+	"""Elements one workgroup of the prefix sums (sign_prefix_sum, rle1d) scans (tests straddle it)."""
+	return _query('convasr_scan_tile')
+
+
+def sliding_max(x, kernel_size, absolute = False, minimum = False):
+	"""F.max_pool1d(x.unsqueeze(1), K, stride = 1, padding = K // 2).squeeze(1) of a (C, L) fp32 device tensor, at a cost that does not depend
+	on K (include/convasr_hip.h: convasr_sliding_max).  absolute: of |x|; minimum: the sliding minimum with +inf padding, -max_pool1d(-x).
+	Returns (C, L + 2 * (K // 2) - K + 1) fp32.  1 <= K <= 16384, 1 <= L <= 2^28; finite values are assumed, not checked."""
+	require_cuda(x)
+	if x.ndim != 2 or x.dtype != torch.float32:
+		raise ValueError(f'sliding_max: x must be a (C, L) float32 tensor, got {tuple(x.shape)} {x.dtype}')
+	C, L = x.shape
+	x = x.contiguous()
+	out = torch.empty(C, max(_query('convasr_sliding_max_out_len', L, int(kernel_size)), 0), dtype = torch.float32, device = x.device)
+	call('convasr_sliding_max', ptr(x), ptr(out), C, L, int(kernel_size), (_lib.SLIDE_ABS if absolute else 0) | (_lib.SLIDE_NEG if minimum else 0), stream_ptr())
+	return out
+
+
+def kth_value(x, k):
+	"""x.kthvalue(k, dim = -1).values of a (C, L) fp32 device tensor of NON-NEGATIVE values (not checked), k 1-based: a radix select over the
+	bit patterns (convasr_kth_value), exact.  Returns (C,) fp32."""
+	require_cuda(x)
+	if x.ndim != 2 or x.dtype != torch.float32:
+		raise ValueError(f'kth_value: x must be a (C, L) float32 tensor, got {tuple(x.shape)} {x.dtype}')
+	C, L = x.shape
+	x = x.contiguous()
+	nbytes = _query('convasr_kth_value_workspace_bytes', C)
+	ws = workspace(nbytes, x.device, 'diar')
+	out = torch.empty(C, dtype = torch.float32, device = x.device)
+	call('convasr_kth_value', ptr(x), ptr(out), ptr(ws), ws.numel(), C, L, int(k), stream_ptr())
+	return out
+
+
+def sign_prefix_sum(d):
+	"""(d[0] - d[1]).sign().cumsum(0) as int32 for a (2, L) fp32 device tensor (convasr_sign_prefix_sum; a multi-workgroup scan)."""
+	require_cuda(d)
+	if d.ndim != 2 or d.shape[0] != 2 or d.dtype != torch.float32:
+		raise ValueError(f'sign_prefix_sum: d must be a (2, L) float32 tensor, got {tuple(d.shape)} {d.dtype}')
+	L = d.shape[1]
+	d = d.contiguous()
+	ws = workspace(_query('convasr_sign_prefix_sum_workspace_bytes', L), d.device, 'diar')
+	out = torch.empty(L, dtype = torch.int32, device = d.device)
+	call('convasr_sign_prefix_sum', ptr(d), ptr(out), ptr(ws), ws.numel(), L, stream_ptr())
+	return out
+
+
+def select_speaker(signal, kernel_size_smooth_silence, kernel_size_smooth_signal, kernel_size_smooth_speaker, silence_absolute_threshold, silence_relative_threshold, eps, k):
+	"""convasr_select_speaker on a (2, N) fp32 device tensor; k = the 1-based rank of the normalisation percentile.  Returns
+	(speaker_id (L,) fp32, mask (3, L) bool)."""
+	require_cuda(signal)
+	N = signal.shape[1]
+	ks = (int(kernel_size_smooth_silence), int(kernel_size_smooth_signal), int(kernel_size_smooth_speaker))
+	L = _query('convasr_select_speaker_out_len', N, *ks)
+	ws = workspace(_query('convasr_select_speaker_workspace_bytes', N, *ks), signal.device, 'diar')
+	speaker_id = torch.empty(L, dtype = torch.float32, device = signal.device)
+	mask = torch.empty(3, L, dtype = torch.bool, device = signal.device)
+	call('convasr_select_speaker', ptr(signal), ptr(speaker_id), ptr(mask), ptr(ws), ws.numel(), N, *ks, float(silence_absolute_threshold), float(silence_relative_threshold),
+	     float(eps), int(k), stream_ptr())
+	return speaker_id, mask
+
+
+def rle1d(x):
+	"""Run-length encoding of a 1-D device tensor (convasr_rle1d_count / convasr_rle1d_write): (starts int64, lengths int64, values of x's
+	dtype).  bool, integer and float32 inputs.  The number of runs decides the size of the result, so it is read back to the host ONCE between
+	the two calls (4 bytes, one synchronisation)."""
+	require_cuda(x)
+	if x.ndim != 1 or x.numel() < 1:
+		raise ValueError(f'rle1d: a 1-D tensor with at least one element expected, got shape {tuple(x.shape)}')
+	if x.dtype != torch.float32 and (x.dtype.is_floating_point or x.dtype.is_complex):
+		raise ValueError(f'rle1d: bool, integer and float32 tensors only, got {x.dtype}')
+	n = x.numel()
+	x = x.contiguous()
+	kind = (x.element_size(), int(x.dtype == torch.float32))
+	ws = workspace(_query('convasr_rle1d_workspace_bytes', n), x.device, 'rle')
+	call('convasr_rle1d_count', ptr(x), *kind, n, ptr(ws), ws.numel(), stream_ptr())
+	at = _query('convasr_rle1d_count_offset', n)
+	runs = int(ws[at:at + 4].view(torch.int32).item()) + 1
+	starts = torch.empty(runs, dtype = torch.int64, device = x.device)
+	lengths = torch.empty(runs, dtype = torch.int64, device = x.device)
+	values = torch.empty(runs, dtype = x.dtype, device = x.device)
+	call('convasr_rle1d_write', ptr(x), *kind, n, ptr(ws), ws.numel(), runs, ptr(starts), ptr(lengths), ptr(values), stream_ptr())
+	return starts, lengths, values
+
+
+def speaker_error_counts(ref_mask, hyp_mask, perms):
+	"""convasr_speaker_error_counts: ref_mask, hyp_mask (3, n) bool device tensors, perms a list of 3-element mappings.  Returns a
+	(len(perms), 7) int64 device tensor: mismatches where exactly one reference speaker talks, mismatches anywhere, confusion, false alarm,
+	miss, positions where exactly one reference speaker talks, positions where a reference speaker talks."""
+	require_cuda(ref_mask, hyp_mask)
+	if ref_mask.shape != hyp_mask.shape or ref_mask.ndim != 2 or ref_mask.shape[0] != 3 or ref_mask.dtype != torch.bool or hyp_mask.dtype != torch.bool:
+		raise ValueError(f'speaker_error_counts: two (3, n) bool masks expected, got {tuple(ref_mask.shape)} {ref_mask.dtype} and {tuple(hyp_mask.shape)} {hyp_mask.dtype}')
+	perms = [[int(v) for v in p] for p in perms]
+	if not perms or any(len(p) != 3 for p in perms):
+		raise ValueError('speaker_error_counts: mappings of 3 rows each expected')
+	n = ref_mask.shape[1]
+	ref_mask, hyp_mask = ref_mask.contiguous(), hyp_mask.contiguous()
+	flat = (ctypes.c_int32 * (3 * len(perms)))(*[v for p in perms for v in p])
+	ws = workspace(_query('convasr_speaker_error_counts_workspace_bytes', n), ref_mask.device, 'diar')
+	counts = torch.empty(len(perms), 7, dtype = torch.int64, device = ref_mask.device)
+	call('convasr_speaker_error_counts', ptr(ref_mask), ptr(hyp_mask), flat, len(perms), n, ptr(counts), ptr(ws), ws.numel(), stream_ptr())
+	return counts

@@ -666,6 +666,90 @@ int convasr_nw_align(const int32_t* a, const int32_t* a_lengths, const int32_t* 
                      int32_t* b_index, int32_t* n_cols, int32_t* score, void* workspace, int64_t workspace_bytes, int N, int La, int Lb,
                      int match, int sub, int del, int ins, void* stream);
 
+/* ---- Two-channel diarization: diarization.py:58-99 (select_speaker, a channel-energy diarizer with a primitive VAD), models.py:777-785
+ * (rle1d, which turns its masks into segments), diarization.py:175-201 (the counts behind speaker_error).  Every result is exact: maxima,
+ * comparisons, integer sums, and one IEEE add and divide per channel and position. --------------------------------------------------------- */
+
+#define CONVASR_DIAR_MAX_LEN 268435456LL /* samples per channel: 2^28, 4.6 hours at 16 kHz */
+#define CONVASR_DIAR_MAX_KERNEL 16384
+#define CONVASR_RLE_MAX_LEN 1073741824LL /* 2^30 elements */
+#define CONVASR_SPEAKER_MAX_PERMS 8
+enum { CONVASR_SLIDE_ABS = 1, CONVASR_SLIDE_NEG = 2 };
+
+/* Sliding maximum of C rows, stride 1, window K, -inf padding of K / 2 (integer division) on both sides: F.max_pool1d(x.unsqueeze(1), K,
+ * stride = 1, padding = K // 2).  in (C, Lin) fp32, out (C, Lout) fp32 with Lout = Lin + 2 * (K / 2) - K + 1 (Lin for an odd K, Lin + 1 for
+ * an even one; the out_len query returns it, -1 outside the envelope): out[c][i] = max over j in [i - K / 2, i - K / 2 + K - 1] within
+ * [0, Lin) of f(in[c][j]).  flags: CONVASR_SLIDE_ABS: f(x) = |x|; CONVASR_SLIDE_NEG: f(x) = -x and the result is negated again, i.e. a
+ * sliding MINIMUM with +inf padding (the erosion -max_pool1d(-x)); both: the minimum of |x|.  The cost does not depend on K (van Herk /
+ * Gil-Werman, one launch).  The tile query returns how many outputs one workgroup produces for a window K (7,936 - K + 1 up to K = 2,048,
+ * 31,744 - K + 1 above), for tests that straddle it.  Samples are assumed finite (not checked; a NaN is dropped by the maximum).
+ * Envelope, checked before any launch: 1 <= C <= 65535, 1 <= Lin <= CONVASR_DIAR_MAX_LEN, 1 <= K <= CONVASR_DIAR_MAX_KERNEL, known flags,
+ * no NULL pointer; outside it CONVASR_EINVAL. */
+int64_t convasr_sliding_max_out_len(int64_t Lin, int K);
+int convasr_sliding_max_tile(int K);
+int convasr_sliding_max(const float* in, float* out, int C, int64_t Lin, int K, int flags, void* stream);
+
+/* out[c] = the k-th smallest (k 1-based, as torch.kthvalue) of the L values of row c of x (C, L) fp32, every value >= +0 (not checked: the
+ * bit patterns are ordered as unsigned integers).  A radix select: three histogram passes over x, no sort.  workspace: at least
+ * convasr_kth_value_workspace_bytes(C) bytes, 16-byte aligned, uninitialised.  Envelope: 1 <= C <= 65535, 1 <= L <= CONVASR_DIAR_MAX_LEN + 1,
+ * 1 <= k <= L, no NULL pointer; outside it CONVASR_EINVAL (the query returns -1). */
+int64_t convasr_kth_value_workspace_bytes(int C);
+int convasr_kth_value(const float* x, float* out, void* workspace, int64_t workspace_bytes, int C, int64_t L, int64_t k, void* stream);
+
+/* prefix[i] = sum over j <= i of s[j], s[j] = +1 / 0 / -1 as d[0][j] is above / equal to / below d[1][j]; d (2, L) fp32, prefix (L,) int32.
+ * Three launches (tile sums, their scan, tile scans); convasr_scan_tile returns the elements one workgroup scans (2,048), here and in the
+ * run-length encoding below, for tests that straddle it.  Envelope: 1 <= L <= CONVASR_DIAR_MAX_LEN + 1, a workspace of at least the query's
+ * bytes, no NULL pointer; outside it CONVASR_EINVAL (the query returns -1). */
+int convasr_scan_tile(void);
+int64_t convasr_sign_prefix_sum_workspace_bytes(int64_t L);
+int convasr_sign_prefix_sum(const float* d, int32_t* prefix, void* workspace, int64_t workspace_bytes, int64_t L, void* stream);
+
+/* select_speaker.  signal (2, N) fp32, contiguous, finite (not checked).  With Ksig / Ksil / Kspk = kernel_size_smooth_signal / _silence /
+ * _speaker and len(L, K) = L + 2 * (K / 2) - K + 1:
+ *   smoothed (2, L1) = sliding maximum of |signal|, window Ksig, L1 = len(N, Ksig);
+ *   eroded (2, Le) = sliding minimum, window Ksil, of the sliding maximum, window Ksil, of |signal|; Le = len(len(N, Ksil), Ksil);
+ *   kth[c] = the k-th smallest of smoothed[c] (the caller computes k = int(normalization_percentile * L1) in double);
+ *   silence[c][i] = eroded[c][i] < silence_absolute_threshold or eroded[c][i] / (eps + kth[c]) < silence_relative_threshold, in fp32, the
+ *     add and the divide correctly rounded;
+ *   s[j] = the sign of smoothed[0][j] - smoothed[1][j]; b[i] = the sign of the zero-padded box sum of s over window Kspk, i < Ls = len(L1, Kspk);
+ *     then every b[i] == 0 whose neighbours (0 outside [0, Ls)) are +1 and -1 in either order becomes +1 (all at once, on the unrepaired b);
+ *   L = min(Le, Ls) (the out_len query returns it).
+ * speaker_id (L,) fp32 = 0 where both channels are silent or b == 0, else 1 for b == +1 and 2 for b == -1.  mask (3, L) bytes of 0 / 1:
+ * row 0 = both channels silent, row 1 = not silence[0] and b == +1, row 2 = not silence[1] and b == -1.
+ * workspace: at least convasr_select_speaker_workspace_bytes(N, Ksil, Ksig, Kspk) bytes (about 28 N), 16-byte aligned, uninitialised; no
+ * memset or copy: the call can be captured into a graph.  14 launches, none of whose cost depends on a kernel size.
+ * Envelope, checked before any launch: 1 <= N <= CONVASR_DIAR_MAX_LEN, every kernel size in [1, CONVASR_DIAR_MAX_KERNEL], 1 <= k <= L1, no
+ * NULL pointer, workspace_bytes at least the query's answer; outside it CONVASR_EINVAL (the queries return -1). */
+int64_t convasr_select_speaker_out_len(int64_t N, int kernel_size_smooth_silence, int kernel_size_smooth_signal, int kernel_size_smooth_speaker);
+int64_t convasr_select_speaker_workspace_bytes(int64_t N, int kernel_size_smooth_silence, int kernel_size_smooth_signal, int kernel_size_smooth_speaker);
+int convasr_select_speaker(const float* signal, float* speaker_id, uint8_t* mask, void* workspace, int64_t workspace_bytes, int64_t N,
+                           int kernel_size_smooth_silence, int kernel_size_smooth_signal, int kernel_size_smooth_speaker,
+                           float silence_absolute_threshold, float silence_relative_threshold, float eps, int64_t k, void* stream);
+
+/* Run-length encoding of n elements (models.rle1d) in two calls around one host read, because the output size depends on the data.
+ * Elements: integers of 1, 2, 4 or 8 bytes compared bit for bit (bool included), or fp32 compared as floats (is_float = 1, elem_bytes = 4).
+ * convasr_rle1d_count leaves, as an int32 at byte convasr_rle1d_count_offset(n) of the workspace, the number of i >= 1 with x[i] != x[i-1];
+ * runs = that number + 1.  convasr_rle1d_write, given the same workspace untouched and `runs`, writes starts (runs,) int64, lengths (runs,)
+ * int64 and values (runs,) of the element type.  Envelope: 1 <= n <= CONVASR_RLE_MAX_LEN, a listed element type, 1 <= runs <= n, a workspace
+ * of at least convasr_rle1d_workspace_bytes(n), no NULL pointer; outside it CONVASR_EINVAL (the queries return -1). */
+int64_t convasr_rle1d_workspace_bytes(int64_t n);
+int64_t convasr_rle1d_count_offset(int64_t n);
+int convasr_rle1d_count(const void* x, int elem_bytes, int is_float, int64_t n, void* workspace, int64_t workspace_bytes, void* stream);
+int convasr_rle1d_write(const void* x, int elem_bytes, int is_float, int64_t n, const void* workspace, int64_t workspace_bytes, int64_t runs,
+                        int64_t* starts, int64_t* lengths, void* values, void* stream);
+
+/* The counts behind speaker_error for n_perms mappings at once.  ref_mask, hyp_mask (3, n) bytes of 0 / 1 on the device (rows 1 and 2: where
+ * speakers 1 and 2 talk); perms: n_perms x 3 int32 ON THE HOST, mapping p reading the hypothesis rows perms[3p + 1] and perms[3p + 2] as
+ * speakers 1 and 2.  counts (n_perms, 7) int64 on the device, per mapping with r1, r2 the reference rows and h1, h2 the mapped hypothesis rows:
+ *   0: positions with (r1 != h1 or r2 != h2) and r1 != r2;   1: positions with r1 != h1 or r2 != h2;
+ *   2: confusion (h1 and r2 and not r1) or (h2 and r1 and not r2);   3: false alarm (h1 or h2) and not r1 and not r2;
+ *   4: miss, not h1 and not h2 and (r1 or r2);   5: positions with r1 != r2;   6: total, r1 or r2.
+ * One pass over both masks and a finishing launch.  Envelope: 1 <= n <= CONVASR_RLE_MAX_LEN, 1 <= n_perms <= CONVASR_SPEAKER_MAX_PERMS, rows
+ * in [0, 2], a workspace of at least the query's bytes, 8-byte aligned, no NULL pointer; outside it CONVASR_EINVAL (the query returns -1). */
+int64_t convasr_speaker_error_counts_workspace_bytes(int64_t n);
+int convasr_speaker_error_counts(const uint8_t* ref_mask, const uint8_t* hyp_mask, const int32_t* perms, int n_perms, int64_t n, int64_t* counts,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
