@@ -97,6 +97,11 @@ _SIGNATURES = dict(
 	convasr_collate_pad = (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_i64, c_p]),
 	convasr_ctc_alignment_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
 	convasr_ctc_alignment = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_ctc_alignment_long_states_per_block = (c_int, []),
+	convasr_ctc_alignment_long_chunk_frames = (c_int, []),
+	convasr_ctc_alignment_long_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
+	convasr_ctc_alignment_long = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_ctc_alignment_long_parts = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_ctc_beam_search_workspace_bytes = (c_i64, [c_int] * 6),
 	convasr_ctc_beam_search = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int, c_p]),
 	convasr_ctc_beam_search_lm_workspace_bytes = (c_i64, [c_int] * 6),

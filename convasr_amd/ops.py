@@ -860,6 +860,39 @@ def ctc_alignment(log_probs_btc, targets, input_lengths, target_lengths, blank):
 	return out
 
 
+ALIGN_LONG_WORKSPACE_CAP = 16 << 30  # bytes of workspace one convasr_ctc_alignment_long call may take; a resource bound like NW_WORKSPACE_CAP, not a measurement
+
+
+def ctc_alignment_long_tiles():
+	"""(states per block, default frames per chunk) of convasr_ctc_alignment_long's tiles (tests straddle them)."""
+	lib = _lib.load()
+	return lib.convasr_ctc_alignment_long_states_per_block(), lib.convasr_ctc_alignment_long_chunk_frames()
+
+
+def ctc_alignment_long(log_probs_btc, targets, input_lengths, target_lengths, blank, chunk_frames = 0, workspace_cap = ALIGN_LONG_WORKSPACE_CAP):
+	"""ctc_alignment for whole recordings (include/convasr_hip.h: convasr_ctc_alignment_long): up to 131,071 labels and 2^20 frames, the same
+	result as ctc_alignment where that takes the targets.  chunk_frames: 0 = the default tile length, 16 .. 4096 forces it.  The workspace
+	(about 4.9 GB for an hour) is allocated for this call and goes back to the allocator; a need above workspace_cap raises ConvasrHipError."""
+	B, T, C = log_probs_btc.shape
+	dev = log_probs_btc.device
+	require_cuda(log_probs_btc)
+	assert log_probs_btc.is_contiguous() and log_probs_btc.dtype == torch.float32
+	targets = targets.to(device = dev, dtype = torch.int64).contiguous()
+	il = input_lengths.to(device = dev, dtype = torch.int64).contiguous()
+	tl = target_lengths.to(device = dev, dtype = torch.int64).contiguous()
+	S_max = targets.shape[1]
+	lib = _lib.load()
+	nbytes = lib.convasr_ctc_alignment_long_workspace_bytes(B, T, S_max)
+	if nbytes < 0:
+		raise _lib.ConvasrHipError(f'convasr_ctc_alignment_long_workspace_bytes failed: {lib.convasr_last_error().decode()}')
+	if nbytes > workspace_cap:
+		raise _lib.ConvasrHipError(f'ctc_alignment_long: {nbytes} bytes of workspace needed for B {B}, T {T}, S_max {S_max}, above the cap of {workspace_cap}')
+	out = torch.empty(B, S_max, dtype = torch.int64, device = dev)
+	ws = torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)  # (not ops.workspace: that cache keeps its buffers for good)
+	call('convasr_ctc_alignment_long', ptr(log_probs_btc), ptr(targets), ptr(il), ptr(tl), ptr(out), ptr(ws), nbytes, B, T, C, S_max, int(blank), int(chunk_frames), stream_ptr())
+	return out
+
+
 def _beam_route(name, args, wide):
 	"""(entry point, workspace bytes): the LDS kernel whenever its workspace query accepts the arguments (wide None), otherwise -- or with
 	wide True -- the wide one (beam state in the workspace, beam_width <= 8192); wide False keeps the LDS kernel.  Raises ConvasrHipError

@@ -101,7 +101,8 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 	out = types.SimpleNamespace(log_probs = log_probs, logits = logits, olen = olen, ts = ts, hyp_segments = hyp_segments, hyp = [join(hyp = h) for h in hyp_segments], alignment = None, ref_segments = None, ref = None, words = None)
 	if getattr(args, 'align', False) and y is not None and y.numel() > 0:
 		y, ylen = y.to(device), ylen.to(device)
-		out.alignment = ctc.alignment_bct(log_probs, y[:, 0, :], olen, ylen[:, 0], blank = tokenizer.eps_id)
+		align = ctc.alignment_long_bct if y.shape[-1] > 8191 else ctc.alignment_bct  # (a whole recording against its transcript: past ctc.alignment's 8,191 labels)
+		out.alignment = align(log_probs, y[:, 0, :], olen, ylen[:, 0], blank = tokenizer.eps_id)
 		aligned_ts = ts.gather(1, out.alignment)
 		one_hot = torch.nn.functional.one_hot(y[:, 0, :], num_classes = log_probs.shape[1]).permute(0, 2, 1).to(torch.float32)
 		ref_generator = generator if isinstance(generator, GreedyCTCGenerator) else GreedyCTCGenerator()  # one-hot targets: the argmax collapse gives back y; a beam search over 0 / 1 "log-probs" would not

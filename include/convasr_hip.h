@@ -500,9 +500,31 @@ int64_t convasr_ctc_alignment_workspace_bytes(int B, int T, int S_max);
  * frame the best path spends in each label's state, 0 for padded labels.  Forward variable = the reference's sum recursion
  * with finfo.min as log-zero over all T frames, back-pointer = first maximum of (stay, s-1, s-2), end state chosen from the
  * column at T-1, walk started at input_lengths[b]-1.  S_max <= 8191 (a recording of ten minutes aligned to its transcript in one call,
- * transcribe.py:176 without segmentation); longer targets return CONVASR_EUNSUPPORTED. */
+ * transcribe.py:176 without segmentation); longer targets return CONVASR_EUNSUPPORTED here: convasr_ctc_alignment_long below takes them. */
 int convasr_ctc_alignment(const float* log_probs, const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths,
                           int64_t* alignment, void* workspace, int B, int T, int C, int S_max, int blank, void* stream);
+
+/* The same alignment -- arguments, quirks and result, bit for bit -- for whole recordings, at every target length: the lattice is cut
+ * into tiles of convasr_ctc_alignment_long_states_per_block() states x chunk frames, one wave per tile, one plain launch per
+ * anti-diagonal of tiles (ceil(T / chunk) + ceil((2 S_max + 1) / states_per_block) - 1 launches at most; tiles in which no state can be
+ * reached yet, s > 2t + 1, are not launched), then one launch that walks the path back through windows of back-pointers staged in LDS.
+ * Nothing waits inside a launch.  chunk_frames: 0 = convasr_ctc_alignment_long_chunk_frames() (256), or 16 .. 4096 to force the chunk
+ * length (tests and tuning; the result does not depend on it).  workspace: at least convasr_ctc_alignment_long_workspace_bytes bytes,
+ * 16-byte aligned, uninitialised: back-pointers [B][T][ceil((2 S_max + 1) / 16)] dwords (2 bits per state), the column carried between
+ * chunks [B][blocks][states_per_block] fp32 and the two last states of every block at every frame [B][blocks][T][2] fp32 -- an hour
+ * (180,000 frames, 48,000 labels) takes about 4.9 GB.  Envelope: 1 <= S_max <= 131071, 1 <= T <= 2^20, 1 <= B <= 65535; outside it
+ * CONVASR_EUNSUPPORTED (the query returns -1); any other bad argument CONVASR_EINVAL. */
+int convasr_ctc_alignment_long_states_per_block(void);
+int convasr_ctc_alignment_long_chunk_frames(void);
+int64_t convasr_ctc_alignment_long_workspace_bytes(int B, int T, int S_max);
+int convasr_ctc_alignment_long(const float* log_probs, const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths,
+                               int64_t* alignment, void* workspace, int64_t workspace_bytes, int B, int T, int C, int S_max, int blank,
+                               int chunk_frames, void* stream);
+/* The same in parts, for measurements that time the two apart: parts = 1 the sweep, 2 the walk over a workspace that a sweep with the same
+ * arguments filled, 3 both (= the call above). */
+int convasr_ctc_alignment_long_parts(const float* log_probs, const int64_t* targets, const int64_t* input_lengths, const int64_t* target_lengths,
+                                     int64_t* alignment, void* workspace, int64_t workspace_bytes, int B, int T, int C, int S_max, int blank,
+                                     int chunk_frames, int parts, void* stream);
 
 /* The padding half of AudioTextDataset.collate_fn (datasets.py:320-330) on the device: B ragged samples of `rows` rows each,
  * delivered as one packed buffer (sample b starts at element offsets[b], its rows are lengths[b] long and contiguous), become the
