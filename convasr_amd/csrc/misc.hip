@@ -275,20 +275,29 @@ extern "C" int convasr_weighted_mean_entropy(const float* log_probs, const int64
 	return 0;
 }
 
+// torch.argmax's total order on (value, index) pairs: NaN ranks above every number, and among equals -- two NaNs count as equal -- the
+// lower index wins.  The lane-local scan and the butterfly both go through this one comparison, so after the last exchange all 64 lanes
+// hold the same pair.  An empty lane starts at (-inf, INT_MAX): it loses to every real element, -inf included.
+__device__ __forceinline__ bool argmax_beats(float v, int i, float best, int bi) {
+	const bool vn = v != v, bn = best != best;
+	if (vn || bn) return vn && (!bn || i < bi);
+	return v > best || (v == best && i < bi);
+}
+
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ lp, int64_t* __restrict__ idx, int64_t rows, int C) {
 	const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
 	const int lane = threadIdx.x & 63;
 	if (row >= rows) return;
 	float best = -INFINITY;
 	int bi = 0x7fffffff;
-	for (int c = lane; c < C; c += 64) { float v = lp[row * C + c]; if (v > best || (v != v && best == best)) { best = v; bi = c; } }
+	for (int c = lane; c < C; c += 64) { float v = lp[row * C + c]; if (argmax_beats(v, c, best, bi)) { best = v; bi = c; } }
 #pragma unroll
 	for (int o = 32; o > 0; o >>= 1) {
 		float ov = __shfl_xor(best, o, 64);
 		int oi = __shfl_xor(bi, o, 64);
-		if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+		if (argmax_beats(ov, oi, best, bi)) { best = ov; bi = oi; }
 	}
-	if (lane == 0) idx[row] = bi == 0x7fffffff ? 0 : bi;
+	if (lane == 0) idx[row] = bi;
 }
 
 extern "C" int convasr_argmax(const float* log_probs, int64_t* idx, int64_t rows, int C, void* stream) {
