@@ -133,6 +133,10 @@ _SIGNATURES = dict(
 	convasr_rle1d_write = (c_int, [c_p, c_int, c_int, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p]),
 	convasr_speaker_error_counts_workspace_bytes = (c_i64, [c_i64]),
 	convasr_speaker_error_counts = (c_int, [c_p, c_p, ctypes.POINTER(ctypes.c_int32), c_int, c_i64, c_p, c_p, c_i64, c_p]),
+	convasr_resample_tile = (c_int, []),
+	convasr_resample_out_len = (c_i64, [c_i64, c_int, c_int]),
+	convasr_resample_taps = (c_int, [c_int, c_int, ctypes.c_double, ctypes.c_double]),
+	convasr_resample = (c_int, [c_p, c_int, c_i64, c_int, c_int, c_p, c_int, c_int, c_int, c_p, c_i64, c_int, c_p]),
 )
 SLIDE_ABS, SLIDE_NEG = 1, 2  # include/convasr_hip.h: CONVASR_SLIDE_ABS / CONVASR_SLIDE_NEG
 DIAR_MAX_LEN, DIAR_MAX_KERNEL, RLE_MAX_LEN, SPEAKER_MAX_PERMS = 1 << 28, 16384, 1 << 30, 8  # CONVASR_DIAR_MAX_LEN, ..._MAX_KERNEL, CONVASR_RLE_MAX_LEN, CONVASR_SPEAKER_MAX_PERMS

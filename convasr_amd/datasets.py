@@ -5,9 +5,16 @@ stay out of scope.
 * BucketingBatchSampler (datasets.py:357-401): same constructor, set_epoch / state_dict protocol and -- given the same epoch --
   the same batches as the reference (it draws from one torch.Generator in the same order).
 * collate_gpu: AudioTextDataset.collate_fn (datasets.py:305-332) with the padding done on the GPU: the ragged samples of a batch
-  travel as ONE pinned, packed host buffer (one copy instead of B), a kernel scatters them into the zero-padded (B, C, Tpad) batch."""
+  travel as ONE pinned, packed host buffer (one copy instead of B), a kernel scatters them into the zero-padded (B, C, Tpad) batch.
+* AudioTextDataset: the default mode of the reference's dataset over a JSON manifest of wav / raw files.  Workers decode on the CPU to int16 at
+  the file's own rate; int16 -> float, the mono mix and the change of sample rate run in collate_gpu (ops.resample, one launch per utterance).
+  The reference's other modes, exclusion lists, duration filters and string-array encoding stay out."""
+import json
 import math
 
+import os
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -67,27 +74,36 @@ def _pad_on_gpu(tensors, rows, pad_multiple, device, pad_to = None):
 	Lpad = int(math.ceil(max(lengths) / pad_multiple)) * pad_multiple if pad_to is None else int(pad_to(max(lengths)))
 	assert Lpad >= max(lengths)
 	dtype = tensors[0].dtype
-	packed = torch.empty(sum(l * rows for l in lengths), dtype = dtype).pin_memory()
-	offsets, pos = [], 0
-	for t, l in zip(tensors, lengths):
-		packed[pos:pos + l * rows].copy_(t.reshape(-1))
-		offsets.append(pos)
-		pos += l * rows
+	offsets = [0]
+	for l in lengths[:-1]:
+		offsets.append(offsets[-1] + l * rows)
+	if tensors[0].is_cuda:  # (samples that a GPU step produced: the resampled waveforms of AudioTextDataset)
+		dev_packed = torch.cat([t.reshape(-1) for t in tensors])
+	else:
+		packed = torch.empty(sum(l * rows for l in lengths), dtype = dtype).pin_memory()
+		for t, l, pos in zip(tensors, lengths, offsets):
+			packed[pos:pos + l * rows].copy_(t.reshape(-1))
+		dev_packed = packed.to(device, non_blocking = True)
 	meta = torch.tensor([offsets, lengths], dtype = torch.int64).pin_memory().to(device, non_blocking = True)
-	dev_packed = packed.to(device, non_blocking = True)
 	out = torch.empty(len(tensors), rows, Lpad, dtype = dtype, device = device)
 	_lib.call('convasr_collate_pad', _lib.ptr(dev_packed), _lib.ptr(meta[0]), _lib.ptr(meta[1]), _lib.ptr(out), dtype.itemsize, len(tensors), rows, Lpad, _lib.stream_ptr())
 	return out, lengths, Lpad
 
 
-def collate_gpu(batch, time_padding_multiple = 128, device = None, speaker_missing = 0, pad_to = None):
+def collate_gpu(batch, time_padding_multiple = 128, device = None, speaker_missing = 0, pad_to = None, sample_rate = None):
 	"""batch: list of (meta, speaker (S,), x (C, T), *targets (L,)) CPU samples, as AudioTextDataset.__getitem__ returns them in
 	the default mode.  Returns (meta list, s, x, xlen, y, ylen) like collate_fn, with x / y / xlen / ylen on `device`.
-	pad_to (optional): callable longest waveform length -> padded length of x (e.g. bucket_ceiling: one shape per bucket)."""
+	pad_to (optional): callable longest waveform length -> padded length of x (e.g. bucket_ceiling: one shape per bucket).
+	sample_rate (optional): the samples are AudioTextDataset's -- x int16 as decoded, at meta['sample_rate'] -- and become one row of float32 at
+	`sample_rate` on the GPU before the padding (ops.resample per utterance: decode, mono mix, and the rate change where the rates differ)."""
 	device = torch.device('cuda', torch.cuda.current_device()) if device is None else device
 	metas = [b[0] for b in batch]
 	n_t = len(batch[0]) - 3
-	x, xl, Tpad = _pad_on_gpu([b[2] for b in batch], len(batch[0][2]), time_padding_multiple, device, pad_to = pad_to)
+	waves = [b[2] for b in batch]
+	if sample_rate is not None:
+		from . import ops
+		waves = [ops.resample(w.t().contiguous().to(device, non_blocking = True), m['sample_rate'], sample_rate, mono = w.shape[0] > 1) for m, w in zip(metas, waves)]
+	x, xl, Tpad = _pad_on_gpu(waves, len(waves[0]), time_padding_multiple, device, pad_to = pad_to)
 	xlen = torch.tensor([l / Tpad if Tpad > 0 else 1.0 for l in xl], dtype = torch.float32).to(device, non_blocking = True)
 	ys, yl = [], []
 	Lpad = max(int(math.ceil(max(b[3 + j].shape[-1] for b in batch) / time_padding_multiple)) * time_padding_multiple for j in range(n_t)) if n_t else 0
@@ -185,6 +201,48 @@ def keep_samples(batch):
 	return batch
 
 
+class AudioTextDataset(torch.utils.data.Dataset):
+	"""The default mode of the reference's AudioTextDataset (datasets.py:23-355) over wav / raw files, with SyntheticAudioTextDataset's sample
+	contract and bucket rule.  manifest: a JSON file (or the list itself) of dict(audio_path, ref, begin?, end?, channel?); relative paths are
+	taken from the manifest's directory.  tokenizer: .encode([text]) -> [[label ids]] (e.g. transcript_generators.CharTokenizerLegacy).
+	__getitem__ runs on the CPU only (a DataLoader worker must never open the GPU): it decodes [begin, end) of the file to int16 at the file's
+	OWN rate and returns (meta, speaker (1,), x (C, T) int16, y (L,) int64) with meta['sample_rate'] = that rate; C = 1 when the entry names a
+	channel, otherwise the file's channels, mixed to one row later.  collate_gpu(..., sample_rate = dataset.sample_rate) -- what gpu_batches
+	passes for this dataset -- turns x into one float32 row at `sample_rate` on the GPU.  bucket[k] = ceil((duration / window_stride + 1) /
+	time_padding_multiple) from the entry's end - begin, or the file's duration where the entry has no end."""
+	decodes_on_gpu = True
+
+	def __init__(self, manifest, tokenizer, sample_rate = 16000, window_stride = 0.01, time_padding_multiple = 128, **read_audio_kwargs):
+		from . import audio
+		root = ''
+		if isinstance(manifest, str):
+			root = os.path.dirname(os.path.abspath(manifest))
+			with open(manifest) as f:
+				manifest = json.load(f)
+		self.examples = [dict(e, audio_path = os.path.join(root, e['audio_path'])) for e in manifest]
+		self.tokenizer, self.sample_rate, self.window_stride, self.time_padding_multiple = tokenizer, sample_rate, window_stride, time_padding_multiple
+		self.read_audio_kwargs = read_audio_kwargs  # raw_dtype / raw_sample_rate / raw_num_channels of .raw files
+		raw = {k: v for k, v in read_audio_kwargs.items() if k in ('raw_dtype', 'raw_sample_rate', 'raw_num_channels')}
+		self.duration = torch.tensor([e['end'] - e.get('begin', 0.0) if e.get('end') is not None else audio.compute_duration(e['audio_path'], **raw) - e.get('begin', 0.0) for e in self.examples], dtype = torch.float64)
+		self.bucket = ((self.duration / window_stride + 1) / time_padding_multiple).ceil().to(torch.short)
+
+	def __len__(self):
+		return len(self.examples)
+
+	def __getitem__(self, k):
+		from . import audio
+		e = self.examples[int(k)]
+		begin = float(e.get('begin', 0.0))
+		signal, rate = audio.decode_audio(e['audio_path'], None, offset = begin, duration = float(self.duration[int(k)]) if e.get('end') is not None else None, dtype = 'int16', **self.read_audio_kwargs)
+		assert signal.dtype == np.int16, f"{e['audio_path']}: int16 PCM expected, got {signal.dtype}"
+		if e.get('channel') is not None:
+			signal = signal[:, int(e['channel']):int(e['channel']) + 1]
+		x = torch.from_numpy(np.ascontiguousarray(signal)).t()  # (C, T) over interleaved memory: collate_gpu copies it as the file holds it
+		y = torch.tensor(self.tokenizer.encode([e['ref']])[0], dtype = torch.int64)
+		meta = dict(example_id = int(k), audio_path = e['audio_path'], ref = e['ref'], sample_rate = rate, channel = e.get('channel'), duration = float(self.duration[int(k)]), begin = begin, end = begin + float(self.duration[int(k)]))
+		return meta, torch.zeros(1, dtype = torch.int64), x, y
+
+
 def gpu_batches(dataset, batch_sampler, device, num_workers = 0, time_padding_multiple = None, timeout = 0, pad_to_bucket = False):
 	"""The reference's train DataLoader (train.py:647-655) with the batch assembly moved to the GPU: worker processes (or the main
 	process) produce lists of ragged CPU samples, collate_gpu packs each list into one pinned buffer, copies it once and pads on
@@ -199,5 +257,5 @@ def gpu_batches(dataset, batch_sampler, device, num_workers = 0, time_padding_mu
 		sr, ws = getattr(dataset, 'sample_rate', 16000), getattr(dataset, 'window_stride', 0.01)
 		pad_to = lambda longest: bucket_ceiling(longest, sr, ws, mult)
 	for samples in loader:
-		meta, s, x, xlen, y, ylen = collate_gpu(samples, time_padding_multiple = mult, device = device, pad_to = pad_to)
+		meta, s, x, xlen, y, ylen = collate_gpu(samples, time_padding_multiple = mult, device = device, pad_to = pad_to, sample_rate = dataset.sample_rate if getattr(dataset, 'decodes_on_gpu', False) else None)
 		yield meta, s, (x.squeeze(1) if x.shape[1] == 1 else x), xlen, y, ylen

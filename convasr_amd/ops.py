@@ -1223,3 +1223,60 @@ def speaker_error_counts(ref_mask, hyp_mask, perms):
 	counts = torch.empty(len(perms), 7, dtype = torch.int64, device = ref_mask.device)
 	call('convasr_speaker_error_counts', ptr(ref_mask), ptr(hyp_mask), flat, len(perms), n, ptr(counts), ptr(ws), ws.numel(), stream_ptr())
 	return counts
+
+
+RESAMPLE_ZEROS, RESAMPLE_BETA, RESAMPLE_ROLLOFF = 64, 14.769656459379492, 0.9475937167399596  # the parameters resampy publishes for 'kaiser_best'
+_resample_tables = {}  # (sr_in, sr_out, zeros, beta, rolloff) -> host table, (.., device) -> its copy there
+
+
+def resample_tile():
+	"""Outputs per workgroup of convasr_resample's tile route (tests straddle it)."""
+	return _lib.load().convasr_resample_tile()
+
+
+def resample_out_len(T_in, sr_in, sr_out):
+	"""ceil(T_in * L / M), the length rule of include/convasr_hip.h (librosa's)."""
+	return _query('convasr_resample_out_len', int(T_in), int(sr_in), int(sr_out))
+
+
+def resample_table(sr_in, sr_out, zeros = RESAMPLE_ZEROS, beta = RESAMPLE_BETA, rolloff = RESAMPLE_ROLLOFF):
+	"""The (taps, L) fp32 coefficient table of include/convasr_hip.h's resampler, computed in float64 on the host and rounded once; cached.
+	Raises ConvasrHipError outside the envelope (L x taps > 2^22) before anything is computed."""
+	import numpy as np
+	key = (int(sr_in), int(sr_out), float(zeros), float(beta), float(rolloff))
+	tab = _resample_tables.get(key)
+	if tab is None:
+		taps = _lib.call_rc('convasr_resample_taps', key[0], key[1], key[2], key[4])
+		g = math.gcd(key[0], key[1])
+		L, M = key[1] // g, key[0] // g
+		s = key[4] * min(1.0, L / M)
+		H = taps // 2 - 1
+		d = (L * (np.arange(taps, dtype = np.int64)[:, None] - H) - np.arange(L, dtype = np.int64)[None, :]) / float(L)  # k - tau per (tap, phase)
+		v = d * s / key[2]
+		inside = np.abs(d) * s <= key[2]
+		h = s * np.sinc(s * d) * np.i0(key[3] * np.sqrt(np.clip(1.0 - v * v, 0.0, None))) / np.i0(key[3])
+		tab = _resample_tables[key] = torch.from_numpy(np.where(inside, h, 0.0).astype(np.float32))
+	return tab
+
+
+def resample(x, sr_in, sr_out, mono = False, zeros = RESAMPLE_ZEROS, beta = RESAMPLE_BETA, rolloff = RESAMPLE_ROLLOFF, route = 0):
+	"""convasr_resample (include/convasr_hip.h): decode + de-interleave + optional mono mix + band-limited resampling in one launch.
+	x: a device tensor, either (T, C) int16 -- interleaved PCM as a wav file holds it, scaled by 1 / 32767 -- or (C, T) float32.  Returns
+	(C, T_out) float32, or (1, T_out) with mono, T_out = ceil(T * L / M).  sr_in == sr_out only decodes and mixes; T == 0 launches nothing.
+	route: 0 automatic, 1 / 2 force the tile / direct kernel (tests; the result does not depend on it)."""
+	require_cuda(x)
+	if x.ndim != 2 or x.dtype not in (torch.int16, torch.float32):
+		raise ValueError(f'resample: a (T, C) int16 or (C, T) float32 tensor expected, got {tuple(x.shape)} {x.dtype}')
+	T, C = (x.shape[0], x.shape[1]) if x.dtype == torch.int16 else (x.shape[1], x.shape[0])
+	sr_in, sr_out = int(sr_in), int(sr_out)
+	table = None
+	if sr_in != sr_out:
+		key = (sr_in, sr_out, float(zeros), float(beta), float(rolloff), x.device)
+		table = _resample_tables.get(key)
+		if table is None:
+			table = _resample_tables[key] = resample_table(sr_in, sr_out, zeros, beta, rolloff).to(x.device)
+	T_out = resample_out_len(T, sr_in, sr_out)
+	x = x.contiguous()
+	out = torch.empty(1 if mono else C, T_out, dtype = torch.float32, device = x.device)
+	call('convasr_resample', ptr(x), dtype_code(x.dtype), T, C, int(bool(mono)), ptr(table), 0 if table is None else table.shape[0], sr_in, sr_out, ptr(out), T_out, int(route), stream_ptr())
+	return out

@@ -114,3 +114,13 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 		aligned = metrics.align_strings_batch(out.hyp, out.ref)
 		out.words = [metrics.align_words(_hyp_, _ref_) for _hyp_, _ref_ in aligned]
 	return out
+
+
+def transcribe_file(args, text_pipeline, model, generator, audio_path, **read_audio_kwargs):
+	"""transcribe_batch on a wav / raw file instead of a tensor: audio.read_audio at args.sample_rate and args.mono (default True) -- decode, mono
+	mix and the change of sample rate on the GPU -- then every channel of the result as one utterance of the batch (transcribe.py:140-200 over
+	the reference's per-channel batches)."""
+	from . import audio
+	signal, sample_rate = audio.read_audio(audio_path, args.sample_rate, mono = getattr(args, 'mono', True), device = args.device, **read_audio_kwargs)
+	channels, duration = signal.shape[0], signal.shape[1] / sample_rate
+	return transcribe_batch(args, text_pipeline, model, generator, signal, torch.ones(channels), torch.zeros(channels), torch.full((channels, ), duration))

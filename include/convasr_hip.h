@@ -772,6 +772,36 @@ int64_t convasr_speaker_error_counts_workspace_bytes(int64_t n);
 int convasr_speaker_error_counts(const uint8_t* ref_mask, const uint8_t* hyp_mask, const int32_t* perms, int n_perms, int64_t n, int64_t* counts,
                                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- audio.read_audio / audio.resample (audio.py:17-128, 150-159) ------------------------------------------------------------------ */
+
+/* Decode + de-interleave + optional mono mix + band-limited rational resampling in one pass.  The reference resamples with librosa
+ * (audio.py:156); the resampler here is DEFINED BY THIS PROJECT and unpinned against librosa (which is not a dependency): same output
+ * length and timing, its own filter.
+ *   g = gcd(sr_in, sr_out), L = sr_out / g, M = sr_in / g, T_out = ceil(T_in * L / M) (librosa's length rule; convasr_resample_out_len);
+ *   s = rolloff * min(1, L / M); output n sits at input time tau = n * M / L:
+ *     y[n] = s * sum over k of x[k] * sinc(s * (k - tau)) * w((k - tau) * s / Z),  the integers k with |k - tau| * s <= Z, x[k] = 0 outside [0, T_in);
+ *     sinc(u) = sin(pi u) / (pi u);  w(v) = I0(beta * sqrt(1 - v * v)) / I0(beta) for |v| <= 1, otherwise 0;
+ *   defaults Z = 64 zero crossings, beta = 14.769656459379492, rolloff = 0.9475937167399596 (the parameters resampy publishes for
+ *   'kaiser_best'), the filter evaluated at the exact rational phases, not from an interpolated table.
+ * table: taps x L fp32 on the device, computed by the caller in float64 and rounded once, taps = 2 * floor(Z / s) + 2 = 2 H + 2
+ * (convasr_resample_taps): table[j * L + p] = s * sinc(s * d) * w(d * s / Z) with d = (L * (j - H) - p) / L where |d| * s <= Z, else 0.  With
+ * k0 = floor(n * M / L) and p = (n * M) mod L the kernel computes y[n] = sum over j = 0 .. taps - 1, in that order, of
+ * fma(x[k0 - H + j], table[j * L + p], .) in fp32: bit-repeatable and the same on every route.
+ * x: x_dtype CONVASR_I16 = interleaved (T_in, C) int16 as a wav file holds it, each sample (float)v / 32767.f correctly rounded (s2f_numpy,
+ * audio.py:15); CONVASR_F32 = planar (C, T_in) fp32.  out: planar (C, T_out) fp32; with mono != 0 (1, T_out), the filter applied to the fp32
+ * mean of the channels (their sum in ascending channel order, divided by C: numpy's mean for C <= 7), mixed on the inputs in the same pass.
+ * sr_in == sr_out: decode, de-interleave and mix only; table and taps are ignored.  T_in == 0: nothing is launched.
+ * route: 0 = automatic; 1 = a workgroup per convasr_resample_tile() (256) consecutive outputs with their input span decoded into LDS
+ * (CONVASR_EUNSUPPORTED when the span does not fit in 64 KiB: a steep downsampling); 2 = one output per thread reading global memory (tests
+ * and tuning; the result does not depend on the route).  No workspace, no memset or copy: the call is one kernel node.
+ * Envelope, checked before any launch: L * taps <= 2^22 table entries, 1 <= C <= 8, T_in * C < 2^40; outside it CONVASR_EUNSUPPORTED (the
+ * queries return -1 / the code); any other bad argument (rates <= 0, odd taps, T_out not the length rule's, NULL) CONVASR_EINVAL. */
+int convasr_resample_tile(void);
+int64_t convasr_resample_out_len(int64_t T_in, int sr_in, int sr_out);
+int convasr_resample_taps(int sr_in, int sr_out, double zeros, double rolloff);
+int convasr_resample(const void* x, int x_dtype, int64_t T_in, int C, int mono, const float* table, int taps, int sr_in, int sr_out,
+                     float* out, int64_t T_out, int route, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
