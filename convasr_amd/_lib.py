@@ -114,6 +114,9 @@ _SIGNATURES = dict(
 	                                           c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p]),
 	convasr_edit_distance = (c_int, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_i64, c_p]),
 	convasr_ctc_greedy_collapse = (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_ctc_greedy_segments_chunk_frames = (c_int, []),
+	convasr_ctc_greedy_segments_workspace_bytes = (c_i64, [c_int, c_int]),
+	convasr_ctc_greedy_segments = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_nw_align_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
 	convasr_nw_align = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_sliding_max_out_len = (c_i64, [c_i64, c_int]),

@@ -1025,6 +1025,46 @@ def ctc_greedy_collapse(path, lengths, eps, space, blank_amount_to_space = 10):
 	return tokens, out_lengths
 
 
+def ctc_greedy_segments_chunk():
+	"""Frames per chunk of convasr_ctc_greedy_segments (one workgroup per utterance and chunk; tests straddle it)."""
+	return _lib.load().convasr_ctc_greedy_segments_chunk_frames()
+
+
+def ctc_greedy_segments(path, lengths, eps, space, blank_amount_to_space = 10, split_words = True):
+	"""GreedyCTCGenerator.generate's collapse with the frame of every token and the word segments, on the device (include/convasr_hip.h:
+	convasr_ctc_greedy_segments has the rule).  path: (B, T) int64 per-frame argmax (ops.argmax); lengths (B,) frames, or None (all T).
+	split_words: every space emitted from the path opens a segment and stands twice at its front (time stamps given); False: one segment
+	per non-empty utterance.  Returns device tensors, packed over the batch in utterance order: tokens (n,) int64, frames (n,) int32,
+	counts (2, B) int64 (tokens, then segments, per utterance), seg_first (m,) int64 (index of a segment's first token in tokens),
+	seg_begin / seg_end (m,) int32 frames.  One read-back, of the counts (16 B bytes), sizes the results.  Outside the envelope it raises
+	ConvasrHipError."""
+	require_cuda(path)
+	if path.ndim != 2 or path.dtype != torch.int64:
+		raise ValueError(f'ctc_greedy_segments: path must be a (B, T) int64 tensor, got {tuple(path.shape)} {path.dtype}')
+	B, T = path.shape
+	dev = path.device
+	path = path.contiguous()
+	lengths = torch.full((B,), T, dtype = torch.int64, device = dev) if lengths is None else torch.as_tensor(lengths).to(device = dev, dtype = torch.int64).contiguous()
+	if lengths.shape != (B,):
+		raise ValueError(f'ctc_greedy_segments: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
+	lib = _lib.load()
+	nbytes = lib.convasr_ctc_greedy_segments_workspace_bytes(B, T)
+	if nbytes < 0:
+		raise _lib.ConvasrHipError(f'convasr_ctc_greedy_segments_workspace_bytes failed: {lib.convasr_last_error().decode()}')
+	room = B * T * (2 if split_words else 1)
+	tokens = torch.empty(room, dtype = torch.int64, device = dev)
+	frames = torch.empty(room, dtype = torch.int32, device = dev)
+	counts = torch.empty(2, B, dtype = torch.int64, device = dev)
+	seg_first = torch.empty(B * T, dtype = torch.int64, device = dev)
+	seg_begin = torch.empty(B * T, dtype = torch.int32, device = dev)
+	seg_end = torch.empty(B * T, dtype = torch.int32, device = dev)
+	ws = torch.empty(nbytes, dtype = torch.uint8, device = dev)
+	call('convasr_ctc_greedy_segments', ptr(path), ptr(lengths), ptr(tokens), ptr(frames), ptr(counts), ptr(seg_first), ptr(seg_begin), ptr(seg_end),
+	     ptr(ws), nbytes, B, T, int(eps), int(space), int(blank_amount_to_space), int(bool(split_words)), stream_ptr())
+	n, m = counts.sum(dim = 1).tolist()
+	return tokens[:n], frames[:n], counts, seg_first[:m], seg_begin[:m], seg_end[:m]
+
+
 # ------------------------------------------------------------------------------------------------ alignment
 
 NW_WORKSPACE_CAP = 1 << 30  # bytes of direction workspace one convasr_nw_align launch may take; a resource bound, not a measurement

@@ -1,9 +1,13 @@
 """Greedy CTC decoding (reference: transcript_generators.py:8-93, text_tokenizers.py:7-51).
 
-The per-frame argmax over classes runs on the GPU (convasr_argmax); the collapse rules -- skip leading blank/space, merge
-repeats unless a blank intervened, >= blank_amount_to_space consecutive blanks insert one space, a blank right after a space
-is ignored, a new segment starts at every word-start token when time stamps are given -- stay a host loop over B x t ints,
-as in the reference."""
+The per-frame argmax over classes runs on the GPU (convasr_argmax).  The collapse rules -- skip leading blank/space, merge repeats
+unless a blank intervened, >= blank_amount_to_space consecutive blanks insert one space, a blank right after a space is ignored, a new
+segment starts at every word-start token when time stamps are given -- are GreedyCTCGenerator.generate_host, a host loop over B x t
+ints as in the reference, and the oracle of everything else.  For CUDA log-probs and a tokenizer of CharTokenizerLegacy's kind
+(silence = {eps, space}, word start = space) GreedyCTCGenerator.generate runs the same rules on the device instead
+(ops.ctc_greedy_segments: tokens, their frames and the word segments, include/convasr_hip.h has the rule), gathers the time stamps at
+the segments' begin / end frames there and copies only counts, tokens and those stamps: host work and device-to-host bytes grow with
+the transcript, not with B x t.  CPU tensors, other tokenizers and output_lengths given as a list keep the host loop."""
 import types
 
 import torch
@@ -46,7 +50,48 @@ class GreedyCTCGenerator:
 	def __init__(self, blank_amount_to_space = 10):
 		self.blank_amount_to_space = blank_amount_to_space
 
+	def device_route(self, tokenizer, log_probs, output_lengths):
+		"""Whether generate decodes on the device: CUDA log-probs, lengths as a tensor (or None), an integer blank_amount_to_space >= 0 and a
+		tokenizer inside convasr_ctc_greedy_segments' scope -- silence = {eps, space}, and space the one word-start token among the classes."""
+		if not (torch.is_tensor(log_probs) and log_probs.is_cuda and log_probs.ndim == 3) or not (output_lengths is None or torch.is_tensor(output_lengths)):
+			return False
+		eps, space, bats = getattr(tokenizer, 'eps_id', None), getattr(tokenizer, 'space_id', None), self.blank_amount_to_space
+		if not all(type(v) is int and v >= 0 for v in (eps, space, bats)) or eps == space or tokenizer.silence_tokens_ids != {eps, space}:
+			return False
+		return all(bool(tokenizer.is_start_word_token(c)) == (c == space) for c in range(log_probs.shape[1]))
+
 	def generate(self, tokenizer, log_probs, begin, end, output_lengths = None, time_stamps = None, segment_text_key = 'hyp', segment_extra_info = None):
+		if not self.device_route(tokenizer, log_probs, output_lengths):
+			return self.generate_host(tokenizer, log_probs, begin, end, output_lengths, time_stamps, segment_text_key, segment_extra_info)
+		B = log_probs.shape[0]
+		tokens, _, counts, seg_first, seg_begin, seg_end = ops.ctc_greedy_segments(ops.argmax(log_probs), output_lengths, tokenizer.eps_id, tokenizer.space_id,
+		                                                                           self.blank_amount_to_space, split_words = time_stamps is not None)
+		n_seg = counts[1].tolist()
+		tokens, seg_first = tokens.tolist(), seg_first.tolist()
+		if time_stamps is not None:  # the stamps of the segments' begin / end frames, gathered where the stamps live
+			utt = torch.repeat_interleave(counts[1], output_size = len(seg_first)).to(time_stamps.device)
+			at = torch.stack([seg_begin, seg_end]).to(device = utt.device, dtype = torch.int64)
+			ts_begin, ts_end = time_stamps[utt, at].cpu().tolist()
+			begin = torch.clamp(begin, min = 0.0).cpu().tolist()
+		else:
+			begin = begin.cpu().tolist()
+		end = end.cpu().tolist()
+		seg_first.append(len(tokens))
+		texts = tokenizer.decode([tokens[seg_first[k]:seg_first[k + 1]] for k in range(len(seg_first) - 1)])
+		result, k0 = [], 0
+		for i in range(B):
+			transcript = Transcript()
+			for k in range(k0, k0 + n_seg[i]):
+				t_begin, t_end = (begin[i] + ts_begin[k], begin[i] + ts_end[k]) if time_stamps is not None else (begin[i], end[i])
+				seg = Segment(begin = t_begin, end = t_end, **{segment_text_key: texts[k]})
+				if segment_extra_info is not None:
+					seg.update(segment_extra_info[i])
+				transcript.append(seg)
+			k0 += n_seg[i]
+			result.append([transcript])
+		return result
+
+	def generate_host(self, tokenizer, log_probs, begin, end, output_lengths = None, time_stamps = None, segment_text_key = 'hyp', segment_extra_info = None):
 		idx_all = (ops.argmax(log_probs) if log_probs.is_cuda else log_probs.argmax(dim = 1)).cpu().tolist()
 		ts_all = time_stamps.cpu().tolist() if time_stamps is not None else None
 		begin = torch.clamp(begin, min = 0.0).cpu().tolist() if time_stamps is not None else begin.cpu().tolist()

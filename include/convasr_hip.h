@@ -658,6 +658,36 @@ int convasr_edit_distance(const int64_t* hyp, const int64_t* hyp_lengths, const 
 int convasr_ctc_greedy_collapse(const int64_t* path, const int64_t* lengths, int64_t* tokens, int64_t* out_lengths, int B, int T,
                                 int eps, int space, int blank_amount_to_space, void* stream);
 
+/* The greedy CTC decode of GreedyCTCGenerator.generate WITH the frame of every token and the word segments, for a tokenizer whose silence
+ * tokens are {eps, space} and whose word-start token is space (CharTokenizerLegacy).  path (B, T) int64: the per-frame argmax
+ * (convasr_argmax); lengths (B,) int64.  The host loop (GreedyCTCGenerator.generate_host) is the oracle; this is the same rule in a form
+ * that decides every frame on its own.  Per utterance, with n = clamp(lengths[b], 0, T) and gap = max(blank_amount_to_space, 1):
+ *   start = the first frame in [0, n) whose class is neither eps nor space; when there is none the utterance yields nothing (a non-silent
+ *   frame at or after n does not count).
+ *   A non-blank frame t in [start, n) (class != eps), with p = the previous non-blank frame >= start and g = t - p - 1 blanks between them:
+ *     frame `start` always emits its class; if path[p] == space, t emits iff path[t] != space; otherwise t emits iff g >= 1 or
+ *     path[t] != path[p].
+ *   A blank frame t in (start, n) emits one INSERTED space iff path[p] != space and t - p == gap -- also in a blank run that reaches n.
+ *     (A space frame of the path after an inserted space is emitted again: g >= 1.)
+ *   Segments, split_words != 0 (time stamps given): the first emission opens segment 0; every space emitted from the path opens a new
+ *     segment and is stored TWICE at its front (the host loop's tokens = [eps, c]; tokens.append(c)), both with its frame; an inserted space
+ *     opens nothing.  A segment's begin frame is the frame of its first emission, its end frame the frame of its last emission that came
+ *     from the path (inserted spaces do not move it).  split_words == 0: one segment per non-empty utterance, from `start` to the last
+ *     path emission, and no token is doubled.
+ * Outputs, packed over the batch in utterance order: tokens int64 / frames int32, room for B * T * (split_words ? 2 : 1) entries each;
+ * counts (2, B) int64 = tokens per utterance, then segments per utterance; seg_first int64 (the segment's first token, an index into the
+ * packed tokens), seg_begin / seg_end int32 (frames inside the utterance), room for B * T entries each.  Nothing past the counts is written.
+ * Utterances are cut into chunks of convasr_ctc_greedy_segments_chunk_frames() frames, one workgroup per (utterance, chunk); five plain
+ * launches in stream order (chunk summaries, their carry, counts, offsets, writes), no workgroup waits on another, no memset or copy: the
+ * call can be captured into a graph.  workspace: convasr_ctc_greedy_segments_workspace_bytes(B, T) bytes (-1 outside the envelope),
+ * uninitialised.  Envelope, checked before any launch: B >= 1, T >= 1, B * T < 2^31, eps != space, both >= 0,
+ * blank_amount_to_space >= 0, no NULL pointer, a workspace of at least that size; outside it CONVASR_EINVAL. */
+int convasr_ctc_greedy_segments_chunk_frames(void);
+int64_t convasr_ctc_greedy_segments_workspace_bytes(int B, int T);
+int convasr_ctc_greedy_segments(const int64_t* path, const int64_t* lengths, int64_t* tokens, int32_t* frames, int64_t* counts,
+                                int64_t* seg_first, int32_t* seg_begin, int32_t* seg_end, void* workspace, int64_t workspace_bytes, int B, int T,
+                                int eps, int space, int blank_amount_to_space, int split_words, void* stream);
+
 /* ---- Alignment: metrics.py:365-407 (align_strings) and its aligner (metrics.py:447-645), the step every error analysis of the reference
  * starts with (ErrorAnalyzer.analyze, transcribe.py --align-words) ------------------------------------------------------------------------ */
 
