@@ -113,8 +113,14 @@ template <typename H> __global__ __launch_bounds__(256) void ng_step_kernel(NgPa
 		const float g2c = (float)(q.g2[s] * (double)clip * (double)clip);  // sum of squares of the CLIPPED gradient (clip_grad_norm_ scales .grad in place)
 		return q.first ? g2c : q.ema_in[s] * q.b2 + g2c * (1.f - q.b2);
 	};
-	// the workgroup that holds a segment's first element publishes its new EMA (ema_in / ema_out are distinct buffers)
-	for (int s = s0 + threadIdx.x; s <= s1; s += 256)
+	// the workgroup that holds a segment's first element publishes its new EMA (ema_in / ema_out are distinct buffers).  An EMPTY segment
+	// (a parameter without elements) has no element to be found by: the ones that start at i0 sort in front of s0, the ones at the arena's
+	// end behind s1 -- the workgroup whose chunk starts there, and the last one, publish them too.  (Every lane walks back on its own: the
+	// loop runs once per empty segment at i0, not at all without one, and reads global offsets only when n_seg + 1 > NG_TABLE.)
+	int p0 = s0;
+	while (p0 > 0 && q.offsets[p0 - 1] >= i0) --p0;
+	const int p1 = i1 == q.n ? q.n_seg - 1 : s1;
+	for (int s = p0 + threadIdx.x; s <= p1; s += 256)
 		if (q.offsets[s] >= i0) q.ema_out[s] = seg_ema(s);
 	auto update = [&](int64_t i, float inv_denom) {
 		const float pv = q.p[i];
