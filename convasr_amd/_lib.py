@@ -56,6 +56,11 @@ _SIGNATURES = dict(
 	convasr_log_softmax_bwd = (c_int, [c_p, c_p, c_p, c_i64, c_int, c_p]),
 	convasr_ctc_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
 	convasr_ctc_loss = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_ctc_loss_supported = (c_int, [c_int, c_int, c_int, c_int]),
+	convasr_ctc_loss_long_states_per_block = (c_int, []),
+	convasr_ctc_loss_long_chunk_frames = (c_int, []),
+	convasr_ctc_loss_long_workspace_bytes = (c_i64, [c_int, c_int, c_int, c_int]),
+	convasr_ctc_loss_long = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_scale_rows = (c_int, [c_p, c_p, c_p, c_i64, c_p, c_int, c_i64, c_p]),
 	convasr_loss_head = (c_int, [c_p, c_p, c_i64, c_p, c_int, c_f32, c_p, c_p, c_p, c_p, c_f32, c_p]),
 	convasr_entropy = (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_f32, c_p]),

@@ -374,6 +374,19 @@ extern "C" int64_t convasr_ctc_workspace_bytes(int B, int T, int S_max) {
 	return (2 * (int64_t)B * T * 128 * (nph + npl) + 4 * (int64_t)B * NB + 2 * (int64_t)B) * (int64_t)sizeof(float);  // lattices, offsets, totals
 }
 
+// bytes of LDS every launch needs whatever the log-probs' home: fin, fcum, the per-frame edge slots of both sweeps and their offsets
+static size_t ctc_lds_fixed(int T, int cap) {
+	const int64_t NB = T / CTC_RENORM + 1;
+	return (size_t)(cap + 4 + ((3 * (int64_t)T + 2 * NB + 3) & ~(int64_t)3)) * sizeof(float);
+}
+
+// 1: convasr_ctc_loss takes the shape (labels within ctc_split, the edge slots of T frames within the LDS of a CU, C <= 8192), 0: it refuses it
+extern "C" int convasr_ctc_loss_supported(int B, int T, int C, int S_max) {
+	int nph, npl;
+	if (B <= 0 || T <= 0 || C <= 1 || C > 8192 || S_max < 0 || ctc_split(S_max, &nph, &npl) < 0) return 0;
+	return ctc_lds_fixed(T, 128 * (nph + npl)) <= 159 * 1024 ? 1 : 0;
+}
+
 extern "C" int convasr_ctc_loss(const float* log_probs, const int64_t* targets, const int64_t* olen, const int64_t* ylen, float* nll, float* grad,
                                 void* workspace, int B, int T, int C, int S_max, int blank, void* stream) {
 	CONVASR_CHECK_ARG(log_probs && targets && olen && ylen && nll && workspace && B > 0 && T > 0 && C > 1 && S_max >= 0 && blank >= 0 && blank < C, "ctc_loss: bad arguments");
@@ -389,7 +402,7 @@ extern "C" int convasr_ctc_loss(const float* log_probs, const int64_t* targets, 
 	const int t_per_block = 32;
 	dim3 ggrid((T + t_per_block - 1) / t_per_block, B);
 	const size_t gsmem = 4 * (size_t)C * sizeof(float);
-	const size_t lds_fixed = (size_t)(cap + 4 + ((3 * T + 2 * NB + 3) & ~3)) * sizeof(float), lds_lp = (size_t)T * (C + 1) * sizeof(float);
+	const size_t lds_fixed = ctc_lds_fixed(T, cap), lds_lp = (size_t)T * (C + 1) * sizeof(float);
 	CONVASR_CHECK_ARG(lds_fixed <= 159 * 1024, "ctc_loss: T %d too long for the edge slots", T);
 	const bool in_lds = lds_fixed + lds_lp <= 159 * 1024;  // T = 753, C = 38: 117 KB + 12 KB of the 160 KiB of a CU
 #define CTC_LAUNCH(NPH, NPL, LDS) do { \

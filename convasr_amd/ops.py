@@ -678,6 +678,8 @@ def ctc_loss(log_probs, targets, olen, ylen, blank, need_grad = True):
 	olen = olen.to(device = dev, dtype = torch.int64).contiguous()
 	ylen = ylen.to(device = dev, dtype = torch.int64).contiguous()
 	S_max = targets.shape[1]
+	if not _lib.load().convasr_ctc_loss_supported(B, T, C, S_max):  # more than 1,023 labels, or more frames than the one-workgroup kernel's LDS slots hold: the tiled kernel
+		return ctc_loss_long(log_probs, targets, olen, ylen, blank, need_grad = need_grad)
 	nbytes = _lib.load().convasr_ctc_workspace_bytes(B, T, S_max)
 	if nbytes < 0:
 		raise _lib.ConvasrHipError(f'ctc_loss: target length {S_max} unsupported')
@@ -685,6 +687,45 @@ def ctc_loss(log_probs, targets, olen, ylen, blank, need_grad = True):
 	nll = torch.empty(B, dtype = torch.float32, device = dev)
 	grad = empty_cl(B, C, T, torch.float32, dev) if need_grad else None
 	call('convasr_ctc_loss', ptr(log_probs), ptr(targets), ptr(olen), ptr(ylen), ptr(nll), ptr(grad), ptr(ws), B, T, C, S_max, blank, stream_ptr())
+	return nll, grad
+
+
+CTC_LONG_WORKSPACE_CAP = 16 << 30  # bytes of workspace one convasr_ctc_loss_long call may take; a resource bound like ALIGN_LONG_WORKSPACE_CAP, not a measurement
+
+
+def ctc_loss_long_tiles():
+	"""(states per block, default frames per chunk) of convasr_ctc_loss_long's tiles (tests straddle them)."""
+	lib = _lib.load()
+	return lib.convasr_ctc_loss_long_states_per_block(), lib.convasr_ctc_loss_long_chunk_frames()
+
+
+def ctc_loss_long(log_probs, targets, olen, ylen, blank, need_grad = True, chunk_frames = 0, workspace_cap = CTC_LONG_WORKSPACE_CAP):
+	"""ctc_loss for whole recordings (include/convasr_hip.h: convasr_ctc_loss_long): up to 131,071 labels and 2^20 frames, the same tensors in
+	and out as ctc_loss, which sends here every shape its own kernel refuses.  chunk_frames: 0 = the default tile length, 16 .. 4096 forces
+	it (the result does not depend on it).  The workspace (two whole fp32 lattices: about 4.4 GB for ten minutes) is allocated for this call
+	and goes back to the allocator; a need above workspace_cap raises ConvasrHipError.  Not under stream capture."""
+	require_cuda(log_probs)
+	B, C, T = log_probs.shape
+	assert is_cl(log_probs) and log_probs.dtype == torch.float32
+	dev = log_probs.device
+	if _capturing[0] or torch.cuda.is_current_stream_capturing():
+		raise _lib.ConvasrHipError(f'ctc_loss_long: B {B}, T {T} is beyond the one-workgroup CTC kernel, and the tiled kernel (hundreds of launches over a workspace allocated per call) cannot be captured into a graph: run this step eagerly')
+	targets = targets.to(device = dev, dtype = torch.int64).contiguous()
+	if targets.ndim == 1:
+		targets = targets.view(B, -1)
+	olen = olen.to(device = dev, dtype = torch.int64).contiguous()
+	ylen = ylen.to(device = dev, dtype = torch.int64).contiguous()
+	S_max = targets.shape[1]
+	lib = _lib.load()
+	nbytes = lib.convasr_ctc_loss_long_workspace_bytes(B, T, C, S_max)
+	if nbytes < 0:
+		raise _lib.ConvasrHipError(f'convasr_ctc_loss_long_workspace_bytes failed: {lib.convasr_last_error().decode()}')
+	if nbytes > workspace_cap:
+		raise _lib.ConvasrHipError(f'ctc_loss_long: {nbytes} bytes of workspace needed for B {B}, T {T}, S_max {S_max}, above the cap of {workspace_cap}')
+	nll = torch.empty(B, dtype = torch.float32, device = dev)
+	grad = empty_cl(B, C, T, torch.float32, dev) if need_grad else None
+	ws = torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)  # (not ops.workspace: that cache keeps its buffers for good)
+	call('convasr_ctc_loss_long', ptr(log_probs), ptr(targets), ptr(olen), ptr(ylen), ptr(nll), ptr(grad), ptr(ws), nbytes, B, T, C, S_max, int(blank), int(chunk_frames), stream_ptr())
 	return nll, grad
 
 

@@ -257,6 +257,31 @@ int64_t convasr_ctc_workspace_bytes(int B, int T, int S_max);
  * the call fails with CONVASR_EUNSUPPORTED / an invalid-argument error and launches nothing. */
 int convasr_ctc_loss(const float* log_probs, const int64_t* targets, const int64_t* olen, const int64_t* ylen,
                      float* nll, float* grad, void* workspace, int B, int T, int C, int S_max, int blank, void* stream);
+/* 1 when convasr_ctc_loss takes the shape -- S_max within its label limit, T within what its LDS hand-over slots hold, C <= 8192 -- and 0
+ * when it refuses it: what a caller asks before it chooses between the call above and convasr_ctc_loss_long (ops.ctc_loss does). */
+int convasr_ctc_loss_supported(int B, int T, int C, int S_max);
+
+/* The same loss and gradient (F.ctc_loss at models.py:323 with no limit on target or input length) for whole recordings: arguments,
+ * results and edge cases are those of convasr_ctc_loss -- +inf and a zero gradient for an infeasible utterance, 0 / +inf for olen == 0
+ * with an empty / non-empty target, a -inf log-prob staged as the finite sentinel, a non-finite loss for a NaN log-prob, a zero gradient
+ * at frames >= olen, ragged olen / ylen and empty targets within one batch.  Both lattices are cut into tiles of
+ * convasr_ctc_loss_long_states_per_block() states x chunk frames, one wave per tile; launch k of ceil(T / chunk) + ceil((2 S_max + 1) /
+ * states_per_block) - 1 plain launches runs the k-th anti-diagonal of the alpha sweep and of the beta sweep (alpha tiles in which no
+ * state can be reached yet, s > 2t + 1, are not launched; beta tiles beyond an utterance's own reach end at once), then one launch for
+ * the totals and one for the gradient (one wave per frame, a fixed order of additions, no atomics on global memory).  Nothing waits inside
+ * a launch.  Arithmetic: fp32 log-sum-exp in base 2, renormalised per block of states by integer log2 offsets at every frame whose
+ * absolute index is a multiple of 8; the result does not depend on chunk_frames: 0 = convasr_ctc_loss_long_chunk_frames() (256), or
+ * 16 .. 4096 to force the chunk length (tests and tuning).  grad may be NULL (forward only).  workspace: at least
+ * convasr_ctc_loss_long_workspace_bytes bytes, 16-byte aligned, uninitialised: two fp32 lattices [B][T][blocks x states_per_block] and
+ * their offsets [B][blocks][T] -- ten minutes (30,000 frames, 9,000 labels) take about 4.4 GB.  Envelope: 0 <= S_max <= 131071,
+ * 1 <= T <= 2^20, 2 <= C <= 8192, 1 <= B <= 65535, checked before any launch; outside it CONVASR_EUNSUPPORTED (the query returns that
+ * negative code, with a message), any other bad argument CONVASR_EINVAL.  Not for stream capture (hundreds of launches over a per-call
+ * workspace). */
+int convasr_ctc_loss_long_states_per_block(void);
+int convasr_ctc_loss_long_chunk_frames(void);
+int64_t convasr_ctc_loss_long_workspace_bytes(int B, int T, int C, int S_max);
+int convasr_ctc_loss_long(const float* log_probs, const int64_t* targets, const int64_t* olen, const int64_t* ylen, float* nll, float* grad,
+                          void* workspace, int64_t workspace_bytes, int B, int T, int C, int S_max, int blank, int chunk_frames, void* stream);
 /* out[b,t,c] = grad[b,t,c] * gscale[b]   (chain rule for reduction='none'); with gdiv != NULL the factor is
  * gscale[b] / (float)gdiv[b * gdiv_stride]: the "/ ylen[:, 0]" of models.py:323 folded into the same pass.  gscale NULL (gdiv given):
  * the factor is 1 / gdiv -- the same division in the forward direction (per_b = 1: nll[b] / ylen[b, 0]). */
