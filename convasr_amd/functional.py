@@ -1,7 +1,7 @@
 """torch.autograd.Function wrappers: each forward/backward is a fixed sequence of libconvasr_hip.so kernels.
 
 Parameters keep the reference's fp32 (Cout, Cin, K) layout; the packed compute-dtype copies the MFMA kernels consume are
-cached per parameter version.  When a parameter carries `_convasr_grad` (a pre-allocated fp32 gradient view installed by
+cached per parameter version (convasr_amd.weights).  When a parameter carries `_convasr_grad` (a pre-allocated fp32 gradient view installed by
 `convasr_amd.train.FlatParameters`), backward writes / accumulates into it directly and hands autograd `None` -- no
 extra gradient copies, and the data-parallel engine is told the moment each gradient is final.
 """
@@ -10,111 +10,7 @@ import os
 import torch
 
 from . import ops, _lib
-
-_pack_cache = {}
-_param_epoch = [0]  # bumped by optimizers that update parameters behind torch's back (convasr_amd.train.SGD)
-
-
-def bump_param_epoch():
-	_param_epoch[0] += 1
-
-
-def param_version(w):
-	"""What a packed copy of `w` is valid for: torch's in-place version counter, the storage address, and the epoch optimizers bump
-	when they update parameters behind torch's back."""
-	return (w._version, w.data_ptr(), _param_epoch[0])
-
-
-def packed_weight(w, dtype, mode):
-	"""Packed [K][rows_pad][cols] copy of a conv parameter, refreshed (in place) only when the parameter changed.  In training
-	the forward and the dgrad layout are produced together the first time either is asked for after an update.
-	A tap-major arena parameter (train.FlatParameters) whose Cout needs no row padding has no forward copy of its own: in fp32
-	the master IS the packed operand, in bf16 / fp16 it is the parameter's segment of the arena's 16-bit mirror, which the fused optimizer
-	kernels keep current -- only the transposed dgrad copy is still built by a packing launch."""
-	ver = param_version(w)
-	ent = _pack_cache.get((id(w), dtype))
-	if ent is not None:
-		# fast path (most calls of a step): the copy asked for is current.  For a weight served from the arena's 16-bit mirror that
-		# also means: the mirror object is still the one the entry points into, and the arena vouches for this version of the segment
-		if mode == _lib.PACK_DGRAD:
-			if ent['dgr_ver'] == ver:
-				return ent['dgr']
-		elif ent['fwd_ver'] == ver:
-			flat = ent.get('flat')
-			if flat is None or (flat.data16 is ent.get('mirror') and flat._mirror_ver.get(id(w)) == ver):
-				return ent['fwd']
-	if ent is None:
-		ent = _pack_cache[(id(w), dtype)] = dict(w = w, fwd = None, dgr = None, fwd_ver = None, dgr_ver = None)  # holds `w`: id() stays unique
-	arena = getattr(w, '_convasr_arena', None)
-	# (the address test: p.data may have been replaced since FlatParameters re-homed it -- model.to(), load_state_dict(assign = True) --
-	# with the strides preserved; such a parameter no longer aliases the arena and is packed like any other)
-	in_place = arena is not None and (ops.weight_layout(w) == _lib.W_KMAJOR or (w.shape[2] == 1 and w.is_contiguous())) and ops.cout_pad(w.shape[0]) == w.shape[0] and dtype in (torch.float32, ) + ops.HALF_DTYPES and w.device == arena[0].data.device and w.data_ptr() == arena[0].data.data_ptr() + 4 * arena[1]
-	if in_place:
-		flat, off = arena
-		Cout, Cin, K = w.shape
-		if dtype == torch.float32:
-			ent['fwd'], ent['fwd_ver'] = flat.data[off:off + w.numel()].view(K, Cout, Cin), ver
-		else:
-			# the mirror segment is current only if the arena says so for THIS version: a mirror re-allocated in the other 16-bit type
-			# (FlatParameters.mirror) is zero-filled, and a cache entry left from before the switch must not vouch for it
-			ent['fwd'] = flat.mirror(dtype)[off:off + w.numel()].view(K, Cout, Cin)
-			ent['fwd_ver'] = ver if flat._mirror_ver.get(id(w)) == ver else None
-			ent['flat'], ent['mirror'] = flat, flat.data16  # (what the fast path above re-checks)
-	if mode == _lib.PACK_FWD and ent['fwd_ver'] == ver:
-		return ent['fwd']
-	if mode == _lib.PACK_DGRAD and ent['dgr_ver'] == ver:
-		return ent['dgr']
-	if mode == _lib.PACK_DGRAD:
-		ent['fwd'], ent['dgr'] = ops.pack_weight(w, dtype, None, out = (ent['fwd'], ent['dgr']), fwd_is_current = ent['fwd_ver'] == ver)
-		ent['fwd_ver'] = ent['dgr_ver'] = ver
-	else:  # (the forward copy alone, also in training: the dgrad copies of a step are made together, by prepack_dgrad_weights' one launch)
-		ent['fwd'] = ops.pack_weight(w, dtype, _lib.PACK_FWD, out = (ent['fwd'], None))
-		ent['fwd_ver'] = ver
-	if in_place and dtype in ops.HALF_DTYPES:
-		arena[0]._mirror_ver[id(w)] = ver
-	return ent['fwd'] if mode == _lib.PACK_FWD else ent['dgr']
-
-
-_structure_epoch = [0]
-
-
-def invalidate_pack_cache():
-	"""Called when conv modules were replaced (fuse_conv_bn_eval): packed copies are dropped and everything derived from the module tree
-	(JasperNet's list of dgrad weights, captured step graphs) is rebuilt on next use."""
-	_pack_cache.clear()
-	_split_cache.clear()
-	_structure_epoch[0] += 1
-
-
-_split_cache = {}
-
-
-def force_repack():
-	"""Declare every packed copy that a launch of this module keeps current stale (the arena's 16-bit mirror segments, which the fused
-	optimizer kernels write, stay vouched for): the next forward / backward re-packs them all.  train.GraphedTrainStep calls it right
-	before a capture so that the graph records every per-step pack launch whatever ran since the last optimizer step."""
-	for ent in _pack_cache.values():
-		ent['dgr_ver'] = None
-		if ent.get('flat') is None:
-			ent['fwd_ver'] = None
-	for cache in (Fold2._cache, _HeadPad._cache, _split_cache):
-		for ent in cache.values():
-			ent['ver'] = None
-
-
-def split_weight(w, dtype, dgrad_planes = 3):
-	"""(forward, dgrad) split operands of a conv parameter for the split-operand path (csrc/split3.hip): hi / lo planes of the fp32 master
-	in the 16-bit type `dtype`, both refreshed by ONE launch when the parameter changed (in place: stable addresses).  dgrad_planes = 1: the
-	dgrad operand is the ordinary 16-bit one (w_hi alone), for layers whose backward runs one product per gradient (cfg['split_hi_bwd'])."""
-	ver = param_version(w)
-	ent = _split_cache.get((id(w), dtype, dgrad_planes))
-	if ent is None:
-		ent = _split_cache[(id(w), dtype, dgrad_planes)] = dict(w = w, ver = None, fwd = None, dgr = None)  # holds `w`: id() stays unique
-	if ent['ver'] != ver:
-		ent['fwd'], ent['dgr'] = ops.pack_weight_split3(w, dtype, out = (ent['fwd'], ent['dgr']), dgrad_planes = dgrad_planes)
-		ent['ver'] = ver
-	return ent['fwd'], ent['dgr']
-
+from . import weights as W
 
 _PLANES_ATTR = '_convasr_planes_only'
 _PLANES_CACHE_ATTR = '_convasr_planes_cache'  # on a REAL fp32 block output that several residual branches read: its planes, split once
@@ -145,127 +41,9 @@ def split_applies(split, dt, spec, Cin, Cout):
 	"""Does a conv of this geometry run as a split-operand conv?  fp32 storage with a 16-bit plane type set, stride 1 and channel counts
 	inside the LDS-DMA kernels' envelope (3 Cin % 64 == 0; the weight gradient's 128-channel tiles take Cin, Cout % 128 == 0 and fall back to the
 	general 16-bit kernel otherwise).  The strided prologue joins through its stride-1 fold (Fold2.plan(split = ...)), a narrow one-tap head as a
-	128-class problem (_HeadPad.split_weight), the one-tap residual branches of a dense block with the tapped output's planes shared by its readers; what
+	128-class problem (weights.head_split_weight), the one-tap residual branches of a dense block with the tapped output's planes shared by its readers; what
 	fits none of these (channel counts outside the envelope) stays on the exact-fp32 kernels."""
 	return split is not None and dt == torch.float32 and spec.stride == 1 and Cin % 64 == 0 and Cout % 8 == 0
-
-
-def structure_epoch():
-	return _structure_epoch[0]
-
-
-# The transposed, tap-flipped dgrad copies of the weights (one ~8 us memory-bound launch per layer and step) depend on nothing but the
-# parameters, and the step has one stretch where most of the chip idles: the CTC alpha / beta recursion, one workgroup per utterance
-# (64 of 256 CUs, ~0.3 ms of dependent steps).  prepack_dgrad_weights() -- called by the network between the decoder and the loss --
-# runs those launches on a side stream there; the first dgrad of the backward pass joins it (join_prepack).
-PREPACK = os.environ.get('CONVASR_NO_PREPACK') != '1'  # A/B hook
-GRAPHS_CAPTURED = [False]  # set by train.GraphedTrainStep at its first capture: from then on an eager step (the warm-up of a new batch shape, a shape beyond max_graphs) makes its dgrad copies on the MAIN stream -- see prepack_dgrad_weights
-_prepack_streams = {}  # device -> [side stream, packs pending on it?]
-
-
-GROUPED_PACK_MIN = int(os.environ.get('CONVASR_GROUPED_PACK_MIN', 32))
-_pack_tables = {}  # (device, dtype, the (src, dst) addresses of the group) -> dict(items = device table, blocks, n); entries live as long as the process: graphs bake their addresses
-
-
-def _pack_group(stale, dtype, refresh = True):
-	"""Which of the `stale` weights' dgrad copies can share the one grouped launch: 16-bit, even channel counts, buffers allocated, packed
-	forward copy current (the arena mirror's segment, or refreshed here when refresh is set)."""
-	group = []
-	# (a grouped launch only for MANY copies: the one launch floods every CU at once -- beside the CTC recursion, whose 64 polling workgroups
-	# it overlaps on the prepack stream, that cost the Wav2Letter step +40 us of CTC time for 18 copies, where 18 small launches cost nothing;
-	# JasperNetLarge's 108 copies drop from 0.83 to 0.24 ms: profiles/r05_ab_rounds_wav2letter.json, r05_config4_kernel_stats.csv)
-	if dtype in ops.HALF_DTYPES and len(stale) >= GROUPED_PACK_MIN:
-		for w in stale:
-			ent = _pack_cache.get((id(w), dtype))
-			if ent is None or ent['dgr'] is None:
-				continue
-			fwd = packed_weight(w, dtype, _lib.PACK_FWD) if refresh else ent['fwd']  # (no launch when the optimizer's 16-bit mirror serves it)
-			Cout, Cin, K = w.shape
-			if fwd is not None and Cout % 2 == 0 and Cin % 2 == 0 and fwd.dtype == dtype:
-				group.append((w, ent, fwd))
-	return group
-
-
-def _pack_table(group, dtype):
-	"""The device-resident item table of a group (rebuilt -- one small host-to-device copy -- only when the set of buffers changed)."""
-	import struct
-	dev = group[0][0].device
-	key = tuple((fwd.data_ptr(), ent['dgr'].data_ptr()) for _, ent, fwd in group)
-	tab = _pack_tables.get((dev, dtype, key))  # one table per set of buffers, never dropped: a captured step graph holds its address (a few KB each)
-	if tab is None:
-		if capturing():
-			raise _lib.ConvasrHipError('the dgrad pack table changed while a step graph is being captured (GraphedTrainStep prewarms it: functional.prewarm_dgrad_pack)')
-		assert _lib.load().convasr_pack_dgrad_item_bytes() == 40
-		blob, first = b'', 0
-		for w, ent, fwd in group:
-			Cout, Cin, K = w.shape
-			blob += struct.pack('<QQiiiiii', fwd.data_ptr(), ent['dgr'].data_ptr(), Cout, Cin, K, ops.cout_pad(Cout), ops.cout_pad(Cin), first)
-			first += K * ((Cout + 63) // 64) * ((Cin + 63) // 64)
-		tab = _pack_tables[(dev, dtype, key)] = dict(key = key, items = torch.frombuffer(bytearray(blob), dtype = torch.uint8).to(dev), blocks = first, n = len(group))
-	return tab
-
-
-def prewarm_dgrad_pack(weights, dtype):
-	"""Build the grouped pack's device table for the weights a training step will re-pack (all of them: every optimizer step makes every
-	copy stale), outside a graph capture -- the capture itself cannot copy a table to the device."""
-	group = _pack_group([w for w in weights], dtype, refresh = False)
-	if group:
-		_pack_table(group, dtype)
-
-
-def _pack_dgrad_many(stale, dtype):
-	"""The transposed dgrad copies of the `stale` weights: ONE launch for all those whose packed forward copy is current and 16-bit (the
-	arena mirror's segments, or a forward pack refreshed here), a launch each for the rest."""
-	group = _pack_group(stale, dtype)
-	grouped = {id(w) for w, _, _ in group}
-	for w in stale:
-		if id(w) not in grouped:
-			packed_weight(w, dtype, _lib.PACK_DGRAD)
-	if not group:
-		return
-	tab = _pack_table(group, dtype)
-	_lib.call('convasr_pack_dgrad_grouped', _lib.ptr(tab['items']), tab['n'], tab['blocks'], _lib.stream_ptr())
-	for w, ent, _ in group:
-		ent['dgr_ver'] = param_version(w)
-
-
-def prepack_dgrad_weights(weights, dtype):
-	if not weights:
-		return
-	dev = weights[0].device
-	join_prepack(dev)  # (a previous step that never reached its backward pass -- a loss skipped on the host -- left its packs unjoined)
-	stale = []
-	for w in weights:
-		ent = _pack_cache.get((id(w), dtype))
-		if ent is None or ent['dgr'] is None:
-			packed_weight(w, dtype, _lib.PACK_DGRAD)  # first use: buffers are allocated (and stay owned) by the main stream
-		elif ent['dgr_ver'] != param_version(w):
-			stale.append(w)
-	if not stale:
-		return
-	# Once step graphs exist in this process, eager steps stay off the prepack stream too: one stream less at the boundary between an eagerly
-	# launched step and a replayed one, where round 6 found a race (profiles/r06_interleave_race.txt).  This alone did not close it -- what does
-	# is the host wait per transition in train.GraphedTrainStep._fence_transition -- but it removed the variant in which the replayed step's
-	# pack nodes rewrote buffers an eager step had just packed on the side stream (scratch/r6_interleave_debug2.py: differing losses in every other
-	# run before, none in 8 after).  Eager steps are the exception once graphs exist, so they simply do not fork.
-	if not PREPACK or GRAPHS_CAPTURED[0]:  # (A/B hook, and what a linear step-graph capture sets: the copies are made on the main stream, still in one launch)
-		_pack_dgrad_many(stale, dtype)
-		return
-	st = _prepack_streams.get(dev)
-	if st is None:
-		st = _prepack_streams[dev] = [torch.cuda.Stream(device = dev), False]
-	side, main = st[0], torch.cuda.current_stream(dev)
-	_lib.stream_wait(side, main)  # the parameters, their 16-bit mirror and every earlier reader of the buffers are ordered before the packs
-	with torch.cuda.stream(side):
-		_pack_dgrad_many(stale, dtype)
-	st[1] = True
-
-
-def join_prepack(device):
-	st = _prepack_streams.get(device)
-	if st is not None and st[1]:
-		_lib.stream_wait(torch.cuda.current_stream(device), st[0])
-		st[1] = False
 
 
 CAPTURING = ops._capturing  # [False]; set by train.GraphedTrainStep while a training step is being captured into a HIP graph: every buffer a captured kernel touches must then be persistent or allocated inside the capture (no module-level / per-stream caches), and double-buffered device state is handed back instead of swapped
@@ -327,58 +105,51 @@ def begin_step(device):
 	_DropoutState.offset = 0
 
 
-def _deliver(params, compute):
-	"""Gradient hand-off for a group of parameters produced by one kernel sequence.
-
-	compute(outs, accumulate) must fill outs[i] (fp32, parameter-shaped; None for parameters that need no gradient).
-	If every live parameter has a gradient arena the kernels write / accumulate there and autograd gets None;
-	otherwise fresh tensors are returned for autograd to accumulate."""
-	live = [p is not None and p.requires_grad for p in params]
-	if not any(live):
-		return [None] * len(params)
-	arenas = [getattr(p, '_convasr_grad', None) if ok else None for p, ok in zip(params, live)]
-	if all(a is not None for a, ok in zip(arenas, live) if ok):
-		fresh = {bool(getattr(p, '_convasr_fresh', True)) for p, ok in zip(params, live) if ok}
-		if len(fresh) != 1:
-			raise _lib.ConvasrHipError('gradient arenas of one layer are out of step (mixed fresh / accumulated state)')
-		compute(arenas, not fresh.pop())
-		for p, ok in zip(params, live):
-			if ok:
-				p._convasr_fresh = False
-				hook = getattr(p, '_convasr_ready', None)
-				if hook is not None:
-					hook(p)
-		return [None] * len(params)
-	outs = [torch.empty_like(p, dtype = torch.float32, memory_format = torch.contiguous_format) if ok else None for p, ok in zip(params, live)]
-	compute(outs, False)
-	return outs
+def _arenas_fresh(params):
+	"""Is the next write into these parameters' gradient arenas the first of the step (True) or an accumulation (False)?  The parameters
+	that one kernel sequence fills must agree: it takes one accumulate flag."""
+	fresh = {bool(getattr(p, '_convasr_fresh', True)) for p in params}
+	if len(fresh) != 1:
+		raise _lib.ConvasrHipError('gradient arenas of one layer are out of step (mixed fresh / accumulated state)')
+	return fresh.pop()
 
 
-def _deliver_many(groups, compute):
-	"""_deliver for several parameter groups (e.g. the (gamma, beta) pairs of a dense block's batch norms) filled by ONE launch:
-	compute(outs, accs) with outs[i] the list of fp32 outputs of group i (None where no gradient is wanted) and accs[i] its accumulate
-	flag.  Returns per group what autograd should get (None for arena parameters)."""
-	outs, accs, ret, arena_groups = [], [], [], []
+def _mark_delivered(params):
+	"""The gradient arenas of `params` hold this backward pass's contribution: later writes of the step accumulate, and whoever waits
+	for the gradients (the data-parallel engine's ready hook) is told."""
+	for p in params:
+		p._convasr_fresh = False
+		hook = getattr(p, '_convasr_ready', None)
+		if hook is not None:
+			hook(p)
+
+
+def _deliver_many(groups, compute, always = False):
+	"""Gradient hand-off for several parameter groups (e.g. the (gamma, beta) pairs of a dense block's batch norms) filled by ONE kernel
+	sequence: compute(outs, accs) must fill outs[i][j] (fp32, parameter-shaped; None for parameters that need no gradient) with accs[i]
+	the accumulate flag of group i.  A group whose live parameters all have a gradient arena is written / accumulated there and autograd
+	gets None; any other group gets fresh tensors, which are returned for autograd to accumulate.  With no live parameter at all compute
+	is not run -- unless `always` is set: the sequence produces more than gradients (the batch-norm backward's coefficients)."""
+	outs, accs, ret, delivered = [], [], [], []
 	for params in groups:
-		live = [p is not None and p.requires_grad for p in params]
-		arenas = [getattr(p, '_convasr_grad', None) if ok else None for p, ok in zip(params, live)]
-		if any(live) and all(a is not None for a, ok in zip(arenas, live) if ok):
-			fresh = {bool(getattr(p, '_convasr_fresh', True)) for p, ok in zip(params, live) if ok}
-			if len(fresh) != 1:
-				raise _lib.ConvasrHipError('gradient arenas of one layer are out of step (mixed fresh / accumulated state)')
-			outs.append(arenas); accs.append(not fresh.pop()); ret.append([None] * len(params)); arena_groups.append((params, live))
+		ok = [p is not None and p.requires_grad for p in params]
+		live = [p for p, k in zip(params, ok) if k]
+		if live and all(getattr(p, '_convasr_grad', None) is not None for p in live):
+			outs.append([p._convasr_grad if k else None for p, k in zip(params, ok)]); accs.append(not _arenas_fresh(live)); ret.append([None] * len(params))
+			delivered += live
 		else:
-			o = [torch.empty_like(p, dtype = torch.float32, memory_format = torch.contiguous_format) if ok else None for p, ok in zip(params, live)]
+			o = [torch.empty_like(p, dtype = torch.float32, memory_format = torch.contiguous_format) if k else None for p, k in zip(params, ok)]
 			outs.append(o); accs.append(False); ret.append(o)
-	compute(outs, accs)
-	for params, live in arena_groups:
-		for p, ok in zip(params, live):
-			if ok:
-				p._convasr_fresh = False
-				hook = getattr(p, '_convasr_ready', None)
-				if hook is not None:
-					hook(p)
+			always = always or bool(live)
+	if delivered or always:
+		compute(outs, accs)
+	_mark_delivered(delivered)
 	return ret
+
+
+def _deliver(params, compute, always = False):
+	"""_deliver_many for one group: compute(outs, accumulate)."""
+	return _deliver_many([params], lambda outs, accs: compute(outs[0], accs[0]), always)[0]
 
 
 GROUP_RES = os.environ.get('CONVASR_NO_GROUPED_RES') != '1'  # A/B hook: a dense block's residual branches in grouped launches + gradient accumulators on the tapped outputs
@@ -409,32 +180,14 @@ def join_side_streams():
 	for dev, side in _side_streams.items():
 		if side is not None:
 			_lib.stream_wait(torch.cuda.current_stream(dev), side)
-	_wgrad_pending.clear()
 	for held in _side_keepalive.values():
 		del held[:]  # (released on the main stream, which has just been ordered behind the side stream's last reader)
-
-
-# WGRAD_AFTER_DGRAD (round 6, with the side stream on): a layer's weight gradient is enqueued on the side stream AFTER the same layer's dgrad and
-# ordered behind it, and the NEXT dgrad of the backward pass waits for it: the two MFMA-bound kernels of a layer never run side by side (that cost
-# the Wav2Letter step 1.5 % in round 3), but the memory-bound BN passes of the next layer (reduce / finalize / apply) run UNDER the weight gradient
-# instead of after it.  Off: the round-3 form -- wgrad enqueued before dgrad, both concurrently.
-WGRAD_AFTER_DGRAD = os.environ.get('CONVASR_WGRAD_AFTER_DGRAD', '0') == '1'
-_wgrad_pending = {}  # device -> a side-stream weight gradient the next dgrad must wait for
-
-
-def _join_pending_wgrad(dev):
-	if _wgrad_pending.pop(dev, False):
-		side = _side_streams.get(dev)
-		if side is not None:
-			torch.cuda.current_stream(dev).wait_stream(side)
 
 
 def _run_wgrad(dev, tensors, fn):
 	side = _side_streams.get(dev)
 	if side is None:
 		return fn()
-	if WGRAD_AFTER_DGRAD:
-		_wgrad_pending[dev] = True
 	_lib.stream_wait(side, torch.cuda.current_stream(dev))
 	with torch.cuda.stream(side):
 		out = fn()
@@ -463,7 +216,6 @@ class Fold2:
 	register-staged kernels took 73 + 161 us per step for 7 % of one big layer's FLOPs.  Needs an even number of input frames (the
 	instance norm in front of the prologue pads its output by one zero frame for this, ops.instnorm(pad_time_to = 2)) and no input
 	gradient (a strided dgrad does not exist here)."""
-	_cache = {}
 	enabled = os.environ.get('CONVASR_NO_FOLD2') != '1'  # tests / A-B runs flip this
 
 	@classmethod
@@ -492,31 +244,6 @@ class Fold2:
 			return False
 		Kf, Pf = ops.fold2_geometry(spec.K, spec.padding)
 		return Tout <= ops.conv_out_len((Tin + 1) // 2, Kf, 1, 1, Pf)
-
-	@classmethod
-	def packed_weight(cls, weight, dt, pad):
-		ver = param_version(weight)
-		ent = cls._cache.get((id(weight), dt))
-		if ent is None:
-			ent = cls._cache[(id(weight), dt)] = dict(w = weight, ver = None, wp = None)
-		if ent['ver'] != ver:
-			ent['wp'] = ops.fold2_pack_weight(weight, dt, pad, out = ent['wp'])
-			ent['ver'] = ver
-		return ent['wp']
-
-	@classmethod
-	def split_weight(cls, weight, split, pad):
-		"""Forward planes [K'][Cout][3 x 2 Cin] of the folded conv of a split-operand network: the fp32 folded weight (convasr_fold2_pack_weight
-		into a tap-major fp32 buffer) split like any other (functional.split_weight's kernel); refreshed per parameter version, in place."""
-		ver = param_version(weight)
-		ent = cls._cache.get((id(weight), 'split', split))
-		if ent is None:
-			ent = cls._cache[(id(weight), 'split', split)] = dict(w = weight, ver = None, wf = None, fwd = None)
-		if ent['ver'] != ver:
-			ent['wf'] = ops.fold2_pack_weight(weight, torch.float32, pad, out = ent['wf'])  # [K'][Cout][2 Cin] fp32 (Cout % 128 == 0: no padded rows)
-			ent['fwd'] = ops.pack_weight_split3(ent['wf'].permute(1, 2, 0), split, out = (ent['fwd'], None), want_dgrad = False)[0]
-			ent['ver'] = ver
-		return ent['fwd']
 
 	@staticmethod
 	def wgrad_split(x3, dy3, weight, spec, Kf, Pf, out, accumulate):
@@ -573,11 +300,7 @@ def _bn_backward_from_g(g, y, gamma, beta, bnp, sums, n):
 	sums into (dgamma, dbeta) and the coefficients of dy = A*g + Bc*y + D, then one streaming kernel applies them."""
 	coef = torch.empty(3 * y.shape[1], dtype = torch.float32, device = y.device)
 	finalize = lambda outs, acc: ops.bn_bwd_finalize(sums, gamma, bnp[0], bnp[1], n, coef = coef, dgamma = outs[0], dbeta = outs[1], accumulate = acc)
-	if (gamma is not None and gamma.requires_grad) or (beta is not None and beta.requires_grad):
-		dgamma, dbeta = _deliver([gamma, beta], finalize)
-	else:
-		finalize([None, None], False)
-		dgamma = dbeta = None
+	dgamma, dbeta = _deliver([gamma, beta], finalize, always = True)  # (always: nobody may want dgamma / dbeta, the apply pass still needs coef)
 	return dgamma, dbeta, ops.bn_act_bwd_apply(g, y, coef, False)
 
 
@@ -592,19 +315,18 @@ def _dgrad(x, dy, weight, spec, dt, link = None, wd = None, split = None, hi = F
 	split: the 16-bit plane type of a split-operand conv -- dy is then its (B, 3 Cout, T) plane tensor (ops.split3, SPLIT_GRAD) and dx is fp32;
 	hi: dy is the dense 16-bit (B, Cout, T) tensor instead and the product is dy x w_hi alone (cfg['split_hi_bwd']), dx still fp32."""
 	pad = spec.dilation * (spec.K - 1) - spec.padding
-	_join_pending_wgrad(dy.device)
 	if split is not None:
 		Cout, Cin, K = weight.shape
 		B, _, Tdy = dy.shape
 		if hi:
-			dx = ops.conv1d(dy, split_weight(weight, split, 1)[1], Cin, spec.K, 1, spec.dilation, pad, out_dtype = torch.float32)
+			dx = ops.conv1d(dy, W.split_weight(weight, split, 1)[1], Cin, spec.K, 1, spec.dilation, pad, out_dtype = torch.float32)
 		else:
-			dx = ops.conv1d(dy, split_weight(weight, split)[1], Cin, spec.K, 1, spec.dilation, pad, out_dtype = torch.float32, work = 2.0 * B * ops.conv_out_len(Tdy, K, 1, spec.dilation, pad) * Cout * Cin * K, family = SPLIT_FAMILY)
+			dx = ops.conv1d(dy, W.split_weight(weight, split)[1], Cin, spec.K, 1, spec.dilation, pad, out_dtype = torch.float32, work = 2.0 * B * ops.conv_out_len(Tdy, K, 1, spec.dilation, pad) * Cout * Cin * K, family = SPLIT_FAMILY)
 		_after_long_launch()
 		return dx
 	Cin = x.shape[1]
-	join_prepack(dy.device)
-	wd = packed_weight(weight, dt, _lib.PACK_DGRAD) if wd is None else wd
+	W.join_prepack(dy.device)
+	wd = W.packed_weight(weight, dt, _lib.PACK_DGRAD) if wd is None else wd
 	if link is not None and dt in ops.HALF_DTYPES and spec.stride == 1:
 		dx = ops.conv1d_dgrad_bn_reduce(dy, wd, Cin, spec.K, spec.dilation, pad, link['y'], link['bnp'][2], link['bnp'][3], link['bnp'][0], link['bnp'][1], link['act'], link['drop'][0], link['drop'][1], link['drop'][2], link['xl'], link['sums'], gate = link.get('gate'), step_key = link['drop'][3])
 		if dx is not None:
@@ -650,20 +372,20 @@ class ConvBnActFunction(torch.autograd.Function):
 			xv, Kf, Pf, Tout = ctx.fold
 			ctx.split = cfg['split']
 			x = ops.split3(xv, ctx.split, ops.SPLIT_INPUT)
-			y = ops.conv1d(x, Fold2.split_weight(weight, ctx.split, spec.padding), Cout, Kf, 1, 1, Pf, out_dtype = torch.float32, stats = stats, Tout = Tout, work = 2.0 * B * Tout * Cout * Cin * spec.K, family = SPLIT_FAMILY)
+			y = ops.conv1d(x, W.fold2_split_weight(weight, ctx.split, spec.padding), Cout, Kf, 1, 1, Pf, out_dtype = torch.float32, stats = stats, Tout = Tout, work = 2.0 * B * Tout * Cout * Cin * spec.K, family = SPLIT_FAMILY)
 			ctx.fold = (Kf, Pf)
 		elif ctx.fold is not None:
 			xv, Kf, Pf, Tout = ctx.fold
-			y = ops.conv1d(xv, Fold2.packed_weight(weight, dt, spec.padding), Cout, Kf, 1, 1, Pf, stats = stats, Tout = Tout, work = 2.0 * B * Tout * Cout * Cin * spec.K)
+			y = ops.conv1d(xv, W.fold2_packed_weight(weight, dt, spec.padding), Cout, Kf, 1, 1, Pf, stats = stats, Tout = Tout, work = 2.0 * B * Tout * Cout * Cin * spec.K)
 			ctx.fold = (Kf, Pf)
 		elif split_applies(cfg.get('split'), dt, spec, Cin, Cout):
 			# split-operand conv (csrc/split3.hip): the fp32 input as three 16-bit planes per frame, read by the LDS-DMA kernel as 3 Cin channels;
 			# the planes, not x, are what backward keeps (the weight gradient reads the same memory as 3 Tin frames of Cin channels)
 			ctx.split = cfg['split']
 			x = planes if planes is not None else ops.split3(x, ctx.split, ops.SPLIT_INPUT)
-			y = ops.conv1d(x, split_weight(weight, ctx.split, 1 if cfg.get('split_hi_bwd') else 3)[0], Cout, spec.K, 1, spec.dilation, spec.padding, out_dtype = torch.float32, stats = stats, work = 2.0 * B * ops.conv_out_len(Tin, spec.K, 1, spec.dilation, spec.padding) * Cout * Cin * spec.K, family = SPLIT_FAMILY)
+			y = ops.conv1d(x, W.split_weight(weight, ctx.split, 1 if cfg.get('split_hi_bwd') else 3)[0], Cout, spec.K, 1, spec.dilation, spec.padding, out_dtype = torch.float32, stats = stats, work = 2.0 * B * ops.conv_out_len(Tin, spec.K, 1, spec.dilation, spec.padding) * Cout * Cin * spec.K, family = SPLIT_FAMILY)
 		else:
-			y = ops.conv1d(x, packed_weight(weight, dt, _lib.PACK_FWD), Cout, spec.K, spec.stride, spec.dilation, spec.padding, stats = stats)
+			y = ops.conv1d(x, W.packed_weight(weight, dt, _lib.PACK_FWD), Cout, spec.K, spec.stride, spec.dilation, spec.padding, stats = stats)
 		Tout = y.shape[2]
 		bnp = ops.bn_finalize(stats, B * Tout, gamma, beta, bn.running_mean, bn.running_var, _momentum(bn), bn.eps, num_batches_tracked = bn.num_batches_tracked)
 
@@ -677,7 +399,7 @@ class ConvBnActFunction(torch.autograd.Function):
 		if GROUP_RES and len(branches) >= 2 and dt in ops.HALF_DTYPES:
 			# all of the block's 1x1 residual convs (+ bias, + BN statistics) in ONE dispatch: same values as a launch each
 			sts = [_stats_buffer(cfg['res_bn'][r], Cout, dev, B, Tout) for r in branches]
-			ys = ops.conv1x1_grouped([res_x[r] for r in branches], [packed_weight(flat_res[5 * r + 1], dt, _lib.PACK_FWD) for r in branches], [Cout] * len(branches), biases = [flat_res[5 * r + 2] for r in branches], stats = sts)
+			ys = ops.conv1x1_grouped([res_x[r] for r in branches], [W.packed_weight(flat_res[5 * r + 1], dt, _lib.PACK_FWD) for r in branches], [Cout] * len(branches), biases = [flat_res[5 * r + 2] for r in branches], stats = sts)
 			if ys is not None:
 				ys, sts = dict(zip(branches, ys)), dict(zip(branches, sts))
 		fin = None
@@ -706,12 +428,12 @@ class ConvBnActFunction(torch.autograd.Function):
 					rx3 = cache.get(_PLANES_CACHE_ATTR)
 					if rx3 is None or rx3.dtype != cfg['split']:
 						rx3 = cache[_PLANES_CACHE_ATTR] = ops.split3(rx, cfg['split'], ops.SPLIT_INPUT)
-					ry = ops.conv1d(rx3, split_weight(rw, cfg['split'], 1 if cfg.get('split_hi_bwd') else 3)[0], Cout, 1, 1, 1, 0, out_dtype = torch.float32, bias = rb, stats = st, work = 2.0 * B * Tout * Cout * rx.shape[1], family = SPLIT_FAMILY)
+					ry = ops.conv1d(rx3, W.split_weight(rw, cfg['split'], 1 if cfg.get('split_hi_bwd') else 3)[0], Cout, 1, 1, 1, 0, out_dtype = torch.float32, bias = rb, stats = st, work = 2.0 * B * Tout * Cout * rx.shape[1], family = SPLIT_FAMILY)
 					res_x[r] = rx3  # (what backward keeps of this branch's input: the weight gradient reads the planes as 3 T frames)
 					res_split[r] = True
 				else:
 					st = _stats_buffer(rbn, Cout, dev, B, Tout)
-					ry = ops.conv1d(rx, packed_weight(rw, dt, _lib.PACK_FWD), Cout, 1, 1, 1, 0, bias = rb, stats = st)
+					ry = ops.conv1d(rx, W.packed_weight(rw, dt, _lib.PACK_FWD), Cout, 1, 1, 1, 0, bias = rb, stats = st)
 				res_y.append(ry)
 				res_bnp.append(ops.bn_finalize(st, B * Tout, rg, rbeta, rbn.running_mean, rbn.running_var, _momentum(rbn), rbn.eps, num_batches_tracked = rbn.num_batches_tracked))
 
@@ -779,11 +501,7 @@ class ConvBnActFunction(torch.autograd.Function):
 			# pass 1 already ran inside the dgrad launch that produced dz: only the per-channel finalize is left
 			coef = torch.empty(3 * Cout, dtype = torch.float32, device = dev)
 			finalize = lambda outs, acc: ops.bn_bwd_finalize(fused_sums, gamma, bnp[0], bnp[1], B * Tout, coef = coef, dgamma = outs[0], dbeta = outs[1], accumulate = acc)
-			if gamma.requires_grad or beta.requires_grad:
-				dgamma, dbeta = _deliver([gamma, beta], finalize)
-			else:
-				finalize([None, None], False)
-				dgamma = dbeta = None
+			dgamma, dbeta = _deliver([gamma, beta], finalize, always = True)
 			dy = ops.bn_act_bwd_apply(dz, y, coef, True, bnp[2], bnp[3], act, xlen = xl, dropout_p = p_drop, seed = seed, offset = offset, gate = ctx.gate, step_key = skey, planes = ctx.split, hi_only = hi)
 			g = rsum_of = None
 		elif n_res == 0:
@@ -791,11 +509,7 @@ class ConvBnActFunction(torch.autograd.Function):
 			# per-channel coefficients, pass 2 recomputes g from dz on the fly: dy = A*g + Bc*y + D
 			coef = torch.empty(3 * Cout, dtype = torch.float32, device = dev)
 			reduce = lambda outs, acc: ops.bn_act_bwd_reduce(dz, y, bnp[2], bnp[3], bnp[0], bnp[1], act, xlen = xl, dropout_p = p_drop, seed = seed, offset = offset, write_g = False, gamma = gamma, coef = coef, dgamma = outs[0], dbeta = outs[1], accumulate = acc, gate = ctx.gate, step_key = skey)
-			if gamma.requires_grad or beta.requires_grad:
-				dgamma, dbeta = _deliver([gamma, beta], reduce)
-			else:
-				reduce([None, None], False)
-				dgamma = dbeta = None
+			dgamma, dbeta = _deliver([gamma, beta], reduce, always = True)
 			dy = ops.bn_act_bwd_apply(dz, y, coef, True, bnp[2], bnp[3], act, xlen = xl, dropout_p = p_drop, seed = seed, offset = offset, gate = ctx.gate, step_key = skey, planes = ctx.split, hi_only = hi)  # (a split-operand conv: dy straight into its planes)
 			g = rsum_of = None
 		else:
@@ -809,7 +523,7 @@ class ConvBnActFunction(torch.autograd.Function):
 				holder = {}
 				def many(outs, accs):
 					holder['g'] = ops.bn_bwd_reduce_many(dz, ctx.gate, p_drop, [t[3] for t in sets], [t[2][0] for t in sets], [t[2][1] for t in sets], [t[0] for t in sets], [coefs[i] for i in range(len(sets))], [o[0] for o in outs], [o[1] for o in outs], accs)
-				dgb = _deliver_many([[gm, bt] for gm, bt, _, _ in sets], many)
+				dgb = _deliver_many([[gm, bt] for gm, bt, _, _ in sets], many, always = True)
 				g = holder['g']
 				dys = ops.bn_bwd_apply_grouped(g, [t[3] for t in sets], [coefs[i] for i in range(len(sets))])
 				(dgamma, dbeta), dy = dgb[0], dys[0]
@@ -835,7 +549,7 @@ class ConvBnActFunction(torch.autograd.Function):
 				coefs = torch.empty(1 + len(bn_idx), 3 * Cout, dtype = torch.float32, device = dev)
 				sets = [(gamma, beta, bnp, sums[:2 * Cout])] + [(ctx.params[3 + 4 * r + 2], ctx.params[3 + 4 * r + 3], res_bnp[r], rsum_of[r]) for r in bn_idx]
 				dgb = _deliver_many([[gm, bt] for gm, bt, _, _ in sets], lambda outs, accs: ops.bn_bwd_finalize_grouped([t[3] for t in sets], [t[0] for t in sets], [t[2][0] for t in sets], [t[2][1] for t in sets], B * Tout,
-					[coefs[i] for i in range(len(sets))], [o[0] for o in outs], [o[1] for o in outs], accs))
+					[coefs[i] for i in range(len(sets))], [o[0] for o in outs], [o[1] for o in outs], accs), always = True)
 				dys = ops.bn_bwd_apply_grouped(g, [y] + [res_y[r] for r in bn_idx], [coefs[i] for i in range(len(sets))])
 				(dgamma, dbeta), dy = dgb[0], dys[0]
 				grouped_bn = {r: (dgb[1 + i][0], dgb[1 + i][1], dys[1 + i]) for i, r in enumerate(bn_idx)}
@@ -865,8 +579,7 @@ class ConvBnActFunction(torch.autograd.Function):
 			wg = lambda: _deliver([weight], lambda outs, acc: Fold2.wgrad(xv, dy, weight, spec, ctx.fold[0], ctx.fold[1], outs[0], acc))
 		else:
 			wg = lambda: _deliver([weight], lambda outs, acc: ops.conv1d_wgrad(x, dy, Cout, spec.K, spec.stride, spec.dilation, spec.padding, outs[0], accumulate = acc))
-		after = WGRAD_AFTER_DGRAD and arena_mode and _side_streams.get(dev) is not None
-		if arena_mode and not after:
+		if arena_mode:
 			# enqueue before dgrad: both only read dy, and the side stream can start while dgrad is still being issued
 			dw, = _run_wgrad(dev, (x, dy), wg)
 		dx = None
@@ -874,8 +587,6 @@ class ConvBnActFunction(torch.autograd.Function):
 			if spec.stride != 1:
 				raise _lib.ConvasrHipError('conv1d dgrad with stride > 1 is not implemented (only the prologue conv is strided and its input needs no gradient)')
 			dx = _dgrad(x, dy, weight, spec, dt, ctx.producer_link, split = ctx.split, hi = hi)
-		if after:
-			dw, = _run_wgrad(dev, (x, dy), wg)  # behind this layer's dgrad on the side stream; the next dgrad waits for it (_join_pending_wgrad)
 		if not arena_mode:
 			dw, = wg()
 
@@ -898,9 +609,9 @@ class ConvBnActFunction(torch.autograd.Function):
 				hi_r = bool(cfg.get('split_hi_bwd'))
 				dry3 = ops.as_cl(dry, sp) if hi_r else ops.split3(dry, sp, ops.SPLIT_GRAD)
 				if need_rx and hi_r:
-					drx = ops.conv1d(dry3, split_weight(rw, sp, 1)[1], cin_r, 1, 1, 1, 0, out_dtype = torch.float32)
+					drx = ops.conv1d(dry3, W.split_weight(rw, sp, 1)[1], cin_r, 1, 1, 1, 0, out_dtype = torch.float32)
 				elif need_rx:
-					drx = ops.conv1d(dry3, split_weight(rw, sp)[1], cin_r, 1, 1, 1, 0, out_dtype = torch.float32, work = 2.0 * B * Tout * Cout * cin_r, family = SPLIT_FAMILY)
+					drx = ops.conv1d(dry3, W.split_weight(rw, sp)[1], cin_r, 1, 1, 1, 0, out_dtype = torch.float32, work = 2.0 * B * Tout * Cout * cin_r, family = SPLIT_FAMILY)
 
 				def res_wgrad3(outs, acc, rx3 = rx, dry3 = dry3, rb = rb, cin_r = cin_r, hi_r = hi_r):
 					if hi_r:
@@ -916,8 +627,8 @@ class ConvBnActFunction(torch.autograd.Function):
 			if need_rx and ctx.res_gacc[r] is not None and rx.shape[1] % 128 == 0 and Cout % 64 == 0:
 				pending.append((r, dry))
 			elif need_rx:
-				join_prepack(dry.device)
-				drx = ops.conv1d(dry, packed_weight(rw, dt, _lib.PACK_DGRAD), rx.shape[1], 1, 1, 1, 0)
+				W.join_prepack(dry.device)
+				drx = ops.conv1d(dry, W.packed_weight(rw, dt, _lib.PACK_DGRAD), rx.shape[1], 1, 1, 1, 0)
 			# The bias of a conv that feeds a train-mode batch norm has an identically zero gradient: dry sums to zero over (b, t) for
 			# every channel (sum of g minus N times its mean, minus mean(g xhat) times sum of xhat = 0).  The reference's autograd
 			# gets rounding noise around 0 from the column sum of dry; here the entry is set to exact zero and the pass is skipped.
@@ -943,20 +654,18 @@ class ConvBnActFunction(torch.autograd.Function):
 		if pending:
 			# the branches' input gradients, all in one dispatch, straight into the tapped outputs' gradient accumulators (first writer of a
 			# step allocates and writes, later ones add): autograd gets None for these inputs
-			join_prepack(dev)
+			W.join_prepack(dev)
 			accs = [ctx.res_gacc[r] for r, _ in pending]
 			fresh = [a['buf'] is None for a in accs]
 			for (r, _), a, fr in zip(pending, accs, fresh):
 				if fr:
 					a['buf'] = ops.empty_cl(B, res_x[r].shape[1], Tout, dt, dev)
-			done = ops.conv1x1_grouped([dry for _, dry in pending], [packed_weight(ctx.params[3 + 4 * r], dt, _lib.PACK_DGRAD) for r, _ in pending], [res_x[r].shape[1] for r, _ in pending], outs = [a['buf'] for a in accs], accumulate = [not fr for fr in fresh])
+			done = ops.conv1x1_grouped([dry for _, dry in pending], [W.packed_weight(ctx.params[3 + 4 * r], dt, _lib.PACK_DGRAD) for r, _ in pending], [res_x[r].shape[1] for r, _ in pending], outs = [a['buf'] for a in accs], accumulate = [not fr for fr in fresh])
 			if done is None:
 				raise _lib.ConvasrHipError('grouped input gradient of the residual branches: a shape left the one-tap kernel\'s envelope between forward and backward')
 		if wg_group:
 			ps = [(ctx.params[3 + 4 * r], ctx.params[3 + 4 * r + 1]) for r, _, _ in wg_group]
-			fresh = [bool(getattr(w, '_convasr_fresh', True)) for w, _ in ps]
-			if any(b is not None and bool(getattr(b, '_convasr_fresh', True)) != fr for (_, b), fr in zip(ps, fresh)):
-				raise _lib.ConvasrHipError('gradient arenas of one residual branch are out of step (mixed fresh / accumulated state)')
+			fresh = [_arenas_fresh([p_ for p_ in wb if p_ is not None]) for wb in ps]
 
 			def run():
 				# a fresh bias gradient is zeroed by the combine kernel (no flag to go stale: every step rewrites it); an accumulated one gets += 0
@@ -967,14 +676,10 @@ class ConvBnActFunction(torch.autograd.Function):
 				_run_wgrad(dev, tuple(t for _, rx, dry in wg_group for t in (rx, dry)), run)
 			else:
 				run()
-			for w, b in ps:
-				for p_ in (w, b):
-					if p_ is not None:
-						p_._convasr_fresh = False
-						p_._convasr_grad_is_zero = False
-						hook = getattr(p_, '_convasr_ready', None)
-						if hook is not None:
-							hook(p_)
+			filled = [p_ for wb in ps for p_ in wb if p_ is not None]
+			for p_ in filled:
+				p_._convasr_grad_is_zero = False  # (the combine kernel zeroes the bias gradient itself: the note the single-branch path keeps would go stale)
+			_mark_delivered(filled)
 		return (None, dx, dw, dgamma, dbeta, None, *res_grads)
 
 
@@ -998,9 +703,6 @@ def _stats_buffer(bn, C, dev, B, Tout, slot = '_convasr_stats'):
 	return st
 
 
-HEAD_PAD = 128  # channels the gradient of a narrow 1x1 head is padded to in backward
-
-
 class _HeadPad:
 	"""Backward of a 1x1 conv head with a ragged class count (the 38-class decoder, models.py:26) through the LDS-DMA kernels: the
 	head's output gradient is converted to the 16-bit storage type into a zero-padded (B, 128, T) tensor, the head's weight is transposed into a
@@ -1008,39 +710,6 @@ class _HeadPad:
 	rows 38.. of the padded weight gradient are dropped).  The general register-staged kernels took 61 + 109 us per step for the
 	3.75 GFLOP involved; these are memory-bound launches of ~30 / ~45 us, and the dgrad can carry the BN-backward sums of the last
 	encoder layer in its epilogue like every other dgrad."""
-	_cache = {}
-
-	@classmethod
-	def dgrad_weight(cls, weight, dt):
-		Cout, Cin, K = weight.shape
-		ver = param_version(weight)
-		ent = cls._cache.get((id(weight), dt))
-		if ent is None:
-			ent = cls._cache[(id(weight), dt)] = dict(w = weight, ver = None, wd = torch.zeros(1, ops.cout_pad(Cin), HEAD_PAD, dtype = dt, device = weight.device))
-		if ent['ver'] != ver:
-			src = weight.detach()
-			# wd[0][ci][co] = w[co][ci][0]: the layout kernel reads (C = co, T = ci) and writes it channels-last with a row pitch of 128
-			_lib.call('convasr_convert_layout', _lib.ptr(src), _lib.F32, 0, src.stride(0), src.stride(1), _lib.ptr(ent['wd']), _lib.dtype_code(dt), 0, 1, HEAD_PAD, 1, Cout, Cin, _lib.stream_ptr())
-			ent['ver'] = ver
-		return ent['wd']
-
-	@classmethod
-	def split_weight(cls, weight, split, dgrad_planes = 3):
-		"""(forward, dgrad) planes of a narrow one-tap head in a split-operand network, as 128-class operands: the fp32 weight is copied into the
-		live rows of a zero-padded (128, Cin, 1) fp32 buffer and split like any other weight; refreshed per parameter version, in place.
-		dgrad_planes = 1: the dgrad operand as the ordinary 16-bit one (a one-product backward, functional.split_weight)."""
-		Cout, Cin, K = weight.shape
-		ver = param_version(weight)
-		ent = cls._cache.get((id(weight), 'split', split, dgrad_planes))
-		if ent is None:
-			ent = cls._cache[(id(weight), 'split', split, dgrad_planes)] = dict(w = weight, ver = None, wp = torch.zeros(HEAD_PAD, Cin, 1, dtype = torch.float32, device = weight.device), fwd = None, dgr = None)
-		if ent['ver'] != ver:
-			src, wp = weight.detach(), ent['wp']
-			_lib.call('convasr_convert_layout', _lib.ptr(src), _lib.F32, 0, src.stride(0), src.stride(1), _lib.ptr(wp), _lib.F32, 0, wp.stride(0), wp.stride(1), 1, Cout, Cin, _lib.stream_ptr())
-			ent['fwd'], ent['dgr'] = ops.pack_weight_split3(wp, split, out = (ent['fwd'], ent['dgr']), dgrad_planes = dgrad_planes)
-			ent['ver'] = ver
-		return ent['fwd'], ent['dgr']
-
 	_pad_bufs = {}
 
 	@classmethod
@@ -1052,11 +721,11 @@ class _HeadPad:
 		key = (B, T, Cout, dt, dy.device, torch.cuda.current_stream(dy.device).cuda_stream)
 		out = None if CAPTURING[0] else cls._pad_bufs.get(key)
 		if CAPTURING[0]:
-			out = ops.zeros_cl(B, HEAD_PAD, T, dt, dy.device)  # (inside a capture: the graph's own buffer, zero-filled at every replay -- by a fill KERNEL node: torch.zeros records no memset node, train.capture_node_kinds)
+			out = ops.zeros_cl(B, W.HEAD_PAD, T, dt, dy.device)  # (inside a capture: the graph's own buffer, zero-filled at every replay -- by a fill KERNEL node: torch.zeros records no memset node, train.capture_node_kinds)
 		elif out is None:
 			if len(cls._pad_bufs) >= 64:
 				cls._pad_bufs.clear()  # mixed-length training: one entry per padded length; bounded
-			out = cls._pad_bufs[key] = ops.zeros_cl(B, HEAD_PAD, T, dt, dy.device)
+			out = cls._pad_bufs[key] = ops.zeros_cl(B, W.HEAD_PAD, T, dt, dy.device)
 		_lib.call('convasr_convert_layout', _lib.ptr(dy), _lib.dtype_code(dy.dtype), dy.stride(0), dy.stride(1), dy.stride(2), _lib.ptr(out), _lib.dtype_code(dt), out.stride(0), out.stride(1), out.stride(2), B, Cout, T, _lib.stream_ptr())
 		return out
 
@@ -1071,15 +740,15 @@ class ConvBiasFunction(torch.autograd.Function):
 		x = ops.as_cl(x, dt)
 		Cout, Cin, K = weight.shape
 		ctx.split = None
-		if cfg.get('split') is not None and dt == torch.float32 and K == 1 and spec.stride == 1 and spec.padding == 0 and Cin % 128 == 0 and Cout <= HEAD_PAD and os.environ.get('CONVASR_NO_HEAD_PAD') != '1':
+		if cfg.get('split') is not None and dt == torch.float32 and K == 1 and spec.stride == 1 and spec.padding == 0 and Cin % 128 == 0 and Cout <= W.HEAD_PAD and os.environ.get('CONVASR_NO_HEAD_PAD') != '1':
 			# the head of a split-operand network: the input's planes against the planes of the weight padded to 128 classes (rows >= Cout are zero
 			# and the kernel stores the Cout live columns only); backward runs dgrad / wgrad as 128-class split problems like _HeadPad's 16-bit form
 			ctx.split = cfg['split']
 			B, _, T = x.shape
 			x = ops.split3(x, ctx.split, ops.SPLIT_INPUT)
-			y = ops.conv1d(x, _HeadPad.split_weight(weight, ctx.split, 1 if cfg.get('split_hi_bwd') else 3)[0], Cout, 1, 1, 1, 0, out_dtype = cfg.get('out_dtype', torch.float32), bias = bias, work = 2.0 * B * T * Cout * Cin, family = SPLIT_FAMILY)
+			y = ops.conv1d(x, W.head_split_weight(weight, ctx.split, 1 if cfg.get('split_hi_bwd') else 3)[0], Cout, 1, 1, 1, 0, out_dtype = cfg.get('out_dtype', torch.float32), bias = bias, work = 2.0 * B * T * Cout * Cin, family = SPLIT_FAMILY)
 		else:
-			y = ops.conv1d(x, packed_weight(weight, dt, _lib.PACK_FWD), weight.shape[0], spec.K, spec.stride, spec.dilation, spec.padding, out_dtype = cfg.get('out_dtype', torch.float32), bias = bias)
+			y = ops.conv1d(x, W.packed_weight(weight, dt, _lib.PACK_FWD), weight.shape[0], spec.K, spec.stride, spec.dilation, spec.padding, out_dtype = cfg.get('out_dtype', torch.float32), bias = bias)
 		ctx.cfg = cfg
 		ctx.params = (weight, bias)
 		ctx.save_for_backward(x)
@@ -1100,18 +769,18 @@ class ConvBiasFunction(torch.autograd.Function):
 			dy3 = _HeadPad.pad_grad(dy, ctx.split) if hi else ops.split3(_HeadPad.pad_grad(dy, torch.float32), ctx.split, ops.SPLIT_GRAD)  # (B, 3 x 128, T): the padded classes are zero planes
 			dx = None
 			if ctx.needs_input_grad[1] and hi:
-				dx = ops.conv1d(dy3, _HeadPad.split_weight(weight, ctx.split, 1)[1], Cin, 1, 1, 1, 0, out_dtype = torch.float32, work = 2.0 * B * T * Cout * Cin)
+				dx = ops.conv1d(dy3, W.head_split_weight(weight, ctx.split, 1)[1], Cin, 1, 1, 1, 0, out_dtype = torch.float32, work = 2.0 * B * T * Cout * Cin)
 				_after_long_launch()
 			elif ctx.needs_input_grad[1]:
-				dx = ops.conv1d(dy3, _HeadPad.split_weight(weight, ctx.split)[1], Cin, 1, 1, 1, 0, out_dtype = torch.float32, work = 2.0 * B * T * Cout * Cin, family = SPLIT_FAMILY)
+				dx = ops.conv1d(dy3, W.head_split_weight(weight, ctx.split)[1], Cin, 1, 1, 1, 0, out_dtype = torch.float32, work = 2.0 * B * T * Cout * Cin, family = SPLIT_FAMILY)
 				_after_long_launch()
 
 			def wgrad3(outs, acc):
-				dwp = torch.empty(HEAD_PAD, Cin, 1, dtype = torch.float32, device = dy.device)
+				dwp = torch.empty(W.HEAD_PAD, Cin, 1, dtype = torch.float32, device = dy.device)
 				if hi:
-					ops.conv1d_wgrad_hi(x, dy3, HEAD_PAD, 1, 1, 0, dwp, work = 2.0 * B * T * Cout * Cin)
+					ops.conv1d_wgrad_hi(x, dy3, W.HEAD_PAD, 1, 1, 0, dwp, work = 2.0 * B * T * Cout * Cin)
 				else:
-					ops.conv1d_wgrad(ops.split3_frames(x), ops.split3_frames(dy3), HEAD_PAD, 1, 1, 3, 0, dwp, work = 2.0 * B * T * Cout * Cin, family = SPLIT_WGRAD_FAMILY)
+					ops.conv1d_wgrad(ops.split3_frames(x), ops.split3_frames(dy3), W.HEAD_PAD, 1, 1, 3, 0, dwp, work = 2.0 * B * T * Cout * Cin, family = SPLIT_WGRAD_FAMILY)
 				if outs[0] is not None:
 					v = dwp[:Cout]
 					if acc:
@@ -1122,14 +791,14 @@ class ConvBiasFunction(torch.autograd.Function):
 					ops.colsum(dy, outs[1], accumulate = acc)  # the bias gradient: the sum of dy itself, not of its planes
 			dw, db = _deliver([weight, bias], wgrad3)
 			return None, dx, dw, db
-		if dt in ops.HALF_DTYPES and spec.K == 1 and spec.stride == 1 and spec.padding == 0 and Cout < HEAD_PAD and x.shape[1] % 128 == 0 and os.environ.get('CONVASR_NO_HEAD_PAD') != '1':
+		if dt in ops.HALF_DTYPES and spec.K == 1 and spec.stride == 1 and spec.padding == 0 and Cout < W.HEAD_PAD and x.shape[1] % 128 == 0 and os.environ.get('CONVASR_NO_HEAD_PAD') != '1':
 			dyp = _HeadPad.pad_grad(dy, dt)
-			dx = _dgrad(x, dyp, weight, spec, dt, ctx.producer_link, wd = _HeadPad.dgrad_weight(weight, dt)) if ctx.needs_input_grad[1] else None
+			dx = _dgrad(x, dyp, weight, spec, dt, ctx.producer_link, wd = W.head_dgrad_weight(weight, dt)) if ctx.needs_input_grad[1] else None
 
 			def wgrad(outs, acc):
-				dwp = torch.empty(HEAD_PAD, x.shape[1], 1, dtype = torch.float32, device = x.device)
-				dbp = torch.empty(HEAD_PAD, dtype = torch.float32, device = x.device) if outs[1] is not None else None
-				ops.conv1d_wgrad(x, dyp, HEAD_PAD, 1, 1, 1, 0, dwp, dbias = dbp)
+				dwp = torch.empty(W.HEAD_PAD, x.shape[1], 1, dtype = torch.float32, device = x.device)
+				dbp = torch.empty(W.HEAD_PAD, dtype = torch.float32, device = x.device) if outs[1] is not None else None
+				ops.conv1d_wgrad(x, dyp, W.HEAD_PAD, 1, 1, 1, 0, dwp, dbias = dbp)
 				for o, v in ((outs[0], dwp[:Cout]), (outs[1], None if dbp is None else dbp[:Cout].view(Cout, 1, 1))):
 					if o is None:
 						continue
@@ -1193,14 +862,14 @@ class ConvBnActEvalFunction:
 		split = cfg.get('split_eval')  # (inference on the split-operand path: JasperNet.set_compute_dtype('bf16x3', inference = True))
 		if fold is not None:
 			xv, Kf, Pf, Tout = fold
-			conv = lambda **epilogue: ops.conv1d(xv, Fold2.packed_weight(weight, dt, spec.padding), Cout, Kf, 1, 1, Pf, bias = bias, Tout = Tout, work = 2.0 * x.shape[0] * Tout * Cout * x.shape[1] * spec.K, splitk = sk, **epilogue)
+			conv = lambda **epilogue: ops.conv1d(xv, W.fold2_packed_weight(weight, dt, spec.padding), Cout, Kf, 1, 1, Pf, bias = bias, Tout = Tout, work = 2.0 * x.shape[0] * Tout * Cout * x.shape[1] * spec.K, splitk = sk, **epilogue)
 		elif split_applies(split, dt, spec, x.shape[1], Cout):
 			# fp32 activations, the conv as hi*hi + hi*lo + lo*hi on the 16-bit matrix pipe (csrc/split3.hip): bias / folded BN / activation / mask in
 			# the conv's own epilogue as on every other path; the weights' planes are packed once per parameter version
-			x3, wp3 = ops.split3(x, split, ops.SPLIT_INPUT), split_weight(weight, split)[0]
+			x3, wp3 = ops.split3(x, split, ops.SPLIT_INPUT), W.split_weight(weight, split)[0]
 			conv = lambda **epilogue: ops.conv1d(x3, wp3, Cout, spec.K, 1, spec.dilation, spec.padding, out_dtype = torch.float32, bias = bias, work = 2.0 * x.shape[0] * ops.conv_out_len(x.shape[2], spec.K, 1, spec.dilation, spec.padding) * Cout * x.shape[1] * spec.K, family = SPLIT_FAMILY, splitk = sk, **epilogue)
 		else:
-			wp = packed_weight(weight, dt, _lib.PACK_FWD)
+			wp = W.packed_weight(weight, dt, _lib.PACK_FWD)
 			conv = lambda **epilogue: ops.conv1d(x, wp, Cout, spec.K, spec.stride, spec.dilation, spec.padding, bias = bias, splitk = sk, **epilogue)  # (splitk: a launch of a few tiles -- one online request -- is cut over the input channels, ops.conv1d)
 		# dropout > 0 here means a FROZEN block (JasperNet.freeze, models.py:328-339): its batch norms run on their running statistics
 		# but the block is still in training mode, and the reference's ResidualActivation applies dropout by self.training (models.py:365-369)
@@ -1214,10 +883,10 @@ class ConvBnActEvalFunction:
 			if rw is None:
 				res_y.append(rx); rscale.append(None); rshift.append(None)
 			elif split_applies(split, dt, ConvSpec(1), rx.shape[1], Cout):
-				res_y.append(ops.conv1d(ops.split3(rx, split, ops.SPLIT_INPUT), split_weight(rw, split)[0], Cout, 1, 1, 1, 0, out_dtype = torch.float32, bias = rb, work = 2.0 * rx.shape[0] * rx.shape[2] * Cout * rx.shape[1], family = SPLIT_FAMILY, splitk = sk))
+				res_y.append(ops.conv1d(ops.split3(rx, split, ops.SPLIT_INPUT), W.split_weight(rw, split)[0], Cout, 1, 1, 1, 0, out_dtype = torch.float32, bias = rb, work = 2.0 * rx.shape[0] * rx.shape[2] * Cout * rx.shape[1], family = SPLIT_FAMILY, splitk = sk))
 				rscale.append(None if rss is None else rss[0]); rshift.append(None if rss is None else rss[1])
 			else:
-				res_y.append(ops.conv1d(rx, packed_weight(rw, dt, _lib.PACK_FWD), Cout, 1, 1, 1, 0, bias = rb, splitk = sk))
+				res_y.append(ops.conv1d(rx, W.packed_weight(rw, dt, _lib.PACK_FWD), Cout, 1, 1, 1, 0, bias = rb, splitk = sk))
 				rscale.append(None if rss is None else rss[0]); rshift.append(None if rss is None else rss[1])
 		# rscale None (identity residual, or a residual conv already fused with its BN) means "add as is"
 		seed, offset = _DropoutState.next(y.numel()) if p_drop > 0 else (0, 0)
@@ -1251,7 +920,7 @@ class ConvBnActFrozenStatsFunction(torch.autograd.Function):
 		dev = x.device
 		Cout = weight.shape[0]
 		xl = ops.xlen_f32(xlen, dev) if (cfg['temporal_mask'] and xlen is not None) else None
-		y = ops.conv1d(x, packed_weight(weight, dt, _lib.PACK_FWD), Cout, spec.K, spec.stride, spec.dilation, spec.padding, bias = bias)
+		y = ops.conv1d(x, W.packed_weight(weight, dt, _lib.PACK_FWD), Cout, spec.K, spec.stride, spec.dilation, spec.padding, bias = bias)
 		aff = ConvBnActFrozenStatsFunction._affine(cfg['bn'], gamma, beta)
 		n_res = len(flat_res) // 5
 		res_x, res_y, res_aff = [], [], []
@@ -1262,7 +931,7 @@ class ConvBnActFrozenStatsFunction(torch.autograd.Function):
 			if rw is None:
 				res_y.append(rx); res_aff.append((None, None, None, None))
 			else:
-				res_y.append(ops.conv1d(rx, packed_weight(rw, dt, _lib.PACK_FWD), Cout, 1, 1, 1, 0, bias = rb))
+				res_y.append(ops.conv1d(rx, W.packed_weight(rw, dt, _lib.PACK_FWD), Cout, 1, 1, 1, 0, bias = rb))
 				res_aff.append(ConvBnActFrozenStatsFunction._affine(cfg['res_bn'][r], rg, rbeta))
 		p_drop = cfg['dropout_p']
 		seed, offset = _DropoutState.next(y.numel()) if p_drop > 0 else (0, 0)
@@ -1336,8 +1005,8 @@ class ConvBnActFrozenStatsFunction(torch.autograd.Function):
 							o.add_(v.float()) if acc else o.copy_(v.float())
 				drg, drbeta = _deliver([rg, rbeta], put)
 			dry = g if rscale is None else ops.bn_act_bwd_apply(g, res_y[r], ConvBnActFrozenStatsFunction._coef(rscale, Cout, dev), False)
-			join_prepack(dev)
-			drx = ops.conv1d(dry, packed_weight(rw, dt, _lib.PACK_DGRAD), res_x[r].shape[1], 1, 1, 1, 0) if need_rx else None
+			W.join_prepack(dev)
+			drx = ops.conv1d(dry, W.packed_weight(rw, dt, _lib.PACK_DGRAD), res_x[r].shape[1], 1, 1, 1, 0) if need_rx else None
 			if rb is not None:
 				rb._convasr_grad_is_zero = False  # a real bias gradient lands in the arena segment: the train-mode path (ConvBnActFunction) must zero it again
 			drw, drb = _deliver([rw, rb], lambda outs, acc, rx = res_x[r], dry = dry: ops.conv1d_wgrad(rx, dry, Cout, 1, 1, 1, 0, outs[0], dbias = outs[1], accumulate = acc))

@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import ops, _lib
 from . import functional as Fn
+from . import weights as W
 from .functional import ConvSpec
 
 FP16_TINY = float(torch.finfo(torch.float16).tiny)
@@ -350,7 +351,7 @@ class ConvBn1d(nn.Module):
 			self.conv_residual[r], self.bn_residual[r] = fold(rc, rbn), nn.Identity()
 		for r, (seq, bn) in enumerate(zip(self.conv, self.bn)):
 			seq[-1], self.bn[r] = fold(seq[-1], bn), nn.Identity()
-		Fn.invalidate_pack_cache()
+		W.invalidate_pack_cache()
 
 
 class Decoder(nn.Sequential):
@@ -485,13 +486,13 @@ class JasperNet(nn.Module):
 
 		logits = self.decoder(x)
 		if y is not None and ylen is not None and self.training and torch.is_grad_enabled():
-			# the backward pass's transposed weight copies, on a side stream under the CTC recursion that follows (functional.prepack_dgrad_weights)
+			# the backward pass's transposed weight copies, on a side stream under the CTC recursion that follows (weights.prepack_dgrad_weights)
 			cached = getattr(self, '_dgrad_weights', None)
-			if cached is None or cached[0] != Fn.structure_epoch():  # (the module tree is walked once, not per step: any fuse_conv_bn_eval -- the network's or a single block's -- replaces conv modules and bumps the epoch)
+			if cached is None or cached[0] != W.structure_epoch():  # (the module tree is walked once, not per step: any fuse_conv_bn_eval -- the network's or a single block's -- replaces conv modules and bumps the epoch)
 				convs = [c[-1] for blk in self.modules() if isinstance(blk, ConvBn1d) for c in blk.conv] + [c for blk in self.modules() if isinstance(blk, ConvBn1d) for c in blk.conv_residual if isinstance(c, nn.Conv1d)]
-				cached = self._dgrad_weights = (Fn.structure_epoch(), [c.weight for c in convs[1:] if c.stride[0] == 1])
-			if self.split_dtype is None:  # (a split-operand network packs both operands of a conv in one launch at its forward pass: functional.split_weight)
-				Fn.prepack_dgrad_weights(cached[1], self.compute_dtype)
+				cached = self._dgrad_weights = (W.structure_epoch(), [c.weight for c in convs[1:] if c.stride[0] == 1])
+			if self.split_dtype is None:  # (a split-operand network packs both operands of a conv in one launch at its forward pass: weights.split_weight)
+				W.prepack_dgrad_weights(cached[1], self.compute_dtype)
 		log_probs = [Fn.LogSoftmaxFunction.apply(l) for l in logits]
 		olen = [ops.output_lengths(xlen, l.shape[0], l.shape[-1], l.device) for l in logits]  # compute_output_lengths (models.py:611-614) as one launch
 		aux = {}

@@ -151,16 +151,23 @@ def weight_layout(w):
 	return None
 
 
-def pack_weight(w, dtype, mode = None, out = None, fwd_is_current = False):
-	"""(Cout, Cin, K) fp32 parameter -> packed [K][rows_pad][cols] tensor(s) for the MFMA kernels.
-	mode PACK_FWD returns the forward layout, PACK_DGRAD the dgrad layout, None both (fwd, dgrad).  `out` = (fwd, dgrad)
-	buffers from an earlier call are refreshed in place (stable addresses, no re-allocation per optimizer step).
-	fwd_is_current: out[0] already holds the parameter's packed forward copy (the optimizer's bf16 mirror): only dgrad is rebuilt."""
+def _fp32_with_layout(w):
+	"""A parameter as the packing kernels read it: (detached fp32 tensor, its layout code) -- the parameter's own memory when it is fp32
+	in one of the two layouts the kernels know (weight_layout), a contiguous fp32 copy otherwise."""
 	require_cuda(w)
 	w = w.detach()
 	layout = weight_layout(w) if w.dtype == torch.float32 else None
 	if layout is None:
 		w, layout = w.float().contiguous(), _lib.W_REFERENCE
+	return w, layout
+
+
+def pack_weight(w, dtype, mode = None, out = None, fwd_is_current = False):
+	"""(Cout, Cin, K) fp32 parameter -> packed [K][rows_pad][cols] tensor(s) for the MFMA kernels.
+	mode PACK_FWD returns the forward layout, PACK_DGRAD the dgrad layout, None both (fwd, dgrad).  `out` = (fwd, dgrad)
+	buffers from an earlier call are refreshed in place (stable addresses, no re-allocation per optimizer step).
+	fwd_is_current: out[0] already holds the parameter's packed forward copy (the optimizer's bf16 mirror): only dgrad is rebuilt."""
+	w, layout = _fp32_with_layout(w)
 	Cout, Cin, K = w.shape
 	fwd, dgr = out if out is not None else (None, None)
 	if fwd is None:
@@ -184,14 +191,20 @@ def conv_out_len(Tin, K, stride, dil, pad):
 	return (Tin + 2 * pad - dil * (K - 1) - 1) // stride + 1
 
 
-_max_rows_cache = {}
+_queries = {}
+
+
+def _cached_query(name, *args):
+	"""The library's answer to a pure question about integer arguments (a row count, a workspace size, "is this shape inside the kernel's
+	envelope?"), asked once per distinct arguments.  Unbounded: one entry per shape the process meets."""
+	r = _queries.get((name, ) + args)
+	if r is None:
+		r = _queries[(name, ) + args] = getattr(_lib.load(), name)(*args)
+	return r
 
 
 def _conv_stats_max_rows(B, Tout):
-	r = _max_rows_cache.get((B, Tout))
-	if r is None:
-		r = _max_rows_cache[(B, Tout)] = _lib.load().convasr_conv_stats_max_rows(B, Tout)
-	return r
+	return _cached_query('convasr_conv_stats_max_rows', B, Tout)
 
 
 class ConvStats:
@@ -354,11 +367,7 @@ def fold2_geometry(K, pad):
 
 def fold2_pack_weight(w, dtype, pad, out = None):
 	"""(Cout, Cin, K) fp32 parameter -> packed forward operand [K'][cout_pad][2 Cin] of the folded conv (refreshed in place if given)."""
-	require_cuda(w)
-	w = w.detach()
-	layout = weight_layout(w) if w.dtype == torch.float32 else None
-	if layout is None:
-		w, layout = w.float().contiguous(), _lib.W_REFERENCE
+	w, layout = _fp32_with_layout(w)
 	Cout, Cin, K = w.shape
 	if out is None:
 		out = torch.empty(fold2_geometry(K, pad)[0], cout_pad(Cout), 2 * Cin, dtype = dtype, device = w.device)
@@ -414,35 +423,16 @@ def conv1d_wgrad_hi(x3, dy, Cout, K, dil, pad, dw, accumulate = False, work = No
 	Cin, Tout = C3 // 3, dy.shape[2]
 	layout = weight_layout(dw)
 	assert is_cl(x3) and is_cl(dy) and x3.dtype == dy.dtype and x3.dtype in HALF_DTYPES and layout is not None and dw.dtype == torch.float32 and tuple(dw.shape) == (Cout, Cin, K), (dw.shape, dw.stride())
-	skey = (x3.dtype, B, Cin, Cout, Tin, Tout, K, dil)
-	ok = _wgrad_ld_ok.get(skey)
-	if ok is None:
-		ok = _wgrad_ld_ok[skey] = bool(_lib.load().convasr_conv1d_wgrad_ld_supported(dtype_code(x3.dtype), B, Cin, Cout, Tin, Tout, K, dil, C3, Cout))
-	if not ok:  # outside the LDS-DMA kernel's envelope (channel counts not multiples of 128, a tap window too wide for its LDS ring): a dense copy of the plane
+	if not _cached_query('convasr_conv1d_wgrad_ld_supported', dtype_code(x3.dtype), B, Cin, Cout, Tin, Tout, K, dil, C3, Cout):  # outside the LDS-DMA kernel's envelope (channel counts not multiples of 128, a tap window too wide for its LDS ring): a dense copy of the plane
 		return conv1d_wgrad(split3_plane(x3), dy, Cout, K, 1, dil, pad, dw, accumulate = accumulate, work = work, family = family)
-	if K == 1 and (Cout * Cin) % 4 == 0:
-		layout = _lib.W_KMAJOR
-	wkey = (B, Cin, Cout, Tin, Tout, K, 1, dil)
-	nbytes = _wgrad_ws_bytes.get(wkey)
-	if nbytes is None:
-		nbytes = _wgrad_ws_bytes[wkey] = _lib.load().convasr_conv1d_wgrad_workspace_bytes(*wkey)
-	ws = workspace(nbytes, x3.device, 'wgrad')
-	_lib.timed(family or 'conv1d_wgrad', 2.0 * B * Tout * Cout * Cin * K if work is None else work, lambda: call('convasr_conv1d_wgrad_ld', ptr(x3), C3, ptr(dy), Cout, ptr(dw), ptr(ws), dtype_code(dy.dtype), B, Cin, Cout, Tin, Tout, K, dil, pad, int(accumulate), layout, stream_ptr()))
-	return dw
-
-
-_wgrad_ld_ok = {}
+	return _wgrad_launch(dw, layout, (B, Cin, Cout, Tin, Tout, K, 1, dil), work, family, lambda ws, layout: call('convasr_conv1d_wgrad_ld', ptr(x3), C3, ptr(dy), Cout, ptr(dw), ptr(ws), dtype_code(dy.dtype), B, Cin, Cout, Tin, Tout, K, dil, pad, int(accumulate), layout, stream_ptr()))
 
 
 def pack_weight_split3(w, dtype, out = None, want_dgrad = True, dgrad_planes = 3):
 	"""(Cout, Cin, K) fp32 parameter -> (fwd [K][cout_pad][3 Cin], dgrad [K][cin_pad][3 Cout]) split operands, refreshed in place when
 	`out` = (fwd, dgrad) of an earlier call.  want_dgrad = False: the forward planes only (dgrad is returned as None).  dgrad_planes = 1: the
 	dgrad operand as the ordinary 16-bit one, [K][cin_pad][Cout] (w_hi alone: a one-product backward)."""
-	require_cuda(w)
-	w = w.detach()
-	layout = weight_layout(w) if w.dtype == torch.float32 else None
-	if layout is None:
-		w, layout = w.float().contiguous(), _lib.W_REFERENCE
+	w, layout = _fp32_with_layout(w)
 	Cout, Cin, K = w.shape
 	fwd, dgr = out if out is not None else (None, None)
 	if fwd is None:
@@ -463,7 +453,15 @@ def colsum(y, out, accumulate = False):
 	return out
 
 
-_wgrad_ws_bytes = {}
+def _wgrad_launch(dw, layout, geometry, work, family, launch):
+	"""What the weight-gradient launches share: the layout override for one tap, the split-K workspace of the geometry
+	(B, Cin, Cout, Tin, Tout, K, stride, dil) and the timed launch(ws, layout).  Returns dw."""
+	B, Cin, Cout, Tin, Tout, K, stride, dil = geometry
+	if K == 1 and (Cout * Cin) % 4 == 0:
+		layout = _lib.W_KMAJOR  # one tap: the two layouts are the same memory, and the tap-major combine is the streaming one
+	ws = workspace(_cached_query('convasr_conv1d_wgrad_workspace_bytes', *geometry), dw.device, 'wgrad')
+	_lib.timed(family or 'conv1d_wgrad', 2.0 * B * Tout * Cout * Cin * K if work is None else work, lambda: launch(ws, layout))
+	return dw
 
 
 def conv1d_wgrad(x, dy, Cout, K, stride, dil, pad, dw, dbias = None, accumulate = False, work = None, family = None):
@@ -473,15 +471,7 @@ def conv1d_wgrad(x, dy, Cout, K, stride, dil, pad, dw, dbias = None, accumulate 
 	Tout = dy.shape[2]
 	layout = weight_layout(dw)
 	assert is_cl(x) and is_cl(dy) and x.dtype == dy.dtype and layout is not None and dw.dtype == torch.float32 and tuple(dw.shape) == (Cout, Cin, K), (dw.shape, dw.stride())
-	if K == 1 and (Cout * Cin) % 4 == 0:
-		layout = _lib.W_KMAJOR  # one tap: the two layouts are the same memory, and the tap-major combine is the streaming one
-	wkey = (B, Cin, Cout, Tin, Tout, K, stride, dil)
-	nbytes = _wgrad_ws_bytes.get(wkey)
-	if nbytes is None:
-		nbytes = _wgrad_ws_bytes[wkey] = _lib.load().convasr_conv1d_wgrad_workspace_bytes(*wkey)
-	ws = workspace(nbytes, x.device, 'wgrad')
-	_lib.timed(family or 'conv1d_wgrad', 2.0 * B * Tout * Cout * Cin * K if work is None else work, lambda: call('convasr_conv1d_wgrad', ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), dtype_code(x.dtype), B, Cin, Cout, Tin, Tout, K, stride, dil, pad, int(accumulate), layout, stream_ptr()))
-	return dw
+	return _wgrad_launch(dw, layout, (B, Cin, Cout, Tin, Tout, K, stride, dil), work, family, lambda ws, layout: call('convasr_conv1d_wgrad', ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), dtype_code(x.dtype), B, Cin, Cout, Tin, Tout, K, stride, dil, pad, int(accumulate), layout, stream_ptr()))
 
 
 # ------------------------------------------------------------------------------------------------ grouped conv (the separable block's first half)

@@ -109,8 +109,8 @@ class DataParallelEngine(nn.Module):
 			dist.broadcast(self.flat.data, src = 0, group = self.group)  # identical initial replicas
 			for buf in module.buffers():
 				dist.broadcast(buf, src = 0, group = self.group)
-			from . import functional as Fn
-			Fn.bump_param_epoch()  # the arena changed behind torch's version counters: packed compute copies are stale
+			from . import weights as W
+			W.bump_param_epoch()  # the arena changed behind torch's version counters: packed compute copies are stale
 
 	def close(self):
 		"""Un-register from the backward pass's hook list and stop the helper thread (idempotent; also runs when the engine is collected)."""

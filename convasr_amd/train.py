@@ -3,7 +3,7 @@
 FlatParameters re-homes every trainable parameter into ONE contiguous fp32 buffer with a matching gradient buffer, so that
 gradient clipping is one reduction launch, the optimizer one elementwise launch, and data-parallel all-reduce a handful of
 large contiguous RCCL calls (288 GB of HBM makes the duplicate-free arena trivially affordable).  Backward kernels write
-gradients straight into the arena (convasr_amd.functional._deliver).
+gradients straight into the arena (convasr_amd.functional._deliver_many).
 
 Conv weights live in the arena TAP-MAJOR ([K][Cout][Cin], include/convasr_hip.h CONVASR_W_KMAJOR): the parameter stays a
 (Cout, Cin, K) tensor -- state_dict(), load_state_dict() and checkpoints see the reference's shapes -- but it is a strided view.
@@ -18,6 +18,7 @@ import torch
 from . import ops, _lib
 from . import models as M
 from . import functional as Fn
+from . import weights as W
 
 
 class FlatParameters:
@@ -38,8 +39,8 @@ class FlatParameters:
 		self.numel = off
 		self.data = torch.zeros(off, dtype = torch.float32, device = dev)
 		self.grad = torch.zeros(off, dtype = torch.float32, device = dev)
+		W.mirror_reallocated(self)  # (no mirror yet: nothing is vouched for)
 		self.data16 = None  # 16-bit (bf16 or fp16: the model's compute dtype) mirror of `data`, allocated on first use (mirror()); written by the fused optimizer kernels
-		self._mirror_ver = {}  # id(param) -> version tuple (functional.packed_weight) at which the mirror segment equals bf16(param)
 		self._as_param = []  # per parameter: flat arena-shaped tensor -> view in the parameter's logical (reference) shape
 		for p, o in zip(params, self.offsets):
 			n = p.numel()
@@ -67,16 +68,13 @@ class FlatParameters:
 		if self.data16 is None or self.data16.dtype != dtype:
 			assert dtype in ops.HALF_DTYPES
 			self.data16 = torch.zeros(self.numel, dtype = dtype, device = self.data.device)
-			self._mirror_ver = {}
+			W.mirror_reallocated(self)
 		return self.data16
 
 	def mirror_carried_over(self, run):
 		"""Run one fused optimizer launch `run(p16)` that rewrites the 16-bit mirror together with the parameters (or leaves both
 		untouched when the device-side gate skips the step): segments that were current before it are current after it."""
-		was = {k for k, v in self._mirror_ver.items() if v == Fn.param_version(self._by_id[k])} if self._mirror_ver else set()
-		run(self.data16)
-		Fn.bump_param_epoch()  # packed compute copies other than the mirror are stale now
-		self._mirror_ver = {k: Fn.param_version(self._by_id[k]) for k in was} if self.data16 is not None else {}
+		W.mirror_carried_over(self, run)
 
 	def param_views(self, flat_tensor):
 		"""Per-parameter views of an arena-shaped tensor (optimizer state) in the parameters' logical shapes -- the reference's
@@ -386,7 +384,7 @@ class GraphedTrainStep:
 			engine.enable_capture()  # (a rendezvous of all ranks: the engine's own RCCL communicator, through which the captured collectives go -- parallel.DataParallelEngine.enable_capture)
 		self.graphs, self.seen = {}, {}
 		self.pool = None
-		self.epoch = Fn.structure_epoch()
+		self.epoch = W.structure_epoch()
 		self.replays = self.captures = self.eager_steps = 0
 		self.non_kernel_nodes = os.environ.get('CONVASR_GRAPH_FENCE') == '1'  # does any captured step hold a memset / memcpy / ... node (see _fence_transition)?
 		self._lr = None
@@ -439,29 +437,29 @@ class GraphedTrainStep:
 		self._sync_lr()
 		net = M.master_module(self.model)
 		cached = getattr(net, '_dgrad_weights', None)
-		if cached is not None and cached[0] == Fn.structure_epoch():
-			Fn.prewarm_dgrad_pack(cached[1], net.compute_dtype)  # (a host-to-device table copy: not possible inside the capture)
+		if cached is not None and cached[0] == W.structure_epoch():
+			W.prewarm_dgrad_pack(cached[1], net.compute_dtype)  # (a host-to-device table copy: not possible inside the capture)
 		# double-buffered device state (NovoGrad's EMAs, AdamW's applied-step counter, the loss scaler): the rows stop swapping for good --
 		# this graph, and every later eager step, hands the new state back to the row that is current now
 		opt._pinned = True
-		Fn.GRAPHS_CAPTURED[0] = True
+		W.GRAPHS_CAPTURED[0] = True
 		if getattr(opt.flat, 'loss_scaler', None) is not None:
 			opt.flat.loss_scaler.pinned = True
 		# every version-keyed packed copy (padded-Cout forward operands, the folded prologue, the padded head, fp32 / split operands) is
 		# declared stale, so that ALL per-step pack launches are recorded in the graph: a copy that happens to be current now -- a validation
 		# forward ran since the last optimizer step -- would otherwise get no pack node and go stale under replays
-		Fn.force_repack()
+		W.force_repack()
 		torch.cuda.synchronize(dev)
 		# The captured step is ONE chain of nodes unless linear = False: the weight-gradient side stream and the dgrad-weight prepack stream are
 		# switched off for the capture.  Measured on ROCm 7.2 (profiles/r05_graph_ab.json): a graph with forked branches replays 2 % SLOWER
 		# than the same nodes in one chain (the runtime spreads the branches over several queues and pays for the cross-queue signals; with
 		# DEBUG_HIP_FORCE_GRAPH_QUEUES=1 the forked capture matches the linear one), and never reaches the eager side stream's overlap.
-		side, prepack = dict(Fn._side_streams), Fn.PREPACK
+		side, prepack = dict(Fn._side_streams), W.PREPACK
 		if self.linear:
 			Fn.join_side_streams()
 			for k in Fn._side_streams:
 				Fn._side_streams[k] = None
-			Fn.PREPACK = False
+			W.PREPACK = False
 		Fn.CAPTURING[0] = True
 		try:
 			with torch.cuda.graph(graph, pool = self.pool):
@@ -470,7 +468,7 @@ class GraphedTrainStep:
 		finally:
 			Fn.CAPTURING[0] = False
 			Fn._side_streams.update(side)
-			Fn.PREPACK = prepack
+			W.PREPACK = prepack
 		opt.steps = steps0  # (nothing ran: the replay below is this step)
 		self.graphs[key] = dict(graph = graph, static = static, res = res, node_kinds = kinds)
 		if kinds is None or any(k != 'kernel' for k in kinds):
@@ -480,8 +478,8 @@ class GraphedTrainStep:
 	def __call__(self, x, xlen, y, ylen, iteration = 0):
 		if not self.enabled:
 			return self._eager(x, xlen, y, ylen, iteration)
-		if self.epoch != Fn.structure_epoch():  # conv modules were replaced (fuse_conv_bn_eval): the captured pointers are stale
-			self.graphs, self.seen, self.epoch = {}, {}, Fn.structure_epoch()
+		if self.epoch != W.structure_epoch():  # conv modules were replaced (fuse_conv_bn_eval): the captured pointers are stale
+			self.graphs, self.seen, self.epoch = {}, {}, W.structure_epoch()
 		key = self.key_of(x, xlen, y, ylen)
 		g = self.graphs.get(key)
 		if g is None:
@@ -496,7 +494,7 @@ class GraphedTrainStep:
 				_lib.call('convasr_copy', _lib.ptr(src if src.is_contiguous() else src.contiguous()), _lib.ptr(dst), dst.numel() * dst.element_size(), _lib.stream_ptr())
 		self._sync_lr()
 		opt = self.optimizer
-		Fn.join_prepack(x.device)  # (side streams an eager step may have left running are joined before the graph is launched)
+		W.join_prepack(x.device)  # (side streams an eager step may have left running are joined before the graph is launched)
 		self._fence_transition(x.device, eager = False)
 		Fn.join_side_streams()
 		opt.flat.mirror_carried_over(lambda p16: g['graph'].replay())  # (the same version bookkeeping an eager optimizer launch gets: the 16-bit mirror stays current, other packed copies go stale)

@@ -1,5 +1,5 @@
 """Host-side logic that needs no GPU: optimizer state in reference shapes, the fp16 / bf16 mapping of the apex opt levels, the
-loss scaler's host interface, graded gradient buckets, the stride-2 fold's padding rule, the accepted configuration flags."""
+loss scaler's host interface, graded gradient buckets, the stride-2 fold's padding rule, the accepted configuration flags, the gradient hand-off."""
 import os
 
 import pytest
@@ -208,3 +208,100 @@ def test_split_operand_arithmetic_restated_on_the_cpu():
 	full = O.conv1d_split3(x, w, padding = 5) + F.conv1d(xl.double(), wl.double(), padding = 5)  # + the dropped term: what is left is the planes' own residue
 	assert rel(full) < 0.8 * e3
 	assert rel(O.conv1d_split3(x, w, padding = 5, dtype = torch.float16)) < 5e-7
+
+
+# ------------------------------------------------------------------------------------------------ the gradient hand-off (functional._deliver_many)
+
+def _arena_param(shape, fresh = True, fired = None):
+	"""A CPU parameter carrying what train.FlatParameters / the data-parallel engine hang on it: a gradient arena, the fresh flag, a ready hook."""
+	p = torch.nn.Parameter(torch.zeros(shape))
+	p._convasr_grad, p._convasr_fresh = torch.zeros(shape), fresh
+	if fired is not None:
+		p._convasr_ready = lambda q: fired.append(q)
+	return p
+
+
+@pytest.mark.parametrize('fresh', [True, False])
+def test_hand_off_writes_arena_groups_in_place_and_fires_the_hooks_after_compute(fresh):
+	"""Every live parameter of the group has an arena: compute gets the arenas and accumulate = not fresh, autograd gets None, the parameters
+	stop being fresh, and each live parameter's ready hook fires once -- after compute.  A parameter that needs no gradient gets None."""
+	fired, log = [], []
+	w, b, frozen = _arena_param((4, 3), fresh, fired), _arena_param((4, ), fresh, fired), _arena_param((2, ), fresh, fired)
+	frozen.requires_grad_(False)
+
+	def compute(outs, acc):
+		log.append((outs, acc, list(fired)))
+	ret = Fn._deliver([w, None, b, frozen], compute)
+	assert ret == [None, None, None, None]
+	(outs, acc, fired_before), = log
+	assert outs[0] is w._convasr_grad and outs[1] is None and outs[2] is b._convasr_grad and outs[3] is None
+	assert acc is (not fresh) and fired_before == []
+	assert w._convasr_fresh is False and b._convasr_fresh is False and frozen._convasr_fresh is fresh
+	assert len(fired) == 2 and fired[0] is w and fired[1] is b
+
+
+def test_hand_off_refuses_a_group_out_of_step_before_compute_runs():
+	ran = []
+	w, b = _arena_param((4, 3), True), _arena_param((4, ), False)
+	with pytest.raises(ca._lib.ConvasrHipError, match = 'gradient arenas of one layer are out of step'):
+		Fn._deliver([w, b], lambda outs, acc: ran.append(1))
+	with pytest.raises(ca._lib.ConvasrHipError, match = 'gradient arenas of one layer are out of step'):
+		Fn._deliver_many([[_arena_param((2, ))], [w, b]], lambda outs, accs: ran.append(1))
+	assert not ran and w._convasr_fresh is True and b._convasr_fresh is False
+
+
+def test_hand_off_returns_fresh_fp32_tensors_for_a_group_without_arenas():
+	"""One live parameter without an arena is enough: the whole group goes to autograd as fresh fp32 contiguous tensors, never accumulated."""
+	fired = []
+	w, b = torch.nn.Parameter(torch.zeros(4, 3, 2, dtype = torch.float64).permute(0, 2, 1)), _arena_param((4, ), False, fired)
+	seen = []
+	ret = Fn._deliver([w, b, None], lambda outs, acc: seen.append((outs, acc)))
+	(outs, acc), = seen
+	assert acc is False and ret[2] is None and outs[2] is None
+	for r, o, p in zip(ret[:2], outs[:2], (w, b)):
+		assert r is o and r.dtype == torch.float32 and r.is_contiguous() and r.shape == p.shape and r is not getattr(p, '_convasr_grad', None)
+	assert b._convasr_fresh is False and not fired  # (nothing was delivered into the arena)
+
+
+def test_hand_off_of_several_groups_runs_compute_once():
+	"""Arena groups (one fresh, one accumulating), a group for autograd and a group nobody wants, in one call: one compute with per-group
+	outputs and flags; hooks only for the arena groups, after it."""
+	fired, log = [], []
+	a, b, c = [_arena_param((3, ), True, fired), _arena_param((3, ), True, fired)], [_arena_param((3, ), False, fired), None], [torch.nn.Parameter(torch.zeros(3)), None]
+	dead = [_arena_param((3, ), True, fired).requires_grad_(False), None]
+	ret = Fn._deliver_many([a, b, c, dead], lambda outs, accs: log.append((outs, accs, len(fired))))
+	(outs, accs, fired_before), = log
+	assert accs == [False, True, False, False] and fired_before == 0
+	assert outs[0][0] is a[0]._convasr_grad and outs[0][1] is a[1]._convasr_grad and outs[1][0] is b[0]._convasr_grad and outs[1][1] is None and outs[3] == [None, None]
+	assert ret[0] == [None, None] and ret[1] == [None, None] and ret[2][0] is outs[2][0] and ret[2][1] is None and ret[3] == [None, None]
+	assert [id(p) for p in fired] == [id(a[0]), id(a[1]), id(b[0])]
+
+
+def test_hand_off_with_no_live_parameter_runs_compute_only_when_told_to():
+	"""Nothing wants a gradient: compute is skipped -- unless it produces more than gradients (the batch-norm backward's coefficients:
+	always = True), then it runs once with all-None outputs."""
+	gamma, beta = _arena_param((4, )).requires_grad_(False), _arena_param((4, )).requires_grad_(False)
+	log = []
+	assert Fn._deliver([gamma, beta], lambda outs, acc: log.append((outs, acc))) == [None, None] and not log
+	assert Fn._deliver_many([[gamma, beta], [None, None]], lambda outs, accs: log.append((outs, accs))) == [[None, None], [None, None]] and not log
+	assert Fn._deliver([gamma, None], lambda outs, acc: log.append((outs, acc)), always = True) == [None, None]
+	assert Fn._deliver_many([[gamma, beta], [None]], lambda outs, accs: log.append((outs, accs)), always = True) == [[None, None], [None]]
+	assert log == [([None, None], False), ([[None, None], [None]], [False, False])]
+	assert gamma._convasr_fresh is True
+
+
+def test_a_repeated_library_query_is_answered_from_memory(monkeypatch):
+	"""ops._cached_query: the row count of the conv statistics and the weight gradient's workspace size are pure functions of their integer
+	arguments and sit on every launch's path -- the second identical question must not reach the library (nor any other helper of that name)."""
+	from convasr_amd import ops, _lib
+	rows = ops._conv_stats_max_rows(3, 777)
+	geometry = (3, 128, 256, 777, 777, 5, 1, 2)
+	nbytes = ops._cached_query('convasr_conv1d_wgrad_workspace_bytes', *geometry)
+	assert rows > 0 and nbytes >= 0 and ops._queries[('convasr_conv_stats_max_rows', 3, 777)] == rows and ops._queries[('convasr_conv1d_wgrad_workspace_bytes', ) + geometry] == nbytes
+
+	def unreachable():
+		raise AssertionError('a memoised query reached the library again')
+	monkeypatch.setattr(_lib, 'load', unreachable)
+	assert ops._conv_stats_max_rows(3, 777) == rows and ops._cached_query('convasr_conv1d_wgrad_workspace_bytes', *geometry) == nbytes
+	with pytest.raises(AssertionError, match = 'reached the library'):
+		ops._conv_stats_max_rows(3, 778)

@@ -230,10 +230,10 @@ def test_dropout_masks_of_different_seeds_are_not_permutations_of_each_other():
 
 
 def test_prepacked_dgrad_weights_leave_training_bitwise_unchanged():
-	"""functional.prepack_dgrad_weights (the backward pass's transposed weight copies, run on a side stream under the CTC recursion)
+	"""weights.prepack_dgrad_weights (the backward pass's transposed weight copies, run on a side stream under the CTC recursion)
 	against packing them in line: three training steps of a bf16 model end with bit-identical parameters."""
 	import convasr_amd as ca
-	from convasr_amd import functional as Fn
+	from convasr_amd import weights as W
 	d = torch.device('cuda:0')
 	g = torch.Generator().manual_seed(3)
 	x = (torch.rand(6, 16000 * 3, generator = g) * 2 - 1).to(d)
@@ -242,7 +242,7 @@ def test_prepacked_dgrad_weights_leave_training_bitwise_unchanged():
 	ylen = torch.tensor([[20], [15], [9], [20], [12], [18]], device = d)
 	finals = []
 	for prepack in (True, False):
-		prev, Fn.PREPACK = Fn.PREPACK, prepack
+		prev, W.PREPACK = W.PREPACK, prepack
 		try:
 			torch.manual_seed(0)
 			ca.functional.manual_seed(9)
@@ -256,7 +256,7 @@ def test_prepacked_dgrad_weights_leave_training_bitwise_unchanged():
 			assert bool(torch.isfinite(r['loss_cur']))
 			finals.append(flat.data.clone())
 		finally:
-			Fn.PREPACK = prev
+			W.PREPACK = prev
 	assert torch.equal(finals[0], finals[1])
 
 

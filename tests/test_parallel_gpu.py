@@ -87,7 +87,7 @@ def test_two_ranks_real_kernels_match_sequential_average():
 		grads = []
 		for r in range(world):
 			flats[r].data.copy_(flats[0].data)
-			ca.functional.bump_param_epoch()
+			ca.weights.bump_param_epoch()
 			x, xlen, y, ylen = _batch(r, d)
 			out = models[r](x, xlen, y = y, ylen = ylen)
 			((out['loss'] * ylen[:, 0]).mean()).backward()

@@ -1,4 +1,4 @@
-"""The split-operand ("x3") conv path on the MI355X (csrc/split3.hip, functional.split_weight, JasperNet.set_compute_dtype('bf16x3')):
+"""The split-operand ("x3") conv path on the MI355X (csrc/split3.hip, weights.split_weight, JasperNet.set_compute_dtype('bf16x3')):
 fp32 storage, every stride-1 conv as hi*hi + hi*lo + lo*hi on the 16-bit matrix pipe.  Reference arithmetic: nn.Conv1d in fp32
 (models.py:47-77); bars: the planes are exact splits, the three conv directions agree with float64 to the split's own 2^-16 / 2^-22, a
 training step agrees with the exact-fp32 path to 1e-5 in the CTC loss (north_star: 1e-4 against the reference; the 64 x 15 s case against
@@ -71,7 +71,7 @@ def test_pack_conv_weight_split3_layouts(dt, kmajor):
 @pytest.mark.parametrize('shape', [(3, 256, 384, 300, 11, 1, 5), (2, 768, 896, 200, 29, 2, 29), (3, 896, 1024, 257, 1, 1, 0), (2, 192, 136, 77, 3, 1, 1)])
 def test_split_conv_forward_dgrad_wgrad_against_float64(dt, tol, shape):
 	"""(fp16 planes: the test's output gradient of ~1e-3 puts its lo plane into fp16's subnormals -- 1.7e-5; a training run scales the loss)"""
-	from convasr_amd import ops, functional as Fn
+	from convasr_amd import ops, weights as W
 	d = torch.device('cuda:0')
 	B, Cin, Cout, T, K, dil, pad = shape
 	torch.manual_seed(2)
@@ -83,7 +83,7 @@ def test_split_conv_forward_dgrad_wgrad_against_float64(dt, tol, shape):
 	dw_ref = torch.nn.grad.conv1d_weight(x.double(), w.shape, dy.double(), padding = pad, dilation = dil)
 	xg, wg, dyg = ops.as_cl(x.to(d), torch.float32), w.to(d), ops.as_cl(dy.to(d), torch.float32)
 	x3, dy3 = ops.split3(xg, dt, ops.SPLIT_INPUT), ops.split3(dyg, dt, ops.SPLIT_GRAD)
-	wf, wd = Fn.split_weight(wg, dt)
+	wf, wd = W.split_weight(wg, dt)
 	y = ops.conv1d(x3, wf, Cout, K, 1, dil, pad, out_dtype = torch.float32)
 	dx = ops.conv1d(dy3, wd, Cin, K, 1, dil, dil * (K - 1) - pad, out_dtype = torch.float32)
 	dw = torch.empty(Cout, Cin, K, device = d)
@@ -372,7 +372,7 @@ def test_graphs_interleaved_with_eager_steps_keep_the_double_buffered_state_curr
 
 def test_capture_after_a_validation_pass_still_records_every_pack_launch():
 	"""fp32 compute (every packed copy is version-keyed, none is served by the optimizer's 16-bit mirror): a validation forward right before
-	the step that gets captured makes the packed forward copies current, so without functional.force_repack() the graph would hold no pack
+	the step that gets captured makes the packed forward copies current, so without weights.force_repack() the graph would hold no pack
 	node for them and replay with frozen weights."""
 	import convasr_amd as ca
 	d = torch.device('cuda:0')
