@@ -124,6 +124,12 @@ _SIGNATURES = dict(
 	convasr_ctc_greedy_segments = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_nw_align_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
 	convasr_nw_align = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_nw_align_long_tile = (c_int, []),
+	convasr_nw_align_long_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
+	convasr_nw_align_long = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_nw_align_long_parts = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_edit_distance_long_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
+	convasr_edit_distance_long = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_p]),
 	convasr_sliding_max_out_len = (c_i64, [c_i64, c_int]),
 	convasr_sliding_max_tile = (c_int, [c_int]),
 	convasr_sliding_max = (c_int, [c_p, c_p, c_int, c_i64, c_int, c_int, c_p]),

@@ -1,4 +1,5 @@
-"""Character and word error rates (reference: metrics.py:409-421, cer / wer) with the edit distances on the GPU (convasr_edit_distance).
+"""Character and word error rates (reference: metrics.py:409-421, cer / wer) with the edit distances on the GPU (convasr_edit_distance; past
+16,383 units a side, a whole recording, convasr_edit_distance_long -- and convasr_nw_align_long for the alignments below).
 
 Two paths:
 * strings -- cer / wer / cer_wer: the reference's arithmetic exactly.  CER compares hyp.replace(' ', '').lower() with the same of ref
@@ -51,16 +52,49 @@ def word_units(hyps, refs):
 	return h, r, [len(s.split()) or 1 for s in refs]
 
 
-def _rates(hyp_units, ref_units, denominators, equal, device):
-	h, hl = _pack(hyp_units, device)
-	r, rl = _pack(ref_units, device)
-	dist, _ = ops.edit_distance(h, hl, r, rl, _lib.METRIC_CHARS, -1)
-	return [0.0 if same else d / n for d, n, same in zip(dist.cpu().tolist(), denominators, equal)]
+def split_route(len_a, len_b, route = None):
+	"""Which pairs take which kernels: (short, long) lists of pair numbers.  route None: a pair whose unit counts both fit
+	_lib.METRIC_MAX_LEN = 16,383 (the envelope of ops.edit_distance / ops.nw_align) is short, the others are long (the tiled
+	ops.edit_distance_long / ops.nw_align_long, up to 131,071 units a side); 'short' / 'long' send every pair one way (tests and timing)."""
+	if route not in (None, 'short', 'long'):
+		raise ValueError(f"route {route!r} is not None, 'short' or 'long'")
+	fits = [route == 'short' or (route is None and max(m, n) <= _lib.METRIC_MAX_LEN) for m, n in zip(len_a, len_b)]
+	return [p for p, f in enumerate(fits) if f], [p for p, f in enumerate(fits) if not f]
 
 
-def cer_wer(hyps, refs, device = None):
+def _pack32(seqs, device):
+	"""_pack for the long route: int32 ids."""
+	t, lengths = _pack(seqs, device)
+	return t.to(torch.int32), lengths.to(torch.int32)
+
+
+def _distances(hyp_units, ref_units, device, route = None, short_fn = None, long_fn = None):
+	"""The edit distance of every pair, as a list: the short pairs in one ops.edit_distance call (the only call when every pair is short),
+	the long ones in one ops.edit_distance_long call."""
+	short_fn, long_fn = short_fn or ops.edit_distance, long_fn or ops.edit_distance_long
+	short, long = split_route([len(h) for h in hyp_units], [len(r) for r in ref_units], route)
+	dist = [0] * len(hyp_units)
+	if short:
+		h, hl = _pack([hyp_units[p] for p in short], device)
+		r, rl = _pack([ref_units[p] for p in short], device)
+		for p, d in zip(short, short_fn(h, hl, r, rl, _lib.METRIC_CHARS, -1)[0].cpu().tolist()):
+			dist[p] = d
+	if long:
+		h, hl = _pack32([hyp_units[p] for p in long], device)
+		r, rl = _pack32([ref_units[p] for p in long], device)
+		for p, d in zip(long, long_fn(h, hl, r, rl).cpu().tolist()):
+			dist[p] = d
+	return dist
+
+
+def _rates(hyp_units, ref_units, denominators, equal, device, route = None):
+	return [0.0 if same else d / n for d, n, same in zip(_distances(hyp_units, ref_units, device, route), denominators, equal)]
+
+
+def cer_wer(hyps, refs, device = None, route = None):
 	"""Per-utterance CER and WER of the string pairs (hyps[i], refs[i]), as the reference's metrics.cer / metrics.wer compute them:
-	two lists of floats.  Every string's units must number at most 16,383 (ops.edit_distance's envelope)."""
+	two lists of floats.  Pairs of at most 16,383 units a side run on ops.edit_distance, longer ones (a whole recording: up to 131,071
+	units a side) on ops.edit_distance_long; route forces one of the two (split_route)."""
 	hyps, refs = list(hyps), list(refs)
 	if len(hyps) != len(refs):
 		raise ValueError(f'cer_wer: {len(hyps)} hypotheses for {len(refs)} references')
@@ -68,7 +102,7 @@ def cer_wer(hyps, refs, device = None):
 		return [], []
 	device = _device(device)
 	equal = [a == b for a, b in zip(hyps, refs)]
-	return _rates(*char_units(hyps, refs), equal, device), _rates(*word_units(hyps, refs), equal, device)
+	return _rates(*char_units(hyps, refs), equal, device, route), _rates(*word_units(hyps, refs), equal, device, route)
 
 
 def cer(*, hyp, ref):
@@ -81,12 +115,72 @@ def wer(*, hyp, ref):
 	return cer_wer([hyp], [ref])[1][0]
 
 
-def token_cer_wer(tokens, lengths, ref, ref_lengths, space):
+def _compact_chars(tokens, lengths, space):
+	"""(N, L) int64 tokens -> (the tokens below each length that are not `space`, moved to the front in order, as int32; their count (N,)
+	int32), on the device: a stable sort of the keep mask."""
+	L = tokens.shape[1]
+	keep = (tokens != space) & (torch.arange(L, device = tokens.device)[None, :] < lengths[:, None])
+	order = torch.sort((~keep).to(torch.uint8), dim = 1, stable = True).indices
+	return tokens.gather(1, order).to(torch.int32), keep.sum(dim = 1).to(torch.int32)
+
+
+def _word_id_rows(rows, lengths, space, ids):
+	"""Host lists of tokens -> per row the ids of its maximal runs of non-space tokens (equal words, equal ids: a dict of tuples, exact)."""
+	out = []
+	for row, n in zip(rows, lengths):
+		words, cur = [], []
+		for t in row[:max(n, 0)] + [space]:
+			if t != space:
+				cur.append(t)
+			elif cur:
+				words.append(ids.setdefault(tuple(cur), len(ids)))
+				cur = []
+		out.append(words)
+	return out
+
+
+def _token_cer_wer_long(tokens, lengths, ref, ref_lengths, space):
+	squeeze = tokens.ndim == 2
+	if squeeze:
+		tokens, lengths = tokens.unsqueeze(1), torch.as_tensor(lengths).unsqueeze(1)
+	B, K, L = tokens.shape
+	dev = tokens.device
+	hyp = tokens.reshape(B * K, L)
+	hl = torch.as_tensor(lengths).to(device = dev, dtype = torch.int64).reshape(B * K).clamp(0, L)
+	rl = torch.as_tensor(ref_lengths).to(device = dev, dtype = torch.int64).clamp(0, ref.shape[1])
+	pair_ref = torch.arange(B, device = dev).repeat_interleave(K)
+	# CHARS: the non-space tokens, compacted on the device
+	hc, hn = _compact_chars(hyp, hl, space)
+	rc, rn = _compact_chars(ref, rl, space)
+	cd = ops.edit_distance_long(hc, hn, rc[pair_ref], rn[pair_ref])
+	# WORDS: word ids through a dict on the host (one round trip)
+	ids = {}
+	rw = _word_id_rows(ref.cpu().tolist(), rl.cpu().tolist(), space, ids)
+	hw = _word_id_rows(hyp.cpu().tolist(), hl.cpu().tolist(), space, ids)
+	hwt, hwl = _pack32(hw, dev)
+	rwt, rwl = _pack32([rw[p // K] for p in range(B * K)], dev)
+	wd = ops.edit_distance_long(hwt, hwl, rwt, rwl)
+	units, words = rn.double().clamp(min = 1), torch.tensor([len(w) for w in rw], dtype = torch.float64, device = dev).clamp(min = 1)
+	cer, wer = cd.double().view(B, K) / units.view(B, 1), wd.double().view(B, K) / words.view(B, 1)
+	return (cer[:, 0], wer[:, 0]) if squeeze else (cer, wer)
+
+
+def token_cer_wer(tokens, lengths, ref, ref_lengths, space, route = None):
 	"""Per-utterance CER and WER of token hypotheses against token references, on the device.  tokens (B, K, L) int64 with lengths (B, K), or
 	(B, L) with (B,); ref (B, Lr) int64 read in place through its row stride (y[:, 0]), ref_lengths (B,) (ylen[:, 0]); space: the space class.
 	CER = edit distance over the tokens that are not `space` / (their number in the reference or 1); WER = edit distance over the maximal
 	runs of non-space tokens / (their number in the reference or 1).  Returns two float64 device tensors shaped like lengths.  Valid for
-	one-character lowercase tokenizers only (see the module docstring)."""
+	one-character lowercase tokenizers only (see the module docstring).
+
+	While L and Lr are at most 16,383 (route None; 'short' forces it) ops.edit_distance makes the units itself and nothing leaves the
+	device.  Longer batches (a whole recording; up to 131,071 units a side; 'long' forces it) go to ops.edit_distance_long, whose unit ids
+	this function makes: the non-space tokens compacted on the device for CER, and for WER word ids through a dict on the HOST, which is
+	exact and costs one round trip of the tokens (class ids must fit int32)."""
+	if route not in (None, 'short', 'long'):
+		raise ValueError(f"route {route!r} is not None, 'short' or 'long'")
+	if route == 'long' or (route is None and max(tokens.shape[-1], ref.shape[-1]) > _lib.METRIC_MAX_LEN):
+		ops.require_cuda(tokens, ref)
+		return _token_cer_wer_long(tokens, lengths, ref, ref_lengths, int(space))
 	cd, units = ops.edit_distance(tokens, lengths, ref, ref_lengths, _lib.METRIC_CHARS, int(space))
 	wd, words = ops.edit_distance(tokens, lengths, ref, ref_lengths, _lib.METRIC_WORDS, int(space))
 	shape = (-1, ) + (1, ) * (cd.ndim - 1)
@@ -114,18 +208,30 @@ def replace_placeholder(s, rep = ''):
 	return s.replace(placeholder, rep)
 
 
-def gpu_aligner(a_seqs, b_seqs, scores, device = None):
-	"""The default aligner: all pairs in one ops.nw_align call, the index rows back in one device-to-host copy."""
+def gpu_aligner(a_seqs, b_seqs, scores, device = None, route = None, short_fn = None, long_fn = None):
+	"""The default aligner: all pairs in one ops.nw_align call, the index rows back in one device-to-host copy.  Pairs with more than
+	16,383 units on a side (a whole recording; up to 131,071) go to ops.nw_align_long in a second call; route forces one of the two
+	(split_route)."""
 	if not a_seqs:
 		return []
 	device = _device(device)
+	short, long = split_route([len(s) for s in a_seqs], [len(t) for t in b_seqs], route)
+	out = [None] * len(a_seqs)
+	for members, fn in ((short, short_fn or ops.nw_align), (long, long_fn or ops.nw_align_long)):
+		if members:
+			for p, cols in zip(members, _align_group(fn, [a_seqs[p] for p in members], [b_seqs[p] for p in members], scores, device)):
+				out[p] = cols
+	return out
+
+
+def _align_group(nw_align, a_seqs, b_seqs, scores, device):
 	N = len(a_seqs)
 	La, Lb = max(map(len, a_seqs)), max(map(len, b_seqs))
 	a, b = np.zeros((N, max(La, 1)), dtype = np.int32), np.zeros((N, max(Lb, 1)), dtype = np.int32)
 	for i, (s, t) in enumerate(zip(a_seqs, b_seqs)):
 		a[i, :len(s)], b[i, :len(t)] = s, t
 	lengths = torch.from_numpy(np.array([[len(s) for s in a_seqs], [len(t) for t in b_seqs]], dtype = np.int32)).to(device)
-	ai, bi, n, _ = ops.nw_align(torch.from_numpy(a).to(device)[:, :La], lengths[0], torch.from_numpy(b).to(device)[:, :Lb], lengths[1], scores)
+	ai, bi, n, _ = nw_align(torch.from_numpy(a).to(device)[:, :La], lengths[0], torch.from_numpy(b).to(device)[:, :Lb], lengths[1], scores)
 	host = torch.cat([n, ai.flatten(), bi.flatten()]).cpu().numpy()
 	W = La + Lb
 	n, ai, bi = host[:N], host[N:N + N * W].reshape(N, W), host[N + N * W:].reshape(N, W)
@@ -154,7 +260,8 @@ def _aligned_units(index_a, index_b, a, b, unit_gap):
 def align_strings_batch(hyps, refs, aligner = None):
 	"""align_strings over lists: [( _hyp_, _ref_ )] per pair.  Two aligner calls for the whole batch -- one over the word ids of every pair,
 	one over the characters of every span of non-equal words of every pair -- so on the GPU two launches and two device-to-host copies,
-	whatever the batch size (while the batch fits under ops.nw_align's workspace cap; a batch it has to split adds one launch per split)."""
+	whatever the batch size (while the batch fits under ops.nw_align's workspace cap; a batch it has to split adds one launch per split;
+	pairs past 16,383 units a side add one ops.nw_align_long call per level)."""
 	aligner = aligner or gpu_aligner
 	hyps, refs = list(hyps), list(refs)
 	if len(hyps) != len(refs):

@@ -1009,7 +1009,7 @@ def edit_distance(hyp, hyp_lengths, ref, ref_lengths, mode = _lib.METRIC_CHARS, 
 	batch needs no copy), ref_lengths (B,) read through its stride as well (ylen[:, 0]).  mode: _lib.METRIC_CHARS (units = the tokens that
 	are not `space`; space < 0: every token) or _lib.METRIC_WORDS (units = maximal runs of non-space tokens, space >= 0).
 	Returns (distance (B, K) int32 -- (B,) for a (B, Lh) hyp -- , ref_units (B,) int32).  Outside the envelope (Lh, Lr <= 16383,
-	B * K < 2^20, ...) it raises ConvasrHipError."""
+	B * K < 2^20, ...) it raises ConvasrHipError; edit_distance_long takes longer pairs (of ready-made unit ids)."""
 	require_cuda(hyp, ref)
 	squeeze = hyp.ndim == 2
 	if squeeze:
@@ -1138,7 +1138,7 @@ def nw_align(a, a_lengths, b, b_lengths, scores, workspace_cap = NW_WORKSPACE_CA
 	NW_WORKSPACE_CAP = 1 GiB, a resource bound) the whole batch is one launch and nothing is copied to the host.  A larger batch is split:
 	the lengths come to the host once, the pairs are ordered by size and cut into the fewest groups that each fit under the cap at their
 	own largest lengths, one launch per group.  A single pair over the cap, or anything outside the envelope (N < 2^20, La, Lb <= 16383),
-	raises ConvasrHipError."""
+	raises ConvasrHipError; nw_align_long takes longer pairs."""
 	require_cuda(a, b)
 	if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
 		raise ValueError(f'nw_align: a {tuple(a.shape)} and b {tuple(b.shape)} are not (N, La) and (N, Lb)')
@@ -1176,6 +1176,149 @@ def nw_align(a, a_lengths, b, b_lengths, scores, workspace_cap = NW_WORKSPACE_CA
 		ai, bi, nc, sc = _nw_launch(a[idx, :ga].contiguous(), al[idx], b[idx, :gb].contiguous(), bl[idx], scores)
 		a_index[idx, :ga + gb], b_index[idx, :ga + gb], n_cols[idx], score[idx] = ai, bi, nc, sc
 	return a_index, b_index, n_cols, score
+
+
+NW_LONG_WORKSPACE_CAP = 16 << 30  # bytes of workspace one convasr_nw_align_long / convasr_edit_distance_long call may take; a resource bound like ALIGN_LONG_WORKSPACE_CAP, not a measurement
+NW_LONG_MAX_LEN = 131071  # CONVASR_NW_LONG_MAX_LEN
+
+
+def nw_align_long_tile():
+	"""The edge of convasr_nw_align_long's (and convasr_edit_distance_long's) square tiles, in cells (tests straddle it)."""
+	return _lib.load().convasr_nw_align_long_tile()
+
+
+def nw_align_long_workspace_bytes(N, La, Lb):
+	"""convasr_nw_align_long_workspace_bytes (include/convasr_hip.h states the formula)."""
+	return _query('convasr_nw_align_long_workspace_bytes', int(N), int(La), int(Lb))
+
+
+def edit_distance_long_workspace_bytes(N, La, Lb):
+	"""convasr_edit_distance_long_workspace_bytes: the two boundary families of include/convasr_hip.h."""
+	return _query('convasr_edit_distance_long_workspace_bytes', int(N), int(La), int(Lb))
+
+
+def _cap_groups(la, lb, need, cap):
+	"""The split ops.nw_align makes of a batch over its workspace cap: the pairs p (of la[p] x lb[p] units) ordered by need(1, la[p], lb[p]),
+	largest first, and cut into the fewest groups that each fit under `cap` at their own largest lengths.  Returns [(members, group La,
+	group Lb)]; the first group holds the largest pair (which alone may still be over the cap: the caller checks)."""
+	order = sorted(range(len(la)), key = lambda p: -need(1, la[p], lb[p]))
+	groups, cur, ga, gb = [], [], 0, 0
+	for p in order:
+		na, nb = max(ga, la[p]), max(gb, lb[p])
+		if cur and need(len(cur) + 1, na, nb) > cap:
+			groups.append((cur, ga, gb))
+			cur, na, nb = [], la[p], lb[p]
+		cur, ga, gb = cur + [p], na, nb
+	groups.append((cur, ga, gb))
+	return groups
+
+
+def _long_pairs(name, a, a_lengths, b, b_lengths):
+	require_cuda(a, b)
+	if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
+		raise ValueError(f'{name}: a {tuple(a.shape)} and b {tuple(b.shape)} are not (N, La) and (N, Lb)')
+	dev = a.device
+	N = a.shape[0]
+	a, b = a.to(torch.int32).contiguous(), b.to(device = dev, dtype = torch.int32).contiguous()
+	al = torch.as_tensor(a_lengths).to(device = dev, dtype = torch.int32).contiguous()
+	bl = torch.as_tensor(b_lengths).to(device = dev, dtype = torch.int32).contiguous()
+	if al.shape != (N,) or bl.shape != (N,):
+		raise ValueError(f'{name}: lengths of shapes {tuple(al.shape)}, {tuple(bl.shape)} for a batch of {N}')
+	return a, al, b, bl
+
+
+def _long_groups(name, query, al, bl, La, Lb, workspace_cap):
+	"""None when the whole batch fits under the cap; otherwise _cap_groups of it (the lengths come to the host once)."""
+	if query(al.shape[0], La, Lb) <= workspace_cap:
+		return None
+	lens = torch.stack([al.clamp(0, La), bl.clamp(0, Lb)]).cpu().tolist()
+	groups = _cap_groups(lens[0], lens[1], query, workspace_cap)
+	_, ga, gb = groups[0]
+	if query(1, ga, gb) > workspace_cap:
+		raise _lib.ConvasrHipError(f'{name}: one pair of {ga} x {gb} units needs {query(1, ga, gb)} bytes of workspace, over the cap of {workspace_cap}')
+	return groups
+
+
+def _nw_long_launch(a, al, b, bl, scores, parts = 3, ws = None):
+	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
+	dev = a.device
+	W = max(La + Lb, 1)
+	a_index = torch.empty(N, W, dtype = torch.int32, device = dev)
+	b_index = torch.empty(N, W, dtype = torch.int32, device = dev)
+	n_cols = torch.empty(N, dtype = torch.int32, device = dev)
+	score = torch.empty(N, dtype = torch.int32, device = dev)
+	nbytes = nw_align_long_workspace_bytes(N, La, Lb)
+	if ws is None:
+		ws = torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)  # (per call, not ops.workspace: that cache keeps its buffers for good)
+	if La == 0:  # (a zero-size tensor has no storage to point at; no unit is read past a length anyway)
+		a = torch.zeros(N, 1, dtype = torch.int32, device = dev)
+	if Lb == 0:
+		b = torch.zeros(N, 1, dtype = torch.int32, device = dev)
+	call('convasr_nw_align_long_parts', ptr(a), ptr(al), ptr(b), ptr(bl), ptr(a_index), ptr(b_index), ptr(n_cols), ptr(score), ptr(ws), nbytes, N, La, Lb,
+	     *scores, int(parts), stream_ptr())
+	return a_index[:, :La + Lb], b_index[:, :La + Lb], n_cols, score
+
+
+def nw_align_long(a, a_lengths, b, b_lengths, scores, workspace_cap = NW_LONG_WORKSPACE_CAP):
+	"""nw_align for whole recordings (include/convasr_hip.h: convasr_nw_align_long): up to 131,071 units a side, scores in [-2048, 2048],
+	the same four results as nw_align, bit for bit where that takes the arguments.  The matrix is filled in tiles of nw_align_long_tile()
+	cells a side, one launch per anti-diagonal of tiles, so one long pair runs on many CUs; not meant for graph capture.
+
+	The workspace (2 direction bits per cell: 16,500 x 16,400 units take 78 MB in all, 100,000 x 100,000 2.5 GB) is allocated for this call and
+	goes back to the allocator.  While the batch's need is at most workspace_cap (default NW_LONG_WORKSPACE_CAP = 16 GiB, a resource
+	bound) it is one call and nothing is copied to the host; a larger batch is split as nw_align splits one: the lengths come to the host
+	once and the pairs are cut into the fewest groups that each fit.  A single pair over the cap, or anything outside the envelope, raises
+	ConvasrHipError."""
+	a, al, b, bl = _long_pairs('nw_align_long', a, a_lengths, b, b_lengths)
+	scores = tuple(int(s) for s in scores)
+	if len(scores) != 4:
+		raise ValueError('nw_align_long: scores = (match, sub, del, ins)')
+	dev = a.device
+	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
+	groups = _long_groups('nw_align_long', nw_align_long_workspace_bytes, al, bl, La, Lb, workspace_cap)
+	if groups is None:
+		return _nw_long_launch(a, al, b, bl, scores)
+	a_index = torch.full((N, La + Lb), -1, dtype = torch.int32, device = dev)
+	b_index = torch.full((N, La + Lb), -1, dtype = torch.int32, device = dev)
+	n_cols = torch.empty(N, dtype = torch.int32, device = dev)
+	score = torch.empty(N, dtype = torch.int32, device = dev)
+	for members, ga, gb in groups:
+		idx = torch.tensor(members, dtype = torch.int64, device = dev)
+		ai, bi, nc, sc = _nw_long_launch(a[idx, :ga].contiguous(), al[idx], b[idx, :gb].contiguous(), bl[idx], scores)
+		a_index[idx, :ga + gb], b_index[idx, :ga + gb], n_cols[idx], score[idx] = ai, bi, nc, sc
+	return a_index, b_index, n_cols, score
+
+
+def _ed_long_launch(a, al, b, bl):
+	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
+	dev = a.device
+	distance = torch.empty(N, dtype = torch.int32, device = dev)
+	nbytes = edit_distance_long_workspace_bytes(N, La, Lb)
+	ws = torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)
+	if La == 0:
+		a = torch.zeros(N, 1, dtype = torch.int32, device = dev)
+	if Lb == 0:
+		b = torch.zeros(N, 1, dtype = torch.int32, device = dev)
+	call('convasr_edit_distance_long', ptr(a), ptr(al), ptr(b), ptr(bl), ptr(distance), ptr(ws), nbytes, N, La, Lb, stream_ptr())
+	return distance
+
+
+def edit_distance_long(a, a_lengths, b, b_lengths, workspace_cap = NW_LONG_WORKSPACE_CAP):
+	"""Levenshtein distances of N pairs of integer unit ids for whole recordings (include/convasr_hip.h: convasr_edit_distance_long): a (N, La)
+	/ b (N, Lb) ids (made int32; equal units, equal ids -- the caller makes them, unlike edit_distance), a_lengths / b_lengths (N,), up to
+	131,071 units a side.  Returns distance (N,) int32, exact.  The tiles, launches, workspace conventions and the split of a batch over
+	workspace_cap are nw_align_long's; the workspace holds the tile boundaries only (4 * (La + Lb) * max(La, Lb) / tile bytes a pair)."""
+	a, al, b, bl = _long_pairs('edit_distance_long', a, a_lengths, b, b_lengths)
+	dev = a.device
+	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
+	groups = _long_groups('edit_distance_long', edit_distance_long_workspace_bytes, al, bl, La, Lb, workspace_cap)
+	if groups is None:
+		return _ed_long_launch(a, al, b, bl)
+	distance = torch.empty(N, dtype = torch.int32, device = dev)
+	for members, ga, gb in groups:
+		idx = torch.tensor(members, dtype = torch.int64, device = dev)
+		distance[idx] = _ed_long_launch(a[idx, :ga].contiguous(), al[idx], b[idx, :gb].contiguous(), bl[idx])
+	return distance
 
 
 # ------------------------------------------------------------------------------------------------ diarization

@@ -553,8 +553,9 @@ def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_sp
 	Returns dict(loss, entropy, cer, wer[, cer_oracle, wer_oracle]) of aggregates -- the mean over the finite per-utterance values, -1.0
 	when there are none (metrics.nanmean) -- and `utterances`: per-utterance CPU tensors in batch order (loss, entropy, uncertainty, cer,
 	wer[, cer_oracle, wer_oracle]); with return_text also `hyp`, the best hypothesis of every utterance as transcribe.join would give it.
-	Everything reaches the host in one copy at the end.  The hypotheses are scored as (B, K, T) token rows, T the batch's output frames, so T
-	is bound by ops.edit_distance's envelope: a batch of more than 16,383 output frames raises ConvasrHipError.  model.training is restored on return; parameters, batch-norm statistics, torch's
+	Everything reaches the host in one copy at the end.  The hypotheses are scored as (B, K, T) token rows, T the batch's output frames, so a
+	batch of more than 16,383 output frames (ops.edit_distance's envelope) takes metrics.token_cer_wer's long route: ops.edit_distance_long, up to 131,071 frames,
+	with one extra round trip of the tokens for the word ids.  model.training is restored on return; parameters, batch-norm statistics, torch's
 	RNG and the dropout generator's offsets are left as they were.
 
 	error_analyzer: a metrics.ErrorAnalyzer, or None.  With one, the best hypothesis and the decoded target y[:, 0] of every utterance (their

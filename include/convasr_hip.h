@@ -743,6 +743,53 @@ int convasr_nw_align(const int32_t* a, const int32_t* a_lengths, const int32_t* 
                      int32_t* b_index, int32_t* n_cols, int32_t* score, void* workspace, int64_t workspace_bytes, int N, int La, int Lb,
                      int match, int sub, int del, int ins, void* stream);
 
+/* The same alignment for whole recordings: up to CONVASR_NW_LONG_MAX_LEN units a side, on many CUs.  Arguments, matrix, end-cell rule,
+ * walk priority and outputs are those of convasr_nw_align, and every output equals convasr_nw_align's bit for bit wherever both accept
+ * the arguments.  The matrix is cut into square tiles of convasr_nw_align_long_tile() cells a side (a multiple of 64; 256), one wave per
+ * tile; launch k of ceil(La / tile) + ceil(Lb / tile) - 1 plain launches runs the k-th anti-diagonal of tiles of all N pairs (the count
+ * comes from La and Lb, nothing is read back; a tile wholly outside a pair's own la x lb ends at once).  What crosses a tile edge -- the
+ * last row of every tile row, the last column of every tile column -- is stored whole in the workspace and only ever read by a later
+ * launch: no workgroup waits on another, no cooperative launch, no atomics.  The tiles of the last tile row (la < lb) or column leave a
+ * per-tile best end cell; one more launch, one wave per pair, reduces them and walks back through the directions a tile at a time.
+ * workspace: at least convasr_nw_align_long_workspace_bytes(N, La, Lb) bytes, 16-byte aligned, uninitialised.  With T the tile edge,
+ * ti = ceil(La / T), tj = ceil(Lb / T) and up(n) = n rounded up to a multiple of 256, the query returns
+ *   up(N * ti * tj * T * T / 4)            2 direction bits per cell, per tile contiguously (16 KiB a tile: 4 GiB for 131,071 x 131,071)
+ * + up(N * ti * (Lb + 1) * 4)              the last row of every tile row
+ * + up(N * tj * (La + 1) * 4)              the last column of every tile column
+ * + up(N * max(ti, tj, 1) * 8)             the per-tile end-cell keys
+ * + up(N * (La + Lb) * 8)                  the walked columns,
+ * or -1 outside the envelope of N, La, Lb.  No memset or copy; the call makes hundreds of launches for a long pair and is NOT meant for
+ * graph capture.
+ * Envelope, checked before any launch: 1 <= N < 2^20, 0 <= La, Lb <= CONVASR_NW_LONG_MAX_LEN (ctc_alignment_long's label limit), every
+ * score in [-2048, 2048] (a cell is at most 2048 * 262,142 < 2^29 in magnitude, E[k] - k * ins below 2^30: int32 cells), no NULL
+ * pointer, workspace_bytes at least the query's answer; outside it CONVASR_EINVAL (a length past the limit: CONVASR_EUNSUPPORTED).
+ * convasr_nw_align_long_parts: parts 1 = the fill only, 2 = the end cell and the walk over a workspace that a fill with the same
+ * arguments left, 3 = both (for measurements that time the two apart). */
+#define CONVASR_NW_LONG_MAX_LEN 131071
+int convasr_nw_align_long_tile(void);
+int64_t convasr_nw_align_long_workspace_bytes(int N, int La, int Lb);
+int convasr_nw_align_long(const int32_t* a, const int32_t* a_lengths, const int32_t* b, const int32_t* b_lengths, int32_t* a_index,
+                          int32_t* b_index, int32_t* n_cols, int32_t* score, void* workspace, int64_t workspace_bytes, int N, int La, int Lb,
+                          int match, int sub, int del, int ins, void* stream);
+int convasr_nw_align_long_parts(const int32_t* a, const int32_t* a_lengths, const int32_t* b, const int32_t* b_lengths, int32_t* a_index,
+                                int32_t* b_index, int32_t* n_cols, int32_t* score, void* workspace, int64_t workspace_bytes, int N, int La,
+                                int Lb, int match, int sub, int del, int ins, int parts, void* stream);
+
+/* Levenshtein distances of N pairs of integer unit ids, up to CONVASR_NW_LONG_MAX_LEN units a side, on many CUs (convasr_edit_distance
+ * stops at CONVASR_METRIC_MAX_LEN and makes the ids itself; here the caller does).  a (N, La) int32 with a_lengths (N,) int32, b (N, Lb)
+ * int32 with b_lengths (N,) int32; only units below a length are read, the lengths are clamped to [0, La] / [0, Lb] on the device; two
+ * units are equal iff their ids are equal.  distance (N,) int32 = D[la][lb] with D[i][0] = i, D[0][j] = j,
+ * D[i][j] = min(D[i-1][j] + 1, D[i][j-1] + 1, D[i-1][j-1] + (a[i-1] != b[j-1])): exact.
+ * The tiles and launches of convasr_nw_align_long with min for max (one more small launch writes the pairs with an empty side); no
+ * directions, no end-cell search, no walk.  workspace: at least convasr_edit_distance_long_workspace_bytes(N, La, Lb) =
+ * up(N * ti * (Lb + 1) * 4) + up(N * tj * (La + 1) * 4) bytes (the two boundary families above: 268 MB each at the limit), 16-byte
+ * aligned, uninitialised; -1 outside the envelope.  No memset or copy; not meant for graph capture.
+ * Envelope, checked before any launch: 1 <= N < 2^20, 0 <= La, Lb <= CONVASR_NW_LONG_MAX_LEN, no NULL pointer, workspace_bytes at least
+ * the query's answer; outside it CONVASR_EINVAL (a length past the limit: CONVASR_EUNSUPPORTED). */
+int64_t convasr_edit_distance_long_workspace_bytes(int N, int La, int Lb);
+int convasr_edit_distance_long(const int32_t* a, const int32_t* a_lengths, const int32_t* b, const int32_t* b_lengths, int32_t* distance,
+                               void* workspace, int64_t workspace_bytes, int N, int La, int Lb, void* stream);
+
 /* ---- Two-channel diarization: diarization.py:58-99 (select_speaker, a channel-energy diarizer with a primitive VAD), models.py:777-785
  * (rle1d, which turns its masks into segments), diarization.py:175-201 (the counts behind speaker_error).  Every result is exact: maxima,
  * comparisons, integer sums, and one IEEE add and divide per channel and position. --------------------------------------------------------- */
