@@ -70,6 +70,71 @@ def xlen_f32(xlen, device):
 	return xlen.to(device = device, dtype = torch.float32).contiguous()
 
 
+# ------------------------------------------------------------------------------------------------ host plumbing: argument arrays, library queries, lengths, per-call workspaces
+
+def _ptr_array(items):
+	arr = (ctypes.c_void_p * max(len(items), 1))()
+	for i, t in enumerate(items):
+		arr[i] = None if t is None else t.data_ptr()
+	return arr
+
+
+def _int_array(vals):
+	return (ctypes.c_int * max(len(vals), 1))(*[int(v) for v in vals])
+
+
+def _float_array(vals):
+	return (ctypes.c_float * max(len(vals), 1))(*[float(v) for v in vals])
+
+
+_queries = {}
+
+
+def _cached_query(name, *args, ask = None):
+	"""The library's answer to a pure question about integer arguments (a row count, a workspace size, "is this shape inside the kernel's
+	envelope?"), asked once per distinct arguments.  Unbounded: one entry per shape the process meets.  ask: what answers in place of the
+	entry point itself, where that does not take the (hashable) arguments as they stand -- arrays, an out-parameter."""
+	r = _queries.get((name, ) + args)
+	if r is None:
+		r = _queries[(name, ) + args] = (ask or getattr(_lib.load(), name))(*args)
+	return r
+
+
+def _query(name, *args):
+	"""_cached_query of a question the library may refuse with a negative answer: that raises ConvasrHipError with the library's message at
+	once and is never stored -- a later hit would report whatever convasr_last_error() holds by then."""
+	r = _queries.get((name, ) + args)
+	if r is None:
+		r = getattr(_lib.load(), name)(*args)
+		if r < 0:
+			raise _lib.ConvasrHipError(f'{name} failed: {_lib.load().convasr_last_error().decode()}')
+		_queries[(name, ) + args] = r
+	return r
+
+
+def _frame_lengths(name, lengths, B, T, dev):
+	"""Frames per utterance as the decoding kernels read them: (B,) int64 on dev, contiguous; None = all T frames of every utterance."""
+	lengths = torch.full((B,), T, dtype = torch.int64, device = dev) if lengths is None else torch.as_tensor(lengths).to(device = dev, dtype = torch.int64).contiguous()
+	if lengths.shape != (B,):
+		raise ValueError(f'{name}: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
+	return lengths
+
+
+def _ctc_targets(targets, in_len, tgt_len, B, dev):
+	"""Targets (B, S_max) -- a flat tensor of B * S_max labels is viewed so -- and the two length vectors as the CTC kernels read them:
+	int64 on dev, contiguous."""
+	targets, in_len, tgt_len = (t.to(device = dev, dtype = torch.int64).contiguous() for t in (targets, in_len, tgt_len))
+	return (targets.view(B, -1) if targets.ndim == 1 else targets), in_len, tgt_len
+
+
+def _call_workspace(nbytes, dev, cap = None, name = None, what = None):
+	"""Scratch for ONE call, handed back to the allocator after it -- not ops.workspace: that cache keeps its buffers for good, and these
+	run to gigabytes.  A need above cap (where the caller has one) raises, naming the entry point and the shape (`what`)."""
+	if cap is not None and nbytes > cap:
+		raise _lib.ConvasrHipError(f'{name}: {nbytes} bytes of workspace needed for {what}, above the cap of {cap}')
+	return torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)
+
+
 # ------------------------------------------------------------------------------------------------ frontend / instance norm
 
 def logmel(signal, xlen, window, mel_weight, mel_bias, nfft, hop, preemphasis = 0.97, normalize = True, denom_multiplier = 1.0):
@@ -137,7 +202,7 @@ def output_lengths(xlen, B, T, device):
 # ------------------------------------------------------------------------------------------------ conv
 
 def cout_pad(c):
-	return _lib.load().convasr_conv_cout_pad(c)
+	return _cached_query('convasr_conv_cout_pad', c)
 
 
 def weight_layout(w):
@@ -191,18 +256,6 @@ def conv_out_len(Tin, K, stride, dil, pad):
 	return (Tin + 2 * pad - dil * (K - 1) - 1) // stride + 1
 
 
-_queries = {}
-
-
-def _cached_query(name, *args):
-	"""The library's answer to a pure question about integer arguments (a row count, a workspace size, "is this shape inside the kernel's
-	envelope?"), asked once per distinct arguments.  Unbounded: one entry per shape the process meets."""
-	r = _queries.get((name, ) + args)
-	if r is None:
-		r = _queries[(name, ) + args] = getattr(_lib.load(), name)(*args)
-	return r
-
-
 def _conv_stats_max_rows(B, Tout):
 	return _cached_query('convasr_conv_stats_max_rows', B, Tout)
 
@@ -226,6 +279,28 @@ class ConvStats:
 		return out
 
 
+SPLITK = os.environ.get('CONVASR_NO_SPLITK') != '1'  # A/B hook: small-batch inference launches cut over the input channels
+
+
+def _splitk_plan(dtype, B, Cin, Cout, Tout, K):
+	"""(splits, workspace bytes) of convasr_conv1d_fwd_splitk_plan, whose byte count comes back through an out-parameter."""
+	nb = ctypes.c_int64(0)
+	return _lib.load().convasr_conv1d_fwd_splitk_plan(dtype, B, Cin, Cout, Tout, K, ctypes.byref(nb)), nb.value
+
+
+def _conv_timer_label(v2s, flops, nbytes, same_width, one_tap = False, suffix = ''):
+	"""(family, symbol class) under which the bench's per-kernel timer books a conv launch.  v2s: the LDS-DMA kernel takes it (the family name is
+	a label: fp16 launches of the same kernel are booked under it too); same_width: 16-bit input AND output; one_tap: conv1x1.hip's launches."""
+	if not v2s:
+		return 'conv1d_igemm (other variants)', None
+	if one_tap:
+		return 'hbm:conv1x1_kernel (one-tap training launches)', None  # bound by bytes moved, booked under the HBM roofline
+	symbol = 'v2s16' if same_width else None
+	if memory_bound(flops, nbytes):
+		return 'hbm:conv1d_igemm_v2s_kernel (memory-bound launches: the 38-class decoder)', symbol
+	return 'conv1d_igemm_v2s_kernel<bf16>' + suffix, symbol
+
+
 def conv1d(x, wp, Cout, K, stride = 1, dil = 1, pad = 0, out_dtype = None, bias = None, stats = None, scale = None, shift = None, act = (_lib.ACT_NONE, 0.0, 0.0), xlen = None, Tout = None, work = None, family = None, splitk = False):
 	"""x: channels-last (B, Cin, Tin); wp: packed weights.  Returns channels-last (B, Cout, Tout).
 	splitk (the inference path's launches): a launch of a few tiles -- one online request is 4-16 workgroups per layer on 256 CUs -- is cut over the
@@ -242,31 +317,19 @@ def conv1d(x, wp, Cout, K, stride = 1, dil = 1, pad = 0, out_dtype = None, bias 
 	rows = ctypes.c_int(0)
 	launch = lambda: call('convasr_conv1d_fwd', ptr(x), ptr(wp), ptr(y), dtype_code(x.dtype), dtype_code(out_dtype), B, Cin, Cout, Tin, Tout, K, stride, dil, pad, ptr(bias), None if part is None else ptr(part.buf), ptr(scale), ptr(shift), act[0], act[1], act[2], ptr(xlen), ctypes.byref(rows) if part is not None else None, stream_ptr())
 	if splitk and SPLITK and stats is None and stride == 1 and (x.dtype in HALF_DTYPES or (x.dtype == torch.float32 and out_dtype == torch.float32)) and Cout % 8 == 0:
-		skey = (x.dtype, B, Cin, Cout, Tout, K)
-		plan = _splitk_plans.get(skey)
-		if plan is None:
-			nb = ctypes.c_int64(0)
-			plan = _splitk_plans[skey] = (_lib.load().convasr_conv1d_fwd_splitk_plan(dtype_code(x.dtype), B, Cin, Cout, Tout, K, ctypes.byref(nb)), nb.value)
+		plan = _cached_query('convasr_conv1d_fwd_splitk_plan', dtype_code(x.dtype), B, Cin, Cout, Tout, K, ask = _splitk_plan)
 		if plan[0] >= 2:
 			ws = workspace(plan[1], x.device, 'splitk')
 			launch = lambda: call('convasr_conv1d_fwd_splitk', ptr(x), ptr(wp), ptr(y), dtype_code(x.dtype), dtype_code(out_dtype), B, Cin, Cout, Tin, Tout, K, dil, pad, ptr(bias), ptr(scale), ptr(shift), act[0], act[1], act[2], ptr(xlen), plan[0], ptr(ws), stream_ptr())
-	if _lib.timer is None:  # (the labels below are for the bench's per-kernel timer only: not on the path of an ordinary step)
+	if _lib.timer is None:  # (the label is for the bench's per-kernel timer only: not on the path of an ordinary step)
 		launch()
-		if part is not None:
-			part.rows = rows.value
-			if part is not stats:
-				stats.copy_(part.totals())
-		return y
-	# which kernel the C side picks (conv.hip: convasr_conv1d_fwd -> convasr_conv1d_v2_try), for the bench's per-kernel timer only
-	label, family = family, 'conv1d_igemm_v2s_kernel<bf16>' if (x.dtype in HALF_DTYPES and stride == 1 and Cin % 64 == 0) else 'conv1d_igemm (other variants)'  # (the family name is a label: fp16 launches of the same kernel are booked under it too)
-	es, osz = x.element_size(), (2 if out_dtype in HALF_DTYPES else 4)
-	flops, nbytes_ = 2.0 * B * Tout * Cout * Cin * K if work is None else work, float(B * Tin * Cin * es + K * Cout * Cin * es + B * Tout * Cout * osz)
-	symbol = 'v2s16' if family.startswith('conv1d_igemm_v2s') and out_dtype == x.dtype else None
-	if family.startswith('conv1d_igemm_v2s') and K == 1 and pad == 0 and Cout % 128 == 0 and out_dtype == x.dtype and scale is None and act[0] == _lib.ACT_NONE and xlen is None:
-		family, symbol = 'hbm:conv1x1_kernel (one-tap training launches)', None  # conv1x1.hip takes these (csrc/conv.hip: conv1d_run); bound by bytes moved, booked under the HBM roofline
-	elif family.startswith('conv1d_igemm_v2s') and memory_bound(flops, nbytes_):
-		family = 'hbm:conv1d_igemm_v2s_kernel (memory-bound launches: the 38-class decoder)'
-	_lib.timed(label or family, flops, launch, nbytes = nbytes_, symbol = symbol)
+	else:
+		# which kernel the C side picks (conv.hip: convasr_conv1d_fwd -> convasr_conv1d_v2_try)
+		es, osz = x.element_size(), (2 if out_dtype in HALF_DTYPES else 4)
+		flops, nbytes_ = 2.0 * B * Tout * Cout * Cin * K if work is None else work, float(B * Tin * Cin * es + K * Cout * Cin * es + B * Tout * Cout * osz)
+		one_tap = K == 1 and pad == 0 and Cout % 128 == 0 and out_dtype == x.dtype and scale is None and act[0] == _lib.ACT_NONE and xlen is None  # conv1x1.hip takes these (csrc/conv.hip: conv1d_run)
+		kernel, symbol = _conv_timer_label(x.dtype in HALF_DTYPES and stride == 1 and Cin % 64 == 0, flops, nbytes_, out_dtype == x.dtype, one_tap)
+		_lib.timed(family or kernel, flops, launch, nbytes = nbytes_, symbol = symbol)
 	if part is not None:
 		part.rows = rows.value
 		if part is not stats:
@@ -274,12 +337,25 @@ def conv1d(x, wp, Cout, K, stride = 1, dil = 1, pad = 0, out_dtype = None, bias 
 	return y
 
 
-SPLITK = os.environ.get('CONVASR_NO_SPLITK') != '1'  # A/B hook: small-batch inference launches cut over the input channels
-_splitk_plans = {}
-
-
-def _int_array(vals):
-	return (ctypes.c_int * max(len(vals), 1))(*[int(v) for v in vals])
+def conv1d_dgrad_bn_reduce(dy, packed_dgrad, Cin, K, dil, pad, bn_y, bn_scale, bn_shift, bn_mean, bn_invstd, act, dropout_p, seed, offset, xlen, bn_sums, work = None, gate = None, step_key = None):
+	"""dx = dgrad(dy) with pass 1 of the consumer layer's batch-norm backward fused into the epilogue (bn_sums += per-channel sums).
+	Returns dx, or None when the shape is outside the fused kernel's envelope (nothing was launched)."""
+	B, Cout, Tdy = dy.shape
+	T = conv_out_len(Tdy, K, 1, dil, pad)
+	assert is_cl(dy) and dy.dtype in HALF_DTYPES and is_cl(bn_y) and bn_y.dtype == dy.dtype and tuple(bn_y.shape) == (B, Cin, T) and isinstance(bn_sums, ConvStats) and bn_sums.fits(Cin, B, T, dy.device), (dy.shape, bn_y.shape, Cin, T)
+	rows = ctypes.c_int(0)
+	dx = empty_cl(B, Cin, T, dy.dtype, dy.device)
+	rc = [0]
+	def run():
+		rc[0] = _lib.call_rc('convasr_conv1d_dgrad_bn_reduce', ptr(dy), ptr(packed_dgrad), ptr(dx), dtype_code(dy.dtype), B, Cout, Cin, Tdy, T, K, dil, pad, ptr(bn_y), ptr(bn_scale), ptr(bn_shift), ptr(bn_mean), ptr(bn_invstd), act[0], act[1], act[2], float(dropout_p), int(seed), int(offset), step_key, ptr(xlen), ptr(bn_sums.buf), ctypes.byref(rows), ptr(gate), stream_ptr())
+	if _lib.timer is None:
+		run()
+	else:
+		flops, nbytes_ = 2.0 * B * T * Cout * Cin * K if work is None else work, float(B * Tdy * Cout * 2 + K * Cout * Cin * 2 + 2 * B * T * Cin * 2)
+		kernel, symbol = _conv_timer_label(Cout % 64 == 0, flops, nbytes_, True, suffix = '+bn_bwd')
+		_lib.timed(kernel, flops, run, nbytes = nbytes_, symbol = symbol)
+	bn_sums.rows = rows.value
+	return dx if rc[0] == 0 else None
 
 
 def conv1x1_grouped(xs, wps, couts, biases = None, stats = None, outs = None, accumulate = None):
@@ -307,9 +383,6 @@ def conv1x1_grouped(xs, wps, couts, biases = None, stats = None, outs = None, ac
 	return ys
 
 
-_wgrad_group_ws = {}
-
-
 def wgrad1x1_grouped(xs, dys, dws, zeros = None, accumulate = None):
 	"""dws[i] (Cout_i, Cin_i, 1) fp32 (+)= the one-tap weight gradient of (xs[i], dys[i]); zeros[i] (optional): a (Cout_i,) fp32 tensor set to
 	zero (the branch's bias gradient).  One dispatch + one combine for all problems.  Returns False (nothing launched) outside the envelope."""
@@ -321,10 +394,7 @@ def wgrad1x1_grouped(xs, dys, dws, zeros = None, accumulate = None):
 		return False
 	for dw, ci, co in zip(dws, cins, couts):
 		assert dw.dtype == torch.float32 and tuple(dw.shape) == (co, ci, 1) and (dw.is_contiguous() or (dw.stride(0) == ci and dw.stride(1) == 1)), (dw.shape, dw.stride())
-	key = (tuple(cins), tuple(couts), B, T)
-	nb = _wgrad_group_ws.get(key)
-	if nb is None:
-		nb = _wgrad_group_ws[key] = _lib.load().convasr_wgrad1x1_grouped_workspace_bytes(n, _int_array(cins), _int_array(couts), B, T)
+	nb = _cached_query('convasr_wgrad1x1_grouped_workspace_bytes', tuple(cins), tuple(couts), B, T, ask = lambda ci, co, B, T: _lib.load().convasr_wgrad1x1_grouped_workspace_bytes(len(ci), _int_array(ci), _int_array(co), B, T))
 	ws = workspace(nb, xs[0].device, 'wgrad')
 	_lib.timed('conv1d_wgrad', 2.0 * B * T * sum(ci * co for ci, co in zip(cins, couts)), lambda: call('convasr_wgrad1x1_grouped', n, _ptr_array(xs), _ptr_array(dys), _ptr_array(dws), _ptr_array(zeros) if zeros else None,
 		_int_array(cins), _int_array(couts), _int_array(accumulate) if accumulate else None, ptr(ws), dtype_code(dt), B, T, stream_ptr()))
@@ -359,7 +429,6 @@ def workspace(nbytes, device, tag = 'default'):
 
 def fold2_geometry(K, pad):
 	"""(K', P') of the stride-1 conv over the (T / 2, 2 Cin) view that equals a stride-2 conv (K, pad); include/convasr_hip.h."""
-	import ctypes
 	kf, pf = ctypes.c_int(0), ctypes.c_int(0)
 	call('convasr_fold2_geometry', K, pad, ctypes.byref(kf), ctypes.byref(pf))
 	return kf.value, pf.value
@@ -448,7 +517,7 @@ def colsum(y, out, accumulate = False):
 	"""out (C,) fp32 (+)= sum over (b, t) of a channels-last (B, C, T) tensor: a conv's bias gradient on its own."""
 	B, C, T = y.shape
 	assert is_cl(y) and out.dtype == torch.float32 and out.numel() == C and out.is_contiguous()
-	ws = workspace(_lib.load().convasr_colsum_workspace_bytes(B * T, C), y.device, 'colsum')
+	ws = workspace(_cached_query('convasr_colsum_workspace_bytes', B * T, C), y.device, 'colsum')
 	call('convasr_colsum', ptr(y), dtype_code(y.dtype), B * T, C, ptr(out), ptr(ws), int(accumulate), stream_ptr())
 	return out
 
@@ -500,7 +569,7 @@ def grouped_conv1d_wgrad(x, dy, y_act, dw, dbias, groups, stride = 1, pad = 0, a
 	B, Cin, Tin = x.shape
 	Cout, Tout, K = dy.shape[1], dy.shape[2], dw.shape[2]
 	assert is_cl(x) and is_cl(dy) and dw.dtype == torch.float32 and tuple(dw.shape) == (Cout, Cin // groups, K)
-	ws = workspace(_lib.load().convasr_grouped_conv1d_wgrad_workspace_bytes(B, Cin, Cout, K, groups), x.device, 'grouped_wgrad')
+	ws = workspace(_cached_query('convasr_grouped_conv1d_wgrad_workspace_bytes', B, Cin, Cout, K, groups), x.device, 'grouped_wgrad')
 	call('convasr_grouped_conv1d_wgrad', ptr(x), ptr(dy), ptr(y_act), ptr(dw), dw.stride(0), dw.stride(1), dw.stride(2), ptr(dbias), ptr(ws), dtype_code(x.dtype), B, Cin, Cout, Tin, Tout, K, stride, pad, groups, int(accumulate), stream_ptr())
 	return dw
 
@@ -517,10 +586,6 @@ def bn_finalize(stats, n, gamma, beta, running_mean, running_var, momentum, eps,
 	o = out.data_ptr()
 	call('convasr_bn_finalize', ptr(buf), rows, n, ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(momentum), float(eps), o, o + 4 * C, o + 8 * C, o + 12 * C, C, ptr(num_batches_tracked), stream_ptr())
 	return out
-
-
-def _float_array(vals):
-	return (ctypes.c_float * max(len(vals), 1))(*[float(v) for v in vals])
 
 
 def bn_finalize_grouped(stats, n, gammas, betas, running_means, running_vars, momenta, epss, num_batches_tracked):
@@ -547,7 +612,7 @@ def bn_bwd_reduce_many(dz, gate, dropout_p, ys, means, invstds, gammas, coefs, d
 	assert is_cl(dz) and dz.dtype in HALF_DTYPES and all(is_cl(y) and y.dtype == dz.dtype and y.shape == dz.shape for y in ys) and gate.dtype == torch.uint8 and gate.numel() * 8 == dz.numel()
 	g = empty_cl(B, C, T, dz.dtype, dz.device)
 	k = len(ys)
-	ws = workspace(_lib.load().convasr_bn_bwd_reduce_many_workspace_bytes(k, B, T, C), dz.device, 'bn_bwd')
+	ws = workspace(_cached_query('convasr_bn_bwd_reduce_many_workspace_bytes', k, B, T, C), dz.device, 'bn_bwd')
 	_lib.timed('hbm:bn_act_bwd_reduce_kernel', 0.0, lambda: call('convasr_bn_bwd_reduce_many', ptr(dz), ptr(gate), float(dropout_p), ptr(g), k, _ptr_array(ys), _ptr_array(means), _ptr_array(invstds), _ptr_array(gammas),
 		_ptr_array(coefs), _ptr_array(dgammas), _ptr_array(dbetas), _int_array(accumulate), ptr(ws), dtype_code(dz.dtype), B, T, C, stream_ptr()), nbytes = float(B * T * C * dz.element_size() * (2 + k)))
 	return g
@@ -569,14 +634,6 @@ def bn_eval_scale_shift(gamma, beta, running_mean, running_var, eps):
 	return out
 
 
-def _ptr_array(items):
-	import ctypes
-	arr = (ctypes.c_void_p * max(len(items), 1))()
-	for i, t in enumerate(items):
-		arr[i] = None if t is None else t.data_ptr()
-	return arr
-
-
 def bn_act(y, scale, shift, act, xlen = None, res = (), rscale = (), rshift = (), dropout_p = 0.0, seed = 0, offset = 0, out = None, gate = None, step_key = None, planes = None):
 	"""gate (optional uint8 (B*T*C/8,)): receives one bit per element, set iff the gradient passes it (include/convasr_hip.h).
 	step_key (optional, here and in the backward passes): device address (int) of the per-step dropout key word (functional.begin_step).
@@ -585,17 +642,14 @@ def bn_act(y, scale, shift, act, xlen = None, res = (), rscale = (), rshift = ()
 	B, C, T = y.shape
 	assert gate is None or (gate.dtype == torch.uint8 and gate.numel() * 8 == B * C * T and gate.is_contiguous())
 	assert is_cl(y) and all(is_cl(r) and r.dtype == y.dtype for r in res)
+	# the two forms share one signature: (entry point, result, its dtype, bytes moved per element for the bench's timer)
 	if planes is not None:
 		assert y.dtype == torch.float32 and planes in HALF_DTYPES and out is None and scale is not None and act[0] != _lib.ACT_LEAKY_RELU
-		z3 = empty_cl(B, 3 * C, T, planes, y.device)
-		_lib.timed('hbm:bn_act_fwd_kernel', 0.0, lambda: call('convasr_bn_act_fwd_split3', ptr(y), ptr(z3), dtype_code(planes), ptr(scale), ptr(shift), len(res), _ptr_array(res), _ptr_array(rscale) if rscale else None, _ptr_array(rshift) if rshift else None, act[0], act[1], act[2], float(dropout_p), int(seed), int(offset), step_key, ptr(xlen), B, T, C, ptr(gate), stream_ptr()), nbytes = float(B * T * C * (10 + 4 * len(res))))
-		return z3
-	z = out if out is not None else empty_cl(B, C, T, y.dtype, y.device)
-	_lib.timed('hbm:bn_act_fwd_kernel', 0.0, lambda: call('convasr_bn_act_fwd', ptr(y), ptr(z), dtype_code(y.dtype), ptr(scale), ptr(shift), len(res), _ptr_array(res), _ptr_array(rscale) if rscale else None, _ptr_array(rshift) if rshift else None, act[0], act[1], act[2], float(dropout_p), int(seed), int(offset), step_key, ptr(xlen), B, T, C, ptr(gate), stream_ptr()), nbytes = float(B * T * C * y.element_size() * (2 + len(res))))
+		entry, z, zdtype, per_elem = 'convasr_bn_act_fwd_split3', empty_cl(B, 3 * C, T, planes, y.device), planes, 10 + 4 * len(res)
+	else:
+		entry, z, zdtype, per_elem = 'convasr_bn_act_fwd', out if out is not None else empty_cl(B, C, T, y.dtype, y.device), y.dtype, y.element_size() * (2 + len(res))
+	_lib.timed('hbm:bn_act_fwd_kernel', 0.0, lambda: call(entry, ptr(y), ptr(z), dtype_code(zdtype), ptr(scale), ptr(shift), len(res), _ptr_array(res), _ptr_array(rscale) if rscale else None, _ptr_array(rshift) if rshift else None, act[0], act[1], act[2], float(dropout_p), int(seed), int(offset), step_key, ptr(xlen), B, T, C, ptr(gate), stream_ptr()), nbytes = float(B * T * C * per_elem))
 	return z
-
-
-_bn_bwd_ws_bytes = {}
 
 
 def bn_act_bwd_reduce(dz, y, scale, shift, mean, invstd, act, xlen = None, res = (), rscale = (), rshift = (), rmean = (), rinvstd = (), rsums = (), dropout_p = 0.0, seed = 0, offset = 0, sums = None, write_g = True, gamma = None, coef = None, dgamma = None, dbeta = None, accumulate = False, gate = None, step_key = None):
@@ -603,10 +657,7 @@ def bn_act_bwd_reduce(dz, y, scale, shift, mean, invstd, act, xlen = None, res =
 	B, C, T = y.shape
 	assert is_cl(y) and is_cl(dz) and dz.dtype == y.dtype and (gate is None or (not write_g and not res))
 	g = empty_cl(B, C, T, y.dtype, y.device) if write_g else None
-	nb = _bn_bwd_ws_bytes.get((B, T, C))
-	if nb is None:
-		nb = _bn_bwd_ws_bytes[(B, T, C)] = _lib.load().convasr_bn_bwd_workspace_bytes(B, T, C)
-	ws = workspace(nb, y.device, 'bn_bwd')
+	ws = workspace(_cached_query('convasr_bn_bwd_workspace_bytes', B, T, C), y.device, 'bn_bwd')
 	_lib.timed('hbm:bn_act_bwd_reduce_kernel', 0.0, lambda: call('convasr_bn_act_bwd_reduce', ptr(dz), ptr(y), ptr(g), dtype_code(y.dtype), ptr(scale), ptr(shift), ptr(mean), ptr(invstd), len(res), _ptr_array(res), _ptr_array(rscale) if rscale else None, _ptr_array(rshift) if rshift else None, _ptr_array(rmean) if rmean else None, _ptr_array(rinvstd) if rinvstd else None, _ptr_array(rsums) if rsums else None, act[0], act[1], act[2], float(dropout_p), int(seed), int(offset), step_key, ptr(xlen), ptr(sums), ptr(ws), ptr(gamma), ptr(coef), ptr(dgamma), ptr(dbeta), int(accumulate), B, T, C, ptr(gate), stream_ptr()), nbytes = float(B * T * C * y.element_size() * (2 + len(res) + (1 if write_g else 0))))
 	return g
 
@@ -616,18 +667,16 @@ def bn_act_bwd_apply(dz_or_g, y, coef, from_dz, scale = None, shift = None, act 
 	would produce -- written by this pass itself; hi_only: as the dense (B, C, T) tensor of that type instead (dy rounded once: the operand of a
 	one-product backward)."""
 	B, C, T = y.shape
-	if planes is not None and hi_only:
-		assert y.dtype == torch.float32 and planes in HALF_DTYPES and out is None
-		dy16 = empty_cl(B, C, T, planes, y.device)
-		_lib.timed('hbm:bn_act_bwd_apply_kernel', 0.0, lambda: call('convasr_bn_act_bwd_apply_to_half', ptr(dz_or_g), ptr(y), ptr(dy16), dtype_code(planes), ptr(coef), int(from_dz), ptr(scale), ptr(shift), act[0], act[1], act[2], float(dropout_p), int(seed), int(offset), step_key, ptr(xlen), B, T, C, ptr(gate), stream_ptr()), nbytes = float(B * T * C * 10))
-		return dy16
+	# the three forms share one signature: (entry point, result, its dtype, bytes moved per element for the bench's timer)
 	if planes is not None:
 		assert y.dtype == torch.float32 and planes in HALF_DTYPES and out is None
-		dy3 = empty_cl(B, 3 * C, T, planes, y.device)
-		_lib.timed('hbm:bn_act_bwd_apply_kernel', 0.0, lambda: call('convasr_bn_act_bwd_apply_split3', ptr(dz_or_g), ptr(y), ptr(dy3), dtype_code(planes), ptr(coef), int(from_dz), ptr(scale), ptr(shift), act[0], act[1], act[2], float(dropout_p), int(seed), int(offset), step_key, ptr(xlen), B, T, C, ptr(gate), stream_ptr()), nbytes = float(B * T * C * 14))
-		return dy3
-	dy = out if out is not None else empty_cl(B, C, T, y.dtype, y.device)
-	_lib.timed('hbm:bn_act_bwd_apply_kernel', 0.0, lambda: call('convasr_bn_act_bwd_apply', ptr(dz_or_g), ptr(y), ptr(dy), dtype_code(y.dtype), ptr(coef), int(from_dz), ptr(scale), ptr(shift), act[0], act[1], act[2], float(dropout_p), int(seed), int(offset), step_key, ptr(xlen), B, T, C, ptr(gate), stream_ptr()), nbytes = float(B * T * C * y.element_size() * 3))
+		if hi_only:
+			entry, dy, dydtype, per_elem = 'convasr_bn_act_bwd_apply_to_half', empty_cl(B, C, T, planes, y.device), planes, 10
+		else:
+			entry, dy, dydtype, per_elem = 'convasr_bn_act_bwd_apply_split3', empty_cl(B, 3 * C, T, planes, y.device), planes, 14
+	else:
+		entry, dy, dydtype, per_elem = 'convasr_bn_act_bwd_apply', out if out is not None else empty_cl(B, C, T, y.dtype, y.device), y.dtype, y.element_size() * 3
+	_lib.timed('hbm:bn_act_bwd_apply_kernel', 0.0, lambda: call(entry, ptr(dz_or_g), ptr(y), ptr(dy), dtype_code(dydtype), ptr(coef), int(from_dz), ptr(scale), ptr(shift), act[0], act[1], act[2], float(dropout_p), int(seed), int(offset), step_key, ptr(xlen), B, T, C, ptr(gate), stream_ptr()), nbytes = float(B * T * C * per_elem))
 	return dy
 
 
@@ -636,6 +685,12 @@ def bn_bwd_apply(g, y, gamma, mean, invstd, sums, dgamma = None, dbeta = None, a
 	dy = (g if inplace else empty_cl(B, C, T, y.dtype, y.device)) if need_dy else None
 	call('convasr_bn_bwd_apply', ptr(g), ptr(y), ptr(dy), dtype_code(y.dtype), ptr(gamma), ptr(mean), ptr(invstd), ptr(sums), ptr(dgamma), ptr(dbeta), int(accumulate), B, T, C, stream_ptr())
 	return dy
+
+
+def bn_bwd_finalize(sums, gamma, mean, invstd, n, coef = None, dgamma = None, dbeta = None, accumulate = False):
+	"""sums: the ConvStats the fused dgrad epilogue filled (partial rows of sum g, sum g*xhat), or a (2 C,) fp64 tensor of totals."""
+	buf, rows, C = (sums.buf, sums.rows, sums.C) if isinstance(sums, ConvStats) else (sums, 1, sums.numel() // 2)
+	call('convasr_bn_bwd_finalize', ptr(buf), rows, ptr(gamma), ptr(mean), ptr(invstd), ptr(coef), ptr(dgamma), ptr(dbeta), int(accumulate), int(n), C, stream_ptr())
 
 
 # ------------------------------------------------------------------------------------------------ head
@@ -655,68 +710,6 @@ def log_softmax_bwd(grad_lp, log_probs):
 	out = empty_cl(B, C, T, torch.float32, log_probs.device)
 	call('convasr_log_softmax_bwd', ptr(grad_lp), ptr(log_probs), ptr(out), B * T, C, stream_ptr())
 	return out
-
-
-def ctc_loss(log_probs, targets, olen, ylen, blank, need_grad = True):
-	"""log_probs channels-last fp32 (B, C, T); returns (nll (B,), grad channels-last (B, C, T) or None)."""
-	B, C, T = log_probs.shape
-	assert is_cl(log_probs) and log_probs.dtype == torch.float32
-	dev = log_probs.device
-	targets = targets.to(device = dev, dtype = torch.int64).contiguous()
-	if targets.ndim == 1:
-		targets = targets.view(B, -1)
-	olen = olen.to(device = dev, dtype = torch.int64).contiguous()
-	ylen = ylen.to(device = dev, dtype = torch.int64).contiguous()
-	S_max = targets.shape[1]
-	if not _lib.load().convasr_ctc_loss_supported(B, T, C, S_max):  # more than 1,023 labels, or more frames than the one-workgroup kernel's LDS slots hold: the tiled kernel
-		return ctc_loss_long(log_probs, targets, olen, ylen, blank, need_grad = need_grad)
-	nbytes = _lib.load().convasr_ctc_workspace_bytes(B, T, S_max)
-	if nbytes < 0:
-		raise _lib.ConvasrHipError(f'ctc_loss: target length {S_max} unsupported')
-	ws = workspace(nbytes, dev, 'ctc')
-	nll = torch.empty(B, dtype = torch.float32, device = dev)
-	grad = empty_cl(B, C, T, torch.float32, dev) if need_grad else None
-	call('convasr_ctc_loss', ptr(log_probs), ptr(targets), ptr(olen), ptr(ylen), ptr(nll), ptr(grad), ptr(ws), B, T, C, S_max, blank, stream_ptr())
-	return nll, grad
-
-
-CTC_LONG_WORKSPACE_CAP = 16 << 30  # bytes of workspace one convasr_ctc_loss_long call may take; a resource bound like ALIGN_LONG_WORKSPACE_CAP, not a measurement
-
-
-def ctc_loss_long_tiles():
-	"""(states per block, default frames per chunk) of convasr_ctc_loss_long's tiles (tests straddle them)."""
-	lib = _lib.load()
-	return lib.convasr_ctc_loss_long_states_per_block(), lib.convasr_ctc_loss_long_chunk_frames()
-
-
-def ctc_loss_long(log_probs, targets, olen, ylen, blank, need_grad = True, chunk_frames = 0, workspace_cap = CTC_LONG_WORKSPACE_CAP):
-	"""ctc_loss for whole recordings (include/convasr_hip.h: convasr_ctc_loss_long): up to 131,071 labels and 2^20 frames, the same tensors in
-	and out as ctc_loss, which sends here every shape its own kernel refuses.  chunk_frames: 0 = the default tile length, 16 .. 4096 forces
-	it (the result does not depend on it).  The workspace (two whole fp32 lattices: about 4.4 GB for ten minutes) is allocated for this call
-	and goes back to the allocator; a need above workspace_cap raises ConvasrHipError.  Not under stream capture."""
-	require_cuda(log_probs)
-	B, C, T = log_probs.shape
-	assert is_cl(log_probs) and log_probs.dtype == torch.float32
-	dev = log_probs.device
-	if _capturing[0] or torch.cuda.is_current_stream_capturing():
-		raise _lib.ConvasrHipError(f'ctc_loss_long: B {B}, T {T} is beyond the one-workgroup CTC kernel, and the tiled kernel (hundreds of launches over a workspace allocated per call) cannot be captured into a graph: run this step eagerly')
-	targets = targets.to(device = dev, dtype = torch.int64).contiguous()
-	if targets.ndim == 1:
-		targets = targets.view(B, -1)
-	olen = olen.to(device = dev, dtype = torch.int64).contiguous()
-	ylen = ylen.to(device = dev, dtype = torch.int64).contiguous()
-	S_max = targets.shape[1]
-	lib = _lib.load()
-	nbytes = lib.convasr_ctc_loss_long_workspace_bytes(B, T, C, S_max)
-	if nbytes < 0:
-		raise _lib.ConvasrHipError(f'convasr_ctc_loss_long_workspace_bytes failed: {lib.convasr_last_error().decode()}')
-	if nbytes > workspace_cap:
-		raise _lib.ConvasrHipError(f'ctc_loss_long: {nbytes} bytes of workspace needed for B {B}, T {T}, S_max {S_max}, above the cap of {workspace_cap}')
-	nll = torch.empty(B, dtype = torch.float32, device = dev)
-	grad = empty_cl(B, C, T, torch.float32, dev) if need_grad else None
-	ws = torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)  # (not ops.workspace: that cache keeps its buffers for good)
-	call('convasr_ctc_loss_long', ptr(log_probs), ptr(targets), ptr(olen), ptr(ylen), ptr(nll), ptr(grad), ptr(ws), nbytes, B, T, C, S_max, int(blank), int(chunk_frames), stream_ptr())
-	return nll, grad
 
 
 def scale_rows(grad, gscale, gdiv = None):
@@ -787,12 +780,59 @@ def argmax(log_probs):
 	return idx
 
 
+# ------------------------------------------------------------------------------------------------ CTC loss
+
+def ctc_loss(log_probs, targets, olen, ylen, blank, need_grad = True):
+	"""log_probs channels-last fp32 (B, C, T); returns (nll (B,), grad channels-last (B, C, T) or None)."""
+	B, C, T = log_probs.shape
+	assert is_cl(log_probs) and log_probs.dtype == torch.float32
+	dev = log_probs.device
+	S_max = targets.numel() // B if targets.ndim == 1 else targets.shape[1]
+	if not _cached_query('convasr_ctc_loss_supported', B, T, C, S_max):  # more than 1,023 labels, or more frames than the one-workgroup kernel's LDS slots hold: the tiled kernel
+		return ctc_loss_long(log_probs, targets, olen, ylen, blank, need_grad = need_grad)
+	targets, olen, ylen = _ctc_targets(targets, olen, ylen, B, dev)
+	ws = workspace(_cached_query('convasr_ctc_workspace_bytes', B, T, S_max), dev, 'ctc')  # (never refused here: convasr_ctc_loss_supported is false for every S_max this query refuses)
+	nll = torch.empty(B, dtype = torch.float32, device = dev)
+	grad = empty_cl(B, C, T, torch.float32, dev) if need_grad else None
+	call('convasr_ctc_loss', ptr(log_probs), ptr(targets), ptr(olen), ptr(ylen), ptr(nll), ptr(grad), ptr(ws), B, T, C, S_max, blank, stream_ptr())
+	return nll, grad
+
+
+CTC_LONG_WORKSPACE_CAP = 16 << 30  # bytes of workspace one convasr_ctc_loss_long call may take; a resource bound like ALIGN_LONG_WORKSPACE_CAP, not a measurement
+
+
+def ctc_loss_long_tiles():
+	"""(states per block, default frames per chunk) of convasr_ctc_loss_long's tiles (tests straddle them)."""
+	return _cached_query('convasr_ctc_loss_long_states_per_block'), _cached_query('convasr_ctc_loss_long_chunk_frames')
+
+
+def ctc_loss_long(log_probs, targets, olen, ylen, blank, need_grad = True, chunk_frames = 0, workspace_cap = CTC_LONG_WORKSPACE_CAP):
+	"""ctc_loss for whole recordings (include/convasr_hip.h: convasr_ctc_loss_long): up to 131,071 labels and 2^20 frames, the same tensors in
+	and out as ctc_loss, which sends here every shape its own kernel refuses.  chunk_frames: 0 = the default tile length, 16 .. 4096 forces
+	it (the result does not depend on it).  The workspace (two whole fp32 lattices: about 4.4 GB for ten minutes) is allocated for this call
+	and goes back to the allocator; a need above workspace_cap raises ConvasrHipError.  Not under stream capture."""
+	require_cuda(log_probs)
+	B, C, T = log_probs.shape
+	assert is_cl(log_probs) and log_probs.dtype == torch.float32
+	dev = log_probs.device
+	if _capturing[0] or torch.cuda.is_current_stream_capturing():
+		raise _lib.ConvasrHipError(f'ctc_loss_long: B {B}, T {T} is beyond the one-workgroup CTC kernel, and the tiled kernel (hundreds of launches over a workspace allocated per call) cannot be captured into a graph: run this step eagerly')
+	targets, olen, ylen = _ctc_targets(targets, olen, ylen, B, dev)
+	S_max = targets.shape[1]
+	nbytes = _query('convasr_ctc_loss_long_workspace_bytes', B, T, C, S_max)
+	ws = _call_workspace(nbytes, dev, workspace_cap, 'ctc_loss_long', f'B {B}, T {T}, S_max {S_max}')
+	nll = torch.empty(B, dtype = torch.float32, device = dev)
+	grad = empty_cl(B, C, T, torch.float32, dev) if need_grad else None
+	call('convasr_ctc_loss_long', ptr(log_probs), ptr(targets), ptr(olen), ptr(ylen), ptr(nll), ptr(grad), ptr(ws), nbytes, B, T, C, S_max, int(blank), int(chunk_frames), stream_ptr())
+	return nll, grad
+
+
 # ------------------------------------------------------------------------------------------------ optimizer
 
 def sumsq(flat_grad, out = None, norm_out = None, norm_scale = 1.0, loss_scaler = None):
 	"""out[0] = sum of squares (fp64); norm_out (1-element fp32, optional) = sqrt(out) * norm_scale (/ the loss scaler's scale)."""
 	out = out if out is not None else torch.empty(1, dtype = torch.float64, device = flat_grad.device)
-	ws = workspace(_lib.load().convasr_sumsq_workspace_bytes(), flat_grad.device, 'sumsq')
+	ws = workspace(_cached_query('convasr_sumsq_workspace_bytes'), flat_grad.device, 'sumsq')
 	call('convasr_sumsq', ptr(flat_grad), flat_grad.numel(), ptr(out), ptr(ws), ptr(norm_out), float(norm_scale), ptr(loss_scaler), stream_ptr())
 	return out
 
@@ -823,36 +863,6 @@ def adamw_step(p, g, exp_avg, exp_avg_sq, n, sumsq_buf, max_norm, lr, beta1, bet
 	call('convasr_adamw_step', ptr(p), ptr(g), ptr(exp_avg), ptr(exp_avg_sq), n, ptr(sumsq_buf), float(max_norm), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), ptr(step_in), ptr(step_out), ptr(loss_gate), float(grad_scale), ptr(p16), _lib.BF16 if p16 is None else dtype_code(p16.dtype), ptr(s_in), ptr(s_out), ptr(lr_dev), stream_ptr())
 
 
-def conv1d_dgrad_bn_reduce(dy, packed_dgrad, Cin, K, dil, pad, bn_y, bn_scale, bn_shift, bn_mean, bn_invstd, act, dropout_p, seed, offset, xlen, bn_sums, work = None, gate = None, step_key = None):
-	"""dx = dgrad(dy) with pass 1 of the consumer layer's batch-norm backward fused into the epilogue (bn_sums += per-channel sums).
-	Returns dx, or None when the shape is outside the fused kernel's envelope (nothing was launched)."""
-	import ctypes
-	B, Cout, Tdy = dy.shape
-	T = conv_out_len(Tdy, K, 1, dil, pad)
-	assert is_cl(dy) and dy.dtype in HALF_DTYPES and is_cl(bn_y) and bn_y.dtype == dy.dtype and tuple(bn_y.shape) == (B, Cin, T) and isinstance(bn_sums, ConvStats) and bn_sums.fits(Cin, B, T, dy.device), (dy.shape, bn_y.shape, Cin, T)
-	rows = ctypes.c_int(0)
-	dx = empty_cl(B, Cin, T, dy.dtype, dy.device)
-	rc = [0]
-	def run():
-		rc[0] = _lib.call_rc('convasr_conv1d_dgrad_bn_reduce', ptr(dy), ptr(packed_dgrad), ptr(dx), dtype_code(dy.dtype), B, Cout, Cin, Tdy, T, K, dil, pad, ptr(bn_y), ptr(bn_scale), ptr(bn_shift), ptr(bn_mean), ptr(bn_invstd), act[0], act[1], act[2], float(dropout_p), int(seed), int(offset), step_key, ptr(xlen), ptr(bn_sums.buf), ctypes.byref(rows), ptr(gate), stream_ptr())
-	family = 'conv1d_igemm_v2s_kernel<bf16>+bn_bwd' if Cout % 64 == 0 else 'conv1d_igemm (other variants)'
-	flops, nbytes_ = 2.0 * B * T * Cout * Cin * K if work is None else work, float(B * Tdy * Cout * 2 + K * Cout * Cin * 2 + 2 * B * T * Cin * 2)
-	symbol = 'v2s16' if family.startswith('conv1d_igemm_v2s') else None
-	if family.startswith('conv1d_igemm_v2s') and memory_bound(flops, nbytes_):
-		family = 'hbm:conv1d_igemm_v2s_kernel (memory-bound launches: the 38-class decoder)'
-	_lib.timed(family, flops, run, nbytes = nbytes_, symbol = symbol)
-	bn_sums.rows = rows.value
-	return dx if rc[0] == 0 else None
-
-
-def bn_bwd_finalize(sums, gamma, mean, invstd, n, coef = None, dgamma = None, dbeta = None, accumulate = False):
-	"""sums: the ConvStats the fused dgrad epilogue filled (partial rows of sum g, sum g*xhat), or a (2 C,) fp64 tensor of totals."""
-	buf, rows, C = (sums.buf, sums.rows, sums.C) if isinstance(sums, ConvStats) else (sums, 1, sums.numel() // 2)
-	call('convasr_bn_bwd_finalize', ptr(buf), rows, ptr(gamma), ptr(mean), ptr(invstd), ptr(coef), ptr(dgamma), ptr(dbeta), int(accumulate), int(n), C, stream_ptr())
-
-
-# ------------------------------------------------------------------------------------------------ SURVEY 8(f) "next" rows
-
 def novograd_work_table(offsets_host, device):
 	"""Static work table of the fused NovoGrad step: every tensor (segment of the arena) cut into items of bounded size.
 	Returns (items (n_items, 3) int64, seg_first (n_seg + 1,) int64, item_part (n_items,) fp64 scratch), all on `device`."""
@@ -876,17 +886,17 @@ def novograd_step(p, g, mom, ema_in, ema_out, g2, offsets, n, table, max_norm, l
 	call('convasr_novograd_step', ptr(p), ptr(g), ptr(mom), ptr(ema_in), ptr(ema_out), ptr(g2), ptr(offsets), n_seg, n, ptr(items), items.shape[0], ptr(seg_first), ptr(item_part), float(max_norm or 0.0), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(bool(dampening)), int(first), ptr(loss_gate), ptr(total_norm), float(grad_scale), ptr(p16), _lib.BF16 if p16 is None else dtype_code(p16.dtype), ptr(s_in), ptr(s_out), ptr(lr_dev), stream_ptr())
 
 
+# ------------------------------------------------------------------------------------------------ forced alignment
+
 def ctc_alignment(log_probs_btc, targets, input_lengths, target_lengths, blank):
 	"""log_probs_btc: contiguous (B, T, C) fp32 on the GPU.  Returns (B, S_max) int64 (see include/convasr_hip.h)."""
 	B, T, C = log_probs_btc.shape
 	dev = log_probs_btc.device
 	assert log_probs_btc.is_contiguous() and log_probs_btc.dtype == torch.float32
-	targets = targets.to(device = dev, dtype = torch.int64).contiguous()
-	il = input_lengths.to(device = dev, dtype = torch.int64).contiguous()
-	tl = target_lengths.to(device = dev, dtype = torch.int64).contiguous()
+	targets, il, tl = _ctc_targets(targets, input_lengths, target_lengths, B, dev)
 	S_max = targets.shape[1]
 	out = torch.empty(B, S_max, dtype = torch.int64, device = dev)
-	ws = workspace(_lib.load().convasr_ctc_alignment_workspace_bytes(B, T, S_max), dev, 'ctc_alignment')
+	ws = workspace(_lib.load().convasr_ctc_alignment_workspace_bytes(B, T, S_max), dev, 'ctc_alignment')  # (asked every time, not _cached_query: the answer follows the library's debug bits -- which of the two kernels runs -- as well as the arguments)
 	call('convasr_ctc_alignment', ptr(log_probs_btc), ptr(targets), ptr(il), ptr(tl), ptr(out), ptr(ws), B, T, C, S_max, int(blank), stream_ptr())
 	return out
 
@@ -896,8 +906,7 @@ ALIGN_LONG_WORKSPACE_CAP = 16 << 30  # bytes of workspace one convasr_ctc_alignm
 
 def ctc_alignment_long_tiles():
 	"""(states per block, default frames per chunk) of convasr_ctc_alignment_long's tiles (tests straddle them)."""
-	lib = _lib.load()
-	return lib.convasr_ctc_alignment_long_states_per_block(), lib.convasr_ctc_alignment_long_chunk_frames()
+	return _cached_query('convasr_ctc_alignment_long_states_per_block'), _cached_query('convasr_ctc_alignment_long_chunk_frames')
 
 
 def ctc_alignment_long(log_probs_btc, targets, input_lengths, target_lengths, blank, chunk_frames = 0, workspace_cap = ALIGN_LONG_WORKSPACE_CAP):
@@ -908,21 +917,16 @@ def ctc_alignment_long(log_probs_btc, targets, input_lengths, target_lengths, bl
 	dev = log_probs_btc.device
 	require_cuda(log_probs_btc)
 	assert log_probs_btc.is_contiguous() and log_probs_btc.dtype == torch.float32
-	targets = targets.to(device = dev, dtype = torch.int64).contiguous()
-	il = input_lengths.to(device = dev, dtype = torch.int64).contiguous()
-	tl = target_lengths.to(device = dev, dtype = torch.int64).contiguous()
+	targets, il, tl = _ctc_targets(targets, input_lengths, target_lengths, B, dev)
 	S_max = targets.shape[1]
-	lib = _lib.load()
-	nbytes = lib.convasr_ctc_alignment_long_workspace_bytes(B, T, S_max)
-	if nbytes < 0:
-		raise _lib.ConvasrHipError(f'convasr_ctc_alignment_long_workspace_bytes failed: {lib.convasr_last_error().decode()}')
-	if nbytes > workspace_cap:
-		raise _lib.ConvasrHipError(f'ctc_alignment_long: {nbytes} bytes of workspace needed for B {B}, T {T}, S_max {S_max}, above the cap of {workspace_cap}')
+	nbytes = _query('convasr_ctc_alignment_long_workspace_bytes', B, T, S_max)
+	ws = _call_workspace(nbytes, dev, workspace_cap, 'ctc_alignment_long', f'B {B}, T {T}, S_max {S_max}')
 	out = torch.empty(B, S_max, dtype = torch.int64, device = dev)
-	ws = torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)  # (not ops.workspace: that cache keeps its buffers for good)
 	call('convasr_ctc_alignment_long', ptr(log_probs_btc), ptr(targets), ptr(il), ptr(tl), ptr(out), ptr(ws), nbytes, B, T, C, S_max, int(blank), int(chunk_frames), stream_ptr())
 	return out
 
+
+# ------------------------------------------------------------------------------------------------ decoding
 
 def _beam_route(name, args, wide):
 	"""(entry point, workspace bytes): the LDS kernel whenever its workspace query accepts the arguments (wide None), otherwise -- or with
@@ -954,9 +958,7 @@ def ctc_beam_search(log_probs_bct, lengths, blank, beam_width, cutoff_top_n = 40
 	B, C, T = log_probs_bct.shape
 	lp = as_cl(log_probs_bct, torch.float32)
 	dev = lp.device
-	lengths = torch.full((B,), T, dtype = torch.int64, device = dev) if lengths is None else torch.as_tensor(lengths).to(device = dev, dtype = torch.int64).contiguous()
-	if lengths.shape != (B,):
-		raise ValueError(f'ctc_beam_search: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
+	lengths = _frame_lengths('ctc_beam_search', lengths, B, T, dev)
 	N = C if cutoff_top_n is None else min(int(cutoff_top_n), C)  # (ctcdecode's pruning takes min(cutoff_top_n, C) too: the reference's default 40 over its 38 classes)
 	W, topk = int(beam_width), int(topk)
 	fn, nbytes = _beam_route('ctc_beam_search', (B, T, C, W, N, topk), wide)
@@ -964,7 +966,7 @@ def ctc_beam_search(log_probs_bct, lengths, blank, beam_width, cutoff_top_n = 40
 	offsets = torch.empty(B, topk, T, dtype = torch.int32, device = dev)
 	out_lengths = torch.empty(B, topk, dtype = torch.int64, device = dev)
 	log_prob = torch.empty(B, topk, dtype = torch.float32, device = dev)
-	ws = torch.empty(nbytes, dtype = torch.uint8, device = dev)  # per call, not the grow-only cache: B x T x W nodes of 8 bytes (393 MB at 64 x 750 x 1024) go back to the allocator
+	ws = _call_workspace(nbytes, dev)  # B x T x W nodes of 8 bytes: 393 MB at 64 x 750 x 1024
 	call(fn, ptr(lp), ptr(lengths), ptr(tokens), ptr(offsets), ptr(out_lengths), ptr(log_prob), ptr(ws), B, T, C, int(blank), W, N, float(cutoff_prob), topk, stream_ptr())
 	return tokens, offsets, out_lengths, log_prob
 
@@ -983,9 +985,7 @@ def ctc_beam_search_lm(log_probs_bct, lengths, blank, beam_width, lm, alpha, bet
 		raise ValueError(f'ctc_beam_search_lm: the space class {lm.space} is the blank')
 	lp = as_cl(log_probs_bct, torch.float32)
 	dev = lp.device
-	lengths = torch.full((B,), T, dtype = torch.int64, device = dev) if lengths is None else torch.as_tensor(lengths).to(device = dev, dtype = torch.int64).contiguous()
-	if lengths.shape != (B,):
-		raise ValueError(f'ctc_beam_search_lm: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
+	lengths = _frame_lengths('ctc_beam_search_lm', lengths, B, T, dev)
 	N = C if cutoff_top_n is None else min(int(cutoff_top_n), C)
 	W, topk = int(beam_width), int(topk)
 	fn, nbytes = _beam_route('ctc_beam_search_lm', (B, T, C, W, N, topk), wide)
@@ -994,14 +994,66 @@ def ctc_beam_search_lm(log_probs_bct, lengths, blank, beam_width, lm, alpha, bet
 	offsets = torch.empty(B, topk, T, dtype = torch.int32, device = dev)
 	out_lengths = torch.empty(B, topk, dtype = torch.int64, device = dev)
 	log_prob = torch.empty(B, topk, dtype = torch.float64, device = dev)
-	ws = torch.empty(nbytes, dtype = torch.uint8, device = dev)
+	ws = _call_workspace(nbytes, dev)
 	call(fn, ptr(lp), ptr(lengths), ptr(tokens), ptr(offsets), ptr(out_lengths), ptr(log_prob), ptr(ws), B, T, C, int(blank), W, N,
 	     float(cutoff_prob), topk, ptr(t['node_mask']), ptr(t['node_child']), ptr(t['node_word']), int(t['node_word'].numel()), ptr(t['ent_pb']), ptr(t['ent_sl']),
 	     int(t['ent_sl'].shape[0]), ptr(t['slots']), int(t['slots'].shape[0]), lm.space, lm.order, lm.start_state, float(alpha), float(beta), stream_ptr())
 	return tokens, offsets, out_lengths, log_prob
 
 
-# ------------------------------------------------------------------------------------------------ validation metrics
+def ctc_greedy_collapse(path, lengths, eps, space, blank_amount_to_space = 10):
+	"""GreedyCTCGenerator.generate's collapse (time_stamps None, silence = {eps, space}, word start = space) on the device
+	(include/convasr_hip.h: convasr_ctc_greedy_collapse).  path: (B, T) int64 per-frame argmax (ops.argmax); lengths (B,) frames, or None
+	(all T).  Returns (tokens (B, T) int64, 0 past the length; out_lengths (B,) int64).  Outside the envelope it raises ConvasrHipError."""
+	require_cuda(path)
+	if path.ndim != 2 or path.dtype != torch.int64:
+		raise ValueError(f'ctc_greedy_collapse: path must be a (B, T) int64 tensor, got {tuple(path.shape)} {path.dtype}')
+	B, T = path.shape
+	dev = path.device
+	path = path.contiguous()
+	lengths = _frame_lengths('ctc_greedy_collapse', lengths, B, T, dev)
+	tokens = torch.empty(B, T, dtype = torch.int64, device = dev)
+	out_lengths = torch.empty(B, dtype = torch.int64, device = dev)
+	call('convasr_ctc_greedy_collapse', ptr(path), ptr(lengths), ptr(tokens), ptr(out_lengths), B, T, int(eps), int(space), int(blank_amount_to_space), stream_ptr())
+	return tokens, out_lengths
+
+
+def ctc_greedy_segments_chunk():
+	"""Frames per chunk of convasr_ctc_greedy_segments (one workgroup per utterance and chunk; tests straddle it)."""
+	return _cached_query('convasr_ctc_greedy_segments_chunk_frames')
+
+
+def ctc_greedy_segments(path, lengths, eps, space, blank_amount_to_space = 10, split_words = True):
+	"""GreedyCTCGenerator.generate's collapse with the frame of every token and the word segments, on the device (include/convasr_hip.h:
+	convasr_ctc_greedy_segments has the rule).  path: (B, T) int64 per-frame argmax (ops.argmax); lengths (B,) frames, or None (all T).
+	split_words: every space emitted from the path opens a segment and stands twice at its front (time stamps given); False: one segment
+	per non-empty utterance.  Returns device tensors, packed over the batch in utterance order: tokens (n,) int64, frames (n,) int32,
+	counts (2, B) int64 (tokens, then segments, per utterance), seg_first (m,) int64 (index of a segment's first token in tokens),
+	seg_begin / seg_end (m,) int32 frames.  One read-back, of the counts (16 B bytes), sizes the results.  Outside the envelope it raises
+	ConvasrHipError."""
+	require_cuda(path)
+	if path.ndim != 2 or path.dtype != torch.int64:
+		raise ValueError(f'ctc_greedy_segments: path must be a (B, T) int64 tensor, got {tuple(path.shape)} {path.dtype}')
+	B, T = path.shape
+	dev = path.device
+	path = path.contiguous()
+	lengths = _frame_lengths('ctc_greedy_segments', lengths, B, T, dev)
+	nbytes = _query('convasr_ctc_greedy_segments_workspace_bytes', B, T)
+	room = B * T * (2 if split_words else 1)
+	tokens = torch.empty(room, dtype = torch.int64, device = dev)
+	frames = torch.empty(room, dtype = torch.int32, device = dev)
+	counts = torch.empty(2, B, dtype = torch.int64, device = dev)
+	seg_first = torch.empty(B * T, dtype = torch.int64, device = dev)
+	seg_begin = torch.empty(B * T, dtype = torch.int32, device = dev)
+	seg_end = torch.empty(B * T, dtype = torch.int32, device = dev)
+	ws = _call_workspace(nbytes, dev)
+	call('convasr_ctc_greedy_segments', ptr(path), ptr(lengths), ptr(tokens), ptr(frames), ptr(counts), ptr(seg_first), ptr(seg_begin), ptr(seg_end),
+	     ptr(ws), nbytes, B, T, int(eps), int(space), int(blank_amount_to_space), int(bool(split_words)), stream_ptr())
+	n, m = counts.sum(dim = 1).tolist()
+	return tokens[:n], frames[:n], counts, seg_first[:m], seg_begin[:m], seg_end[:m]
+
+
+# ------------------------------------------------------------------------------------------------ metrics and alignment
 
 def edit_distance(hyp, hyp_lengths, ref, ref_lengths, mode = _lib.METRIC_CHARS, space = -1):
 	"""Levenshtein distances of hypotheses against references (include/convasr_hip.h: convasr_edit_distance).  hyp: (B, K, Lh) or (B, Lh)
@@ -1037,145 +1089,12 @@ def edit_distance(hyp, hyp_lengths, ref, ref_lengths, mode = _lib.METRIC_CHARS, 
 	return (distance[:, 0] if squeeze else distance), ref_units
 
 
-def ctc_greedy_collapse(path, lengths, eps, space, blank_amount_to_space = 10):
-	"""GreedyCTCGenerator.generate's collapse (time_stamps None, silence = {eps, space}, word start = space) on the device
-	(include/convasr_hip.h: convasr_ctc_greedy_collapse).  path: (B, T) int64 per-frame argmax (ops.argmax); lengths (B,) frames, or None
-	(all T).  Returns (tokens (B, T) int64, 0 past the length; out_lengths (B,) int64).  Outside the envelope it raises ConvasrHipError."""
-	require_cuda(path)
-	if path.ndim != 2 or path.dtype != torch.int64:
-		raise ValueError(f'ctc_greedy_collapse: path must be a (B, T) int64 tensor, got {tuple(path.shape)} {path.dtype}')
-	B, T = path.shape
-	dev = path.device
-	path = path.contiguous()
-	lengths = torch.full((B,), T, dtype = torch.int64, device = dev) if lengths is None else torch.as_tensor(lengths).to(device = dev, dtype = torch.int64).contiguous()
-	if lengths.shape != (B,):
-		raise ValueError(f'ctc_greedy_collapse: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
-	tokens = torch.empty(B, T, dtype = torch.int64, device = dev)
-	out_lengths = torch.empty(B, dtype = torch.int64, device = dev)
-	call('convasr_ctc_greedy_collapse', ptr(path), ptr(lengths), ptr(tokens), ptr(out_lengths), B, T, int(eps), int(space), int(blank_amount_to_space), stream_ptr())
-	return tokens, out_lengths
-
-
-def ctc_greedy_segments_chunk():
-	"""Frames per chunk of convasr_ctc_greedy_segments (one workgroup per utterance and chunk; tests straddle it)."""
-	return _lib.load().convasr_ctc_greedy_segments_chunk_frames()
-
-
-def ctc_greedy_segments(path, lengths, eps, space, blank_amount_to_space = 10, split_words = True):
-	"""GreedyCTCGenerator.generate's collapse with the frame of every token and the word segments, on the device (include/convasr_hip.h:
-	convasr_ctc_greedy_segments has the rule).  path: (B, T) int64 per-frame argmax (ops.argmax); lengths (B,) frames, or None (all T).
-	split_words: every space emitted from the path opens a segment and stands twice at its front (time stamps given); False: one segment
-	per non-empty utterance.  Returns device tensors, packed over the batch in utterance order: tokens (n,) int64, frames (n,) int32,
-	counts (2, B) int64 (tokens, then segments, per utterance), seg_first (m,) int64 (index of a segment's first token in tokens),
-	seg_begin / seg_end (m,) int32 frames.  One read-back, of the counts (16 B bytes), sizes the results.  Outside the envelope it raises
-	ConvasrHipError."""
-	require_cuda(path)
-	if path.ndim != 2 or path.dtype != torch.int64:
-		raise ValueError(f'ctc_greedy_segments: path must be a (B, T) int64 tensor, got {tuple(path.shape)} {path.dtype}')
-	B, T = path.shape
-	dev = path.device
-	path = path.contiguous()
-	lengths = torch.full((B,), T, dtype = torch.int64, device = dev) if lengths is None else torch.as_tensor(lengths).to(device = dev, dtype = torch.int64).contiguous()
-	if lengths.shape != (B,):
-		raise ValueError(f'ctc_greedy_segments: lengths of shape {tuple(lengths.shape)} for a batch of {B}')
-	lib = _lib.load()
-	nbytes = lib.convasr_ctc_greedy_segments_workspace_bytes(B, T)
-	if nbytes < 0:
-		raise _lib.ConvasrHipError(f'convasr_ctc_greedy_segments_workspace_bytes failed: {lib.convasr_last_error().decode()}')
-	room = B * T * (2 if split_words else 1)
-	tokens = torch.empty(room, dtype = torch.int64, device = dev)
-	frames = torch.empty(room, dtype = torch.int32, device = dev)
-	counts = torch.empty(2, B, dtype = torch.int64, device = dev)
-	seg_first = torch.empty(B * T, dtype = torch.int64, device = dev)
-	seg_begin = torch.empty(B * T, dtype = torch.int32, device = dev)
-	seg_end = torch.empty(B * T, dtype = torch.int32, device = dev)
-	ws = torch.empty(nbytes, dtype = torch.uint8, device = dev)
-	call('convasr_ctc_greedy_segments', ptr(path), ptr(lengths), ptr(tokens), ptr(frames), ptr(counts), ptr(seg_first), ptr(seg_begin), ptr(seg_end),
-	     ptr(ws), nbytes, B, T, int(eps), int(space), int(blank_amount_to_space), int(bool(split_words)), stream_ptr())
-	n, m = counts.sum(dim = 1).tolist()
-	return tokens[:n], frames[:n], counts, seg_first[:m], seg_begin[:m], seg_end[:m]
-
-
-# ------------------------------------------------------------------------------------------------ alignment
-
 NW_WORKSPACE_CAP = 1 << 30  # bytes of direction workspace one convasr_nw_align launch may take; a resource bound, not a measurement
 
 
 def nw_align_workspace_bytes(N, La, Lb):
 	"""convasr_nw_align_workspace_bytes: N * La * ceil(Lb / 64) * 16 + N * (La + Lb) * 4."""
-	n = _lib.load().convasr_nw_align_workspace_bytes(int(N), int(La), int(Lb))
-	if n < 0:
-		raise _lib.ConvasrHipError(f'convasr_nw_align_workspace_bytes failed: {_lib.load().convasr_last_error().decode()}')
-	return n
-
-
-def _nw_launch(a, al, b, bl, scores):
-	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
-	dev = a.device
-	W = max(La + Lb, 1)
-	a_index = torch.empty(N, W, dtype = torch.int32, device = dev)
-	b_index = torch.empty(N, W, dtype = torch.int32, device = dev)
-	n_cols = torch.empty(N, dtype = torch.int32, device = dev)
-	score = torch.empty(N, dtype = torch.int32, device = dev)
-	nbytes = nw_align_workspace_bytes(N, La, Lb)
-	ws = torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)
-	if La == 0:  # (a zero-size tensor has no storage to point at; no unit is read past a length anyway)
-		a = torch.zeros(N, 1, dtype = torch.int32, device = dev)
-	if Lb == 0:
-		b = torch.zeros(N, 1, dtype = torch.int32, device = dev)
-	call('convasr_nw_align', ptr(a), ptr(al), ptr(b), ptr(bl), ptr(a_index), ptr(b_index), ptr(n_cols), ptr(score), ptr(ws), nbytes, N, La, Lb,
-	     *scores, stream_ptr())
-	return a_index[:, :La + Lb], b_index[:, :La + Lb], n_cols, score
-
-
-def nw_align(a, a_lengths, b, b_lengths, scores, workspace_cap = NW_WORKSPACE_CAP):
-	"""Semi-global Needleman-Wunsch alignment with traceback of N pairs (include/convasr_hip.h: convasr_nw_align).  a (N, La) / b (N, Lb):
-	integer ids of the hypothesis / reference units (made int32), a_lengths / b_lengths (N,); scores = (match, sub, del, ins), integers in
-	[-32768, 32768].  Returns (a_index (N, La + Lb) int32, b_index (N, La + Lb) int32, n_cols (N,) int32, score (N,) int32): per alignment
-	column the 0-based unit of a / b or -1 for a gap, -1 past column n_cols; score is the end cell's.
-
-	One launch takes N * La * ceil(Lb / 64) * 16 + N * (La + Lb) * 4 bytes of workspace.  While that is at most workspace_cap (default
-	NW_WORKSPACE_CAP = 1 GiB, a resource bound) the whole batch is one launch and nothing is copied to the host.  A larger batch is split:
-	the lengths come to the host once, the pairs are ordered by size and cut into the fewest groups that each fit under the cap at their
-	own largest lengths, one launch per group.  A single pair over the cap, or anything outside the envelope (N < 2^20, La, Lb <= 16383),
-	raises ConvasrHipError; nw_align_long takes longer pairs."""
-	require_cuda(a, b)
-	if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
-		raise ValueError(f'nw_align: a {tuple(a.shape)} and b {tuple(b.shape)} are not (N, La) and (N, Lb)')
-	scores = tuple(int(s) for s in scores)
-	if len(scores) != 4:
-		raise ValueError('nw_align: scores = (match, sub, del, ins)')
-	dev = a.device
-	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
-	a, b = a.to(torch.int32).contiguous(), b.to(device = dev, dtype = torch.int32).contiguous()
-	al = torch.as_tensor(a_lengths).to(device = dev, dtype = torch.int32).contiguous()
-	bl = torch.as_tensor(b_lengths).to(device = dev, dtype = torch.int32).contiguous()
-	if al.shape != (N,) or bl.shape != (N,):
-		raise ValueError(f'nw_align: lengths of shapes {tuple(al.shape)}, {tuple(bl.shape)} for a batch of {N}')
-	if nw_align_workspace_bytes(N, La, Lb) <= workspace_cap:
-		return _nw_launch(a, al, b, bl, scores)
-	need = lambda n, la, lb: n * (la * ((lb + 63) // 64) * 16 + (la + lb) * 4)
-	lens = torch.stack([al.clamp(0, La), bl.clamp(0, Lb)]).cpu().tolist()
-	order = sorted(range(N), key = lambda p: -need(1, lens[0][p], lens[1][p]))
-	groups, cur, ga, gb = [], [], 0, 0
-	for p in order:
-		na, nb = max(ga, lens[0][p]), max(gb, lens[1][p])
-		if cur and need(len(cur) + 1, na, nb) > workspace_cap:
-			groups.append((cur, ga, gb))
-			cur, na, nb = [], lens[0][p], lens[1][p]
-		cur, ga, gb = cur + [p], na, nb
-	groups.append((cur, ga, gb))
-	if need(1, groups[0][1], groups[0][2]) > workspace_cap:
-		raise _lib.ConvasrHipError(f'nw_align: one pair of {groups[0][1]} x {groups[0][2]} units needs {need(1, groups[0][1], groups[0][2])} bytes of workspace, over the cap of {workspace_cap}')
-	a_index = torch.full((N, La + Lb), -1, dtype = torch.int32, device = dev)
-	b_index = torch.full((N, La + Lb), -1, dtype = torch.int32, device = dev)
-	n_cols = torch.empty(N, dtype = torch.int32, device = dev)
-	score = torch.empty(N, dtype = torch.int32, device = dev)
-	for members, ga, gb in groups:
-		idx = torch.tensor(members, dtype = torch.int64, device = dev)
-		ai, bi, nc, sc = _nw_launch(a[idx, :ga].contiguous(), al[idx], b[idx, :gb].contiguous(), bl[idx], scores)
-		a_index[idx, :ga + gb], b_index[idx, :ga + gb], n_cols[idx], score[idx] = ai, bi, nc, sc
-	return a_index, b_index, n_cols, score
+	return _query('convasr_nw_align_workspace_bytes', int(N), int(La), int(Lb))
 
 
 NW_LONG_WORKSPACE_CAP = 16 << 30  # bytes of workspace one convasr_nw_align_long / convasr_edit_distance_long call may take; a resource bound like ALIGN_LONG_WORKSPACE_CAP, not a measurement
@@ -1184,7 +1103,7 @@ NW_LONG_MAX_LEN = 131071  # CONVASR_NW_LONG_MAX_LEN
 
 def nw_align_long_tile():
 	"""The edge of convasr_nw_align_long's (and convasr_edit_distance_long's) square tiles, in cells (tests straddle it)."""
-	return _lib.load().convasr_nw_align_long_tile()
+	return _cached_query('convasr_nw_align_long_tile')
 
 
 def nw_align_long_workspace_bytes(N, La, Lb):
@@ -1195,6 +1114,26 @@ def nw_align_long_workspace_bytes(N, La, Lb):
 def edit_distance_long_workspace_bytes(N, La, Lb):
 	"""convasr_edit_distance_long_workspace_bytes: the two boundary families of include/convasr_hip.h."""
 	return _query('convasr_edit_distance_long_workspace_bytes', int(N), int(La), int(Lb))
+
+
+def _pairs(name, a, a_lengths, b, b_lengths):
+	"""N pairs of unit ids as the alignment kernels read them: a (N, La) and b (N, Lb) int32, contiguous, with (N,) int32 lengths, all on a's device."""
+	require_cuda(a, b)
+	if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
+		raise ValueError(f'{name}: a {tuple(a.shape)} and b {tuple(b.shape)} are not (N, La) and (N, Lb)')
+	dev = a.device
+	N = a.shape[0]
+	a, b = a.to(torch.int32).contiguous(), b.to(device = dev, dtype = torch.int32).contiguous()
+	al = torch.as_tensor(a_lengths).to(device = dev, dtype = torch.int32).contiguous()
+	bl = torch.as_tensor(b_lengths).to(device = dev, dtype = torch.int32).contiguous()
+	if al.shape != (N,) or bl.shape != (N,):
+		raise ValueError(f'{name}: lengths of shapes {tuple(al.shape)}, {tuple(bl.shape)} for a batch of {N}')
+	return a, al, b, bl
+
+
+def _units(x):
+	"""x, or a one-column stand-in for an (N, 0) tensor: a zero-size tensor has no storage to point at (no unit is read past a length anyway)."""
+	return x if x.shape[1] else torch.zeros(x.shape[0], 1, dtype = torch.int32, device = x.device)
 
 
 def _cap_groups(la, lb, need, cap):
@@ -1213,33 +1152,35 @@ def _cap_groups(la, lb, need, cap):
 	return groups
 
 
-def _long_pairs(name, a, a_lengths, b, b_lengths):
-	require_cuda(a, b)
-	if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
-		raise ValueError(f'{name}: a {tuple(a.shape)} and b {tuple(b.shape)} are not (N, La) and (N, Lb)')
-	dev = a.device
-	N = a.shape[0]
-	a, b = a.to(torch.int32).contiguous(), b.to(device = dev, dtype = torch.int32).contiguous()
-	al = torch.as_tensor(a_lengths).to(device = dev, dtype = torch.int32).contiguous()
-	bl = torch.as_tensor(b_lengths).to(device = dev, dtype = torch.int32).contiguous()
-	if al.shape != (N,) or bl.shape != (N,):
-		raise ValueError(f'{name}: lengths of shapes {tuple(al.shape)}, {tuple(bl.shape)} for a batch of {N}')
-	return a, al, b, bl
-
-
-def _long_groups(name, query, al, bl, La, Lb, workspace_cap):
-	"""None when the whole batch fits under the cap; otherwise _cap_groups of it (the lengths come to the host once)."""
-	if query(al.shape[0], La, Lb) <= workspace_cap:
-		return None
+def _launch_pairs(name, query, launch, a, al, b, bl, workspace_cap):
+	"""launch(a, al, b, bl) -> tuple of per-pair results, over the whole batch while query(N, La, Lb) bytes of workspace fit under the cap
+	(nothing is copied to the host).  A larger batch is split: the lengths come to the host once, _cap_groups cuts it, and every group is
+	launched at its own largest lengths and scattered back -- (N,) results whole, index rows into the first columns of (N, La + Lb) rows of -1."""
+	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
+	if query(N, La, Lb) <= workspace_cap:
+		return launch(a, al, b, bl)
 	lens = torch.stack([al.clamp(0, La), bl.clamp(0, Lb)]).cpu().tolist()
 	groups = _cap_groups(lens[0], lens[1], query, workspace_cap)
 	_, ga, gb = groups[0]
 	if query(1, ga, gb) > workspace_cap:
 		raise _lib.ConvasrHipError(f'{name}: one pair of {ga} x {gb} units needs {query(1, ga, gb)} bytes of workspace, over the cap of {workspace_cap}')
-	return groups
+	outs = None
+	for members, ga, gb in groups:
+		idx = torch.tensor(members, dtype = torch.int64, device = a.device)
+		parts = launch(a[idx, :ga].contiguous(), al[idx], b[idx, :gb].contiguous(), bl[idx])
+		if outs is None:
+			outs = tuple(torch.empty(N, dtype = p.dtype, device = p.device) if p.ndim == 1 else torch.full((N, La + Lb), -1, dtype = p.dtype, device = p.device) for p in parts)
+		for out, part in zip(outs, parts):
+			if out.ndim == 1:
+				out[idx] = part
+			else:
+				out[idx, :ga + gb] = part
+	return outs
 
 
-def _nw_long_launch(a, al, b, bl, scores, parts = 3, ws = None):
+def _nw_launch(entry, query, a, al, b, bl, scores, parts = None, ws = None):
+	"""One call of convasr_nw_align (parts None) or convasr_nw_align_long_parts (parts 1 = the fill, 2 = the end cell and the walk, 3 = both; ws: a
+	workspace of query(N, La, Lb) bytes the caller keeps between the parts)."""
 	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
 	dev = a.device
 	W = max(La + Lb, 1)
@@ -1247,16 +1188,34 @@ def _nw_long_launch(a, al, b, bl, scores, parts = 3, ws = None):
 	b_index = torch.empty(N, W, dtype = torch.int32, device = dev)
 	n_cols = torch.empty(N, dtype = torch.int32, device = dev)
 	score = torch.empty(N, dtype = torch.int32, device = dev)
-	nbytes = nw_align_long_workspace_bytes(N, La, Lb)
-	if ws is None:
-		ws = torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)  # (per call, not ops.workspace: that cache keeps its buffers for good)
-	if La == 0:  # (a zero-size tensor has no storage to point at; no unit is read past a length anyway)
-		a = torch.zeros(N, 1, dtype = torch.int32, device = dev)
-	if Lb == 0:
-		b = torch.zeros(N, 1, dtype = torch.int32, device = dev)
-	call('convasr_nw_align_long_parts', ptr(a), ptr(al), ptr(b), ptr(bl), ptr(a_index), ptr(b_index), ptr(n_cols), ptr(score), ptr(ws), nbytes, N, La, Lb,
-	     *scores, int(parts), stream_ptr())
+	nbytes = query(N, La, Lb)
+	ws = _call_workspace(nbytes, dev) if ws is None else ws
+	a, b = _units(a), _units(b)
+	call(entry, ptr(a), ptr(al), ptr(b), ptr(bl), ptr(a_index), ptr(b_index), ptr(n_cols), ptr(score), ptr(ws), nbytes, N, La, Lb,
+	     *scores, *(() if parts is None else (int(parts), )), stream_ptr())
 	return a_index[:, :La + Lb], b_index[:, :La + Lb], n_cols, score
+
+
+def _nw(name, entry, query, parts, a, a_lengths, b, b_lengths, scores, workspace_cap):
+	a, al, b, bl = _pairs(name, a, a_lengths, b, b_lengths)
+	scores = tuple(int(s) for s in scores)
+	if len(scores) != 4:
+		raise ValueError(f'{name}: scores = (match, sub, del, ins)')
+	return _launch_pairs(name, query, lambda *group: _nw_launch(entry, query, *group, scores, parts), a, al, b, bl, workspace_cap)
+
+
+def nw_align(a, a_lengths, b, b_lengths, scores, workspace_cap = NW_WORKSPACE_CAP):
+	"""Semi-global Needleman-Wunsch alignment with traceback of N pairs (include/convasr_hip.h: convasr_nw_align).  a (N, La) / b (N, Lb):
+	integer ids of the hypothesis / reference units (made int32), a_lengths / b_lengths (N,); scores = (match, sub, del, ins), integers in
+	[-32768, 32768].  Returns (a_index (N, La + Lb) int32, b_index (N, La + Lb) int32, n_cols (N,) int32, score (N,) int32): per alignment
+	column the 0-based unit of a / b or -1 for a gap, -1 past column n_cols; score is the end cell's.
+
+	One launch takes N * La * ceil(Lb / 64) * 16 + N * (La + Lb) * 4 bytes of workspace.  While that is at most workspace_cap (default
+	NW_WORKSPACE_CAP = 1 GiB, a resource bound) the whole batch is one launch and nothing is copied to the host.  A larger batch is split:
+	the lengths come to the host once, the pairs are ordered by size and cut into the fewest groups that each fit under the cap at their
+	own largest lengths, one launch per group.  A single pair over the cap, or anything outside the envelope (N < 2^20, La, Lb <= 16383),
+	raises ConvasrHipError; nw_align_long takes longer pairs."""
+	return _nw('nw_align', 'convasr_nw_align', nw_align_workspace_bytes, None, a, a_lengths, b, b_lengths, scores, workspace_cap)
 
 
 def nw_align_long(a, a_lengths, b, b_lengths, scores, workspace_cap = NW_LONG_WORKSPACE_CAP):
@@ -1269,38 +1228,17 @@ def nw_align_long(a, a_lengths, b, b_lengths, scores, workspace_cap = NW_LONG_WO
 	bound) it is one call and nothing is copied to the host; a larger batch is split as nw_align splits one: the lengths come to the host
 	once and the pairs are cut into the fewest groups that each fit.  A single pair over the cap, or anything outside the envelope, raises
 	ConvasrHipError."""
-	a, al, b, bl = _long_pairs('nw_align_long', a, a_lengths, b, b_lengths)
-	scores = tuple(int(s) for s in scores)
-	if len(scores) != 4:
-		raise ValueError('nw_align_long: scores = (match, sub, del, ins)')
-	dev = a.device
-	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
-	groups = _long_groups('nw_align_long', nw_align_long_workspace_bytes, al, bl, La, Lb, workspace_cap)
-	if groups is None:
-		return _nw_long_launch(a, al, b, bl, scores)
-	a_index = torch.full((N, La + Lb), -1, dtype = torch.int32, device = dev)
-	b_index = torch.full((N, La + Lb), -1, dtype = torch.int32, device = dev)
-	n_cols = torch.empty(N, dtype = torch.int32, device = dev)
-	score = torch.empty(N, dtype = torch.int32, device = dev)
-	for members, ga, gb in groups:
-		idx = torch.tensor(members, dtype = torch.int64, device = dev)
-		ai, bi, nc, sc = _nw_long_launch(a[idx, :ga].contiguous(), al[idx], b[idx, :gb].contiguous(), bl[idx], scores)
-		a_index[idx, :ga + gb], b_index[idx, :ga + gb], n_cols[idx], score[idx] = ai, bi, nc, sc
-	return a_index, b_index, n_cols, score
+	return _nw('nw_align_long', 'convasr_nw_align_long_parts', nw_align_long_workspace_bytes, 3, a, a_lengths, b, b_lengths, scores, workspace_cap)
 
 
 def _ed_long_launch(a, al, b, bl):
 	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
-	dev = a.device
-	distance = torch.empty(N, dtype = torch.int32, device = dev)
+	distance = torch.empty(N, dtype = torch.int32, device = a.device)
 	nbytes = edit_distance_long_workspace_bytes(N, La, Lb)
-	ws = torch.empty(max(nbytes, 16), dtype = torch.uint8, device = dev)
-	if La == 0:
-		a = torch.zeros(N, 1, dtype = torch.int32, device = dev)
-	if Lb == 0:
-		b = torch.zeros(N, 1, dtype = torch.int32, device = dev)
+	ws = _call_workspace(nbytes, a.device)
+	a, b = _units(a), _units(b)
 	call('convasr_edit_distance_long', ptr(a), ptr(al), ptr(b), ptr(bl), ptr(distance), ptr(ws), nbytes, N, La, Lb, stream_ptr())
-	return distance
+	return (distance, )
 
 
 def edit_distance_long(a, a_lengths, b, b_lengths, workspace_cap = NW_LONG_WORKSPACE_CAP):
@@ -1308,27 +1246,11 @@ def edit_distance_long(a, a_lengths, b, b_lengths, workspace_cap = NW_LONG_WORKS
 	/ b (N, Lb) ids (made int32; equal units, equal ids -- the caller makes them, unlike edit_distance), a_lengths / b_lengths (N,), up to
 	131,071 units a side.  Returns distance (N,) int32, exact.  The tiles, launches, workspace conventions and the split of a batch over
 	workspace_cap are nw_align_long's; the workspace holds the tile boundaries only (4 * (La + Lb) * max(La, Lb) / tile bytes a pair)."""
-	a, al, b, bl = _long_pairs('edit_distance_long', a, a_lengths, b, b_lengths)
-	dev = a.device
-	N, La, Lb = a.shape[0], a.shape[1], b.shape[1]
-	groups = _long_groups('edit_distance_long', edit_distance_long_workspace_bytes, al, bl, La, Lb, workspace_cap)
-	if groups is None:
-		return _ed_long_launch(a, al, b, bl)
-	distance = torch.empty(N, dtype = torch.int32, device = dev)
-	for members, ga, gb in groups:
-		idx = torch.tensor(members, dtype = torch.int64, device = dev)
-		distance[idx] = _ed_long_launch(a[idx, :ga].contiguous(), al[idx], b[idx, :gb].contiguous(), bl[idx])
-	return distance
+	a, al, b, bl = _pairs('edit_distance_long', a, a_lengths, b, b_lengths)
+	return _launch_pairs('edit_distance_long', edit_distance_long_workspace_bytes, _ed_long_launch, a, al, b, bl, workspace_cap)[0]
 
 
 # ------------------------------------------------------------------------------------------------ diarization
-
-def _query(name, *args):
-	n = getattr(_lib.load(), name)(*args)
-	if n < 0:
-		raise _lib.ConvasrHipError(f'{name} failed: {_lib.load().convasr_last_error().decode()}')
-	return n
-
 
 def sliding_max_tile(kernel_size):
 	"""Outputs one workgroup of convasr_sliding_max produces at this window (tests straddle it)."""
@@ -1439,13 +1361,15 @@ def speaker_error_counts(ref_mask, hyp_mask, perms):
 	return counts
 
 
+# ------------------------------------------------------------------------------------------------ audio
+
 RESAMPLE_ZEROS, RESAMPLE_BETA, RESAMPLE_ROLLOFF = 64, 14.769656459379492, 0.9475937167399596  # the parameters resampy publishes for 'kaiser_best'
 _resample_tables = {}  # (sr_in, sr_out, zeros, beta, rolloff) -> host table, (.., device) -> its copy there
 
 
 def resample_tile():
 	"""Outputs per workgroup of convasr_resample's tile route (tests straddle it)."""
-	return _lib.load().convasr_resample_tile()
+	return _cached_query('convasr_resample_tile')
 
 
 def resample_out_len(T_in, sr_in, sr_out):

@@ -65,8 +65,9 @@ def measure(a, b, with_short, d):
 	res = dict(pairs = N, units = n, tile = T, fill_launches = 2 * tiles - 1, align_workspace_bytes = ops.nw_align_long_workspace_bytes(N, n, n),
 	           distance_workspace_bytes = ops.edit_distance_long_workspace_bytes(N, n, n))
 	ws = torch.empty(res['align_workspace_bytes'], dtype = torch.uint8, device = d)
-	res['fill'] = gpu_ms(lambda: ops._nw_long_launch(a, ln, b, ln, SCORES, 1, ws))
-	res['walk'] = gpu_ms(lambda: ops._nw_long_launch(a, ln, b, ln, SCORES, 2, ws))
+	parts = lambda which: ops._nw_launch('convasr_nw_align_long_parts', ops.nw_align_long_workspace_bytes, a, ln, b, ln, SCORES, which, ws)
+	res['fill'] = gpu_ms(lambda: parts(1))
+	res['walk'] = gpu_ms(lambda: parts(2))
 	del ws
 	a64, l64 = a.long(), ln.long()
 	b64 = b.long()

@@ -305,3 +305,50 @@ def test_a_repeated_library_query_is_answered_from_memory(monkeypatch):
 	assert ops._conv_stats_max_rows(3, 777) == rows and ops._cached_query('convasr_conv1d_wgrad_workspace_bytes', *geometry) == nbytes
 	with pytest.raises(AssertionError, match = 'reached the library'):
 		ops._conv_stats_max_rows(3, 778)
+
+
+def test_a_refused_library_query_raises_with_its_message_and_is_not_remembered():
+	"""ops._query: a negative answer raises with the library's message and is never stored -- the same question asked again reaches the
+	library again and reports its own message, not whatever another refusal left in convasr_last_error() meanwhile."""
+	import re
+	from convasr_amd import ops, _lib
+	lib = _lib.load()
+	name, args = 'convasr_ctc_loss_long_workspace_bytes', (2, 500, 38, 131072)
+	assert lib.convasr_ctc_loss_long_workspace_bytes(*args) < 0
+	message = lib.convasr_last_error().decode()
+	assert '131072' in message
+	for _ in range(2):
+		assert lib.convasr_nw_align_workspace_bytes(0, 5, 5) < 0 and lib.convasr_last_error().decode() != message  # another refusal in between
+		with pytest.raises(_lib.ConvasrHipError, match = re.escape(f'{name} failed: {message}')):
+			ops._query(name, *args)
+		assert (name, ) + args not in ops._queries
+	good = (2, 500, 38, 1024)
+	assert ops._query(name, *good) == lib.convasr_ctc_loss_long_workspace_bytes(*good) == ops._queries[(name, ) + good] > 0
+
+
+def test_frame_lengths_of_the_decoding_wrappers():
+	from convasr_amd import ops
+	cpu = torch.device('cpu')
+	full = ops._frame_lengths('f', None, 3, 7, cpu)
+	assert full.dtype == torch.int64 and full.tolist() == [7, 7, 7] and full.device == cpu
+	for given in ([5, 0, 7], torch.tensor([5, 0, 7], dtype = torch.int32), torch.tensor([[5, 1], [0, 1], [7, 1]], dtype = torch.int32)[:, 0]):
+		got = ops._frame_lengths('f', given, 3, 7, cpu)
+		assert got.dtype == torch.int64 and got.is_contiguous() and got.tolist() == [5, 0, 7]
+	for bad in ([5, 7], [[5, 0, 7]], 5):
+		with pytest.raises(ValueError, match = 'ctc_greedy_collapse: lengths of shape .* for a batch of 3'):
+			ops._frame_lengths('ctc_greedy_collapse', bad, 3, 7, cpu)
+
+
+def test_ctc_targets_of_the_loss_and_alignment_wrappers():
+	from convasr_amd import ops
+	cpu = torch.device('cpu')
+	B, S = 3, 4
+	flat = torch.arange(B * S, dtype = torch.int32)
+	lens = torch.tensor([[4, 9], [2, 9], [0, 9]], dtype = torch.int32)
+	targets, il, tl = ops._ctc_targets(flat, torch.tensor([10, 9, 8], dtype = torch.int32), lens[:, 0], B, cpu)
+	assert targets.shape == (B, S) and targets.tolist() == flat.view(B, S).tolist()
+	assert all(t.dtype == torch.int64 and t.is_contiguous() and t.device == cpu for t in (targets, il, tl))
+	assert il.tolist() == [10, 9, 8] and tl.tolist() == [4, 2, 0] and not lens[:, 0].is_contiguous()
+	wide = torch.arange(B * 2 * S).view(B, 2 * S)[:, ::2]  # a strided (B, S) view
+	targets, _, _ = ops._ctc_targets(wide, il, tl, B, cpu)
+	assert targets.shape == (B, S) and targets.is_contiguous() and torch.equal(targets, wide)

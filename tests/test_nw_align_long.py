@@ -148,3 +148,23 @@ def test_grouping_under_a_cap():
 	for (members, ga, gb), (nxt, na, nb) in zip(groups, groups[1:]):
 		assert need(len(members) + 1, max(ga, la[nxt[0]]), max(gb, lb[nxt[0]])) > big
 	assert ops._cap_groups(la, lb, need, big - 1)[0] == ([2], 5000, 5100)  # one pair over the cap still comes back, first: the caller raises
+
+
+def test_nw_align_splits_by_the_library_query_as_it_did_by_its_formula():
+	"""ops.nw_align sizes the groups of a batch over its cap with convasr_nw_align_workspace_bytes; it used to size them with the formula
+	the header states for that query, written out in Python.  The two are the same function, so the split -- groups and launches -- of
+	the batch tests/test_align_gpu.py::test_split_over_the_workspace_cap runs is the same."""
+	import random
+	from convasr_amd import ops
+	formula = lambda n, la, lb: n * (la * ((lb + 63) // 64) * 16 + (la + lb) * 4)
+	for shape in [(1, 0, 0), (1, 700, 650), (150, 199, 199), (7, 64, 65), (1, 16383, 16383)]:
+		assert _lib.load().convasr_nw_align_workspace_bytes(*shape) == ops.nw_align_workspace_bytes(*shape) == formula(*shape), shape
+	rng = random.Random(10)
+	seq = lambda n: [rng.randrange(3) for _ in range(n)]
+	pairs = [(seq(rng.randrange(0, 200)), seq(rng.randrange(0, 200))) for _ in range(150)] + [(seq(700), seq(650))]
+	rng.shuffle(pairs)
+	la, lb = [len(a) for a, b in pairs], [len(b) for a, b in pairs]
+	cap = 400_000
+	groups = ops._cap_groups(la, lb, ops.nw_align_workspace_bytes, cap)
+	assert groups == ops._cap_groups(la, lb, formula, cap)
+	assert 2 <= len(groups) < 20 and groups[0][1:] == (700, 650) and all(formula(len(members), ga, gb) <= cap for members, ga, gb in groups)
