@@ -45,6 +45,7 @@ _SIGNATURES = dict(
 	convasr_debug_set_conv_v2 = (c_int, [c_int]),
 	convasr_conv1d_wgrad_workspace_bytes = (c_i64, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
 	convasr_conv1d_wgrad = (c_int, [c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_conv1d_wgrad_plan = (c_int, [c_int] * 11 + [ctypes.POINTER(c_int)]),
 	convasr_bn_finalize = (c_int, [c_p, c_int, c_i64, c_p, c_p, c_p, c_p, c_f32, c_f32, c_p, c_p, c_p, c_p, c_int, c_p, c_p]),
 	convasr_bn_eval_scale_shift = (c_int, [c_p, c_p, c_p, c_p, c_f32, c_p, c_p, c_int, c_p]),
 	convasr_bn_act_fwd = (c_int, [c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_p, c_p, c_int, c_f32, c_f32, c_f32, c_u64, c_u64, c_p, c_p, c_int, c_int, c_int, c_p, c_p]),
@@ -84,6 +85,7 @@ _SIGNATURES = dict(
 	convasr_bn_bwd_finalize_grouped = (c_int, [c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_p]),
 	convasr_bn_bwd_apply_grouped = (c_int, [c_p, c_int, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p]),
 	convasr_wgrad1x1_grouped_workspace_bytes = (c_i64, [c_int, c_p, c_p, c_int, c_int]),
+	convasr_wgrad1x1_grouped_plan = (c_int, [c_int, c_p, c_p, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
 	convasr_wgrad1x1_grouped = (c_int, [c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p]),
 	convasr_copy = (c_int, [c_p, c_p, c_i64, c_p]),
 	convasr_colsum_workspace_bytes = (c_i64, [c_i64, c_int]),

@@ -428,6 +428,7 @@ int convasr_conv1d_v2_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s,
 int convasr_conv1x1_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s, int* rows_out);        // conv1x1.hip
 int convasr_wgrad_v2_try(WgradParams& p, int dtype, hipStream_t s);      // wgrad_v2.hip
 int convasr_wgrad_v2_supports(const WgradParams& p);
+int convasr_wgrad_v2_query(WgradParams& p);
 static int g_conv_use_v2 = 1;
 static int g_conv_debug = 0;
 // test / A-B hook: bit 0 clear forces the register-staged kernels for every dtype; bits 8.. are experiment flags (ConvParams::debug)
@@ -887,11 +888,18 @@ template <typename T, int XI, bool AX, bool AY> static void launch_wgrad(const W
 	hipLaunchKernelGGL(kern, dim3(p.units * p.splits), dim3(NTHREADS), smem, s, p);
 }
 
-template <typename T> static int dispatch_wgrad(WgradParams& p, hipStream_t s) {
+// The general kernel's plan in `p`, its dynamic LDS bytes and register chunks per thread of the X tile; false = the tile is too large for it.
+template <typename T> static bool wgrad_general_plan(WgradParams& p, size_t* smem, int* xi) {
 	wgrad_plan(p, WgTile<T>::BKT, sizeof(T) == 2 ? 2.7 : 11.0);
-	const int xi = (p.x_rows * WgTile<T>::CPR + NTHREADS - 1) / NTHREADS;
-	const size_t smem = 2 * (size_t)(WgTile<T>::BKT + p.x_rows) * WgTile<T>::PITCH;
-	if (smem > 160 * 1024 || xi > 12) return convasr_fail(CONVASR_EUNSUPPORTED, "conv1d_wgrad: tile too large (x_rows %d)", p.x_rows);
+	*xi = (p.x_rows * WgTile<T>::CPR + NTHREADS - 1) / NTHREADS;
+	*smem = 2 * (size_t)(WgTile<T>::BKT + p.x_rows) * WgTile<T>::PITCH;
+	return *smem <= 160 * 1024 && *xi <= 12;
+}
+
+template <typename T> static int dispatch_wgrad(WgradParams& p, hipStream_t s) {
+	size_t smem;
+	int xi;
+	if (!wgrad_general_plan<T>(p, &smem, &xi)) return convasr_fail(CONVASR_EUNSUPPORTED, "conv1d_wgrad: tile too large (x_rows %d)", p.x_rows);
 	const bool ax = ((p.Cin * sizeof(T)) & 15) == 0, ay = ((p.Cout * sizeof(T)) & 15) == 0;
 	if (ax && ay) { if (xi <= 5) launch_wgrad<T, 5, true, true>(p, smem, s); else launch_wgrad<T, 12, true, true>(p, smem, s); }
 	else if (ax) launch_wgrad<T, 12, true, false>(p, smem, s);
@@ -944,6 +952,28 @@ static int wgrad_impl(const void* x, int x_ld, const void* dy, int dy_ld, float*
 extern "C" int convasr_conv1d_wgrad(const void* x, const void* dy, float* dw, float* dbias, void* workspace, int dtype, int B, int Cin, int Cout, int Tin,
                                     int Tout, int K, int stride, int dil, int pad, int accumulate, int dw_layout, void* stream) {
 	return wgrad_impl(x, 0, dy, 0, dw, dbias, workspace, dtype, B, Cin, Cout, Tin, Tout, K, stride, dil, pad, accumulate, dw_layout, stream);
+}
+
+// Which kernel convasr_conv1d_wgrad (x_ld = dy_ld = 0) / convasr_conv1d_wgrad_ld would launch for this geometry under the current
+// convasr_debug_set_conv_v2 state, and with what plan: 0 = refused, 1 = the general kernel, 2 = the LDS-DMA kernel;
+// out = {splits, chunks_per_split, chunks_per_b, tap_groups, x_rows}.  The same plan functions as wgrad_impl above.  No launch, no GPU.
+extern "C" int convasr_conv1d_wgrad_plan(int dtype, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil, int x_ld, int dy_ld, int* out) {
+	if (!out || B <= 0 || Cin <= 0 || Cout <= 0 || Tin <= 0 || Tout <= 0 || K <= 0 || K > 64 || stride <= 0 || dil <= 0) return 0;
+	if ((x_ld && (x_ld < Cin || (x_ld & 7))) || (dy_ld && (dy_ld < Cout || (dy_ld & 7))) || ((x_ld || dy_ld) && (!convasr_is_half(dtype) || stride != 1))) return 0;  // (0 = dense, the argument check of convasr_conv1d_wgrad_ld otherwise)
+	WgradParams p = WgradParams();
+	p.B = B; p.Cin = Cin; p.Cout = Cout; p.Tin = Tin; p.Tout = Tout; p.K = K; p.stride = stride; p.dil = dil;
+	p.x_ld = x_ld == Cin ? 0 : x_ld; p.dy_ld = dy_ld == Cout ? 0 : dy_ld;
+	size_t smem;
+	int xi, route;
+	if (convasr_is_half(dtype) && g_conv_use_v2 && convasr_wgrad_v2_query(p)) route = 2;
+	else if (p.x_ld || p.dy_ld) return 0;
+	else if (dtype == CONVASR_F32) route = wgrad_general_plan<float>(p, &smem, &xi);
+	else if (dtype == CONVASR_BF16) route = wgrad_general_plan<bf16_t>(p, &smem, &xi);
+	else if (dtype == CONVASR_F16) route = wgrad_general_plan<f16_t>(p, &smem, &xi);
+	else return 0;
+	if (!route) return 0;
+	out[0] = p.splits; out[1] = p.chunks_per_split; out[2] = p.chunks_per_b; out[3] = p.tap_groups; out[4] = p.x_rows;
+	return route;
 }
 
 // The same gradient from operands whose frames are x_ld / dy_ld elements apart (>= Cin / Cout, multiples of 8): plane 0 of a split-operand

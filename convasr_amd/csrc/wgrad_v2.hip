@@ -353,6 +353,14 @@ int convasr_wgrad_v2_supports(const WgradParams& p) {
 	return wgrad_v2_plan(p, q) != 0;
 }
 
+// The plan convasr_wgrad_v2_try would launch with, in `p` (untouched outside the envelope: returns 0).  No launch: convasr_conv1d_wgrad_plan.
+int convasr_wgrad_v2_query(WgradParams& p) {
+	WgradParams q;
+	if (!wgrad_v2_plan(p, q)) return 0;
+	p = q;
+	return 1;
+}
+
 // Fills the plan in `p` and launches; returns 0 (plan untouched) if the shape is outside this kernel's envelope.
 int convasr_wgrad_v2_try(WgradParams& p, int dtype, hipStream_t s) {
 	WgradParams q;
@@ -434,19 +442,37 @@ extern "C" int64_t convasr_wgrad1x1_grouped_workspace_bytes(int n, const int* ci
 	return bytes;
 }
 
+// The grouped launch's envelope beyond its argument check: 16-bit storage, channel counts in whole 128-wide tiles, rows the DMA descriptors can address.
+static int wgrad_group_envelope(int n, const int* cin, const int* cout, int T, int dtype) {
+	if (!convasr_is_half(dtype)) return convasr_fail(CONVASR_EUNSUPPORTED, "wgrad1x1_grouped: dtype %d (16-bit storage only)", dtype);
+	for (int i = 0; i < n; ++i)
+		if ((cin[i] & 127) || (cout[i] & 127) || cin[i] <= 0 || cout[i] <= 0 || (int64_t)T * cin[i] * 2 >= (1ll << 31) || (int64_t)T * cout[i] * 2 >= (1ll << 31))
+			return convasr_fail(CONVASR_EUNSUPPORTED, "wgrad1x1_grouped: problem %d (%d x %d channels) is outside the kernel's envelope (channel counts %% 128)", i, cout[i], cin[i]);
+	return 0;
+}
+
+// What convasr_wgrad1x1_grouped would launch for these problems: out[0] = splits, out[1] = chunks per split (common to all problems), from the
+// same wgrad_group_plan.  Returns 1, or 0 where the launch would be refused.  No launch, no GPU.
+extern "C" int convasr_wgrad1x1_grouped_plan(int n, const int* cin, const int* cout, int dtype, int B, int T, int* out) {
+	if (n <= 0 || n > W2_MAX_GROUP || !cin || !cout || !out || B <= 0 || T <= 0 || wgrad_group_envelope(n, cin, cout, T, dtype)) return 0;
+	WgradParams probs[W2_MAX_GROUP];
+	for (int i = 0; i < n; ++i) { probs[i] = WgradParams(); probs[i].B = B; probs[i].Cin = cin[i]; probs[i].Cout = cout[i]; probs[i].Tin = probs[i].Tout = T; probs[i].K = 1; probs[i].stride = probs[i].dil = 1; }
+	wgrad_group_plan(probs, n);
+	out[0] = probs[0].splits; out[1] = probs[0].chunks_per_split;
+	return 1;
+}
+
 // n one-tap weight gradients dw_i[co][ci] (+)= sum_(b,t) dy_i[b,t,co] * x_i[b,t,ci] over the same B * T frames: ONE dispatch of the LDS-DMA
 // wgrad kernel over all problems' (co tile, ci tile, split) units and ONE streaming combine.  zero_i (may be NULL): cout[i] floats set to
 // zero by the combine (the branch's bias gradient).  cin[i] % 128 == 0, cout[i] % 128 == 0, 16-bit storage.
 extern "C" int convasr_wgrad1x1_grouped(int n, const void* const* x, const void* const* dy, float* const* dw, float* const* zero, const int* cin, const int* cout,
                                         const int* accumulate, void* workspace, int dtype, int B, int T, void* stream) {
 	CONVASR_CHECK_ARG(n > 0 && n <= W2_MAX_GROUP && x && dy && dw && cin && cout && workspace && B > 0 && T > 0, "wgrad1x1_grouped: bad arguments (at most %d problems)", W2_MAX_GROUP);
-	if (!convasr_is_half(dtype)) return convasr_fail(CONVASR_EUNSUPPORTED, "wgrad1x1_grouped: dtype %d (16-bit storage only)", dtype);
+	if (const int rc = wgrad_group_envelope(n, cin, cout, T, dtype)) return rc;
 	WgradGroup g = {};
 	WgradCombine c = {};
 	for (int i = 0; i < n; ++i) {
 		CONVASR_CHECK_ARG(x[i] && dy[i] && dw[i], "wgrad1x1_grouped: problem %d has a NULL operand", i);
-		if ((cin[i] & 127) || (cout[i] & 127) || cin[i] <= 0 || cout[i] <= 0 || (int64_t)T * cin[i] * 2 >= (1ll << 31) || (int64_t)T * cout[i] * 2 >= (1ll << 31))
-			return convasr_fail(CONVASR_EUNSUPPORTED, "wgrad1x1_grouped: problem %d (%d x %d channels) is outside the kernel's envelope (channel counts %% 128)", i, cout[i], cin[i]);
 		WgradParams& p = g.prob[i];
 		p = WgradParams();
 		p.x = x[i]; p.dy = dy[i]; p.B = B; p.Cin = cin[i]; p.Cout = cout[i]; p.Tin = p.Tout = T; p.K = 1; p.stride = p.dil = 1; p.pad = 0; p.debug = 0;

@@ -543,6 +543,29 @@ def conv1d_wgrad(x, dy, Cout, K, stride, dil, pad, dw, dbias = None, accumulate 
 	return _wgrad_launch(dw, layout, (B, Cin, Cout, Tin, Tout, K, stride, dil), work, family, lambda ws, layout: call('convasr_conv1d_wgrad', ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), dtype_code(x.dtype), B, Cin, Cout, Tin, Tout, K, stride, dil, pad, int(accumulate), layout, stream_ptr()))
 
 
+WGRAD_ROUTES = ('refused', 'general', 'lds_dma')  # convasr_conv1d_wgrad_plan's answer
+
+
+def wgrad_plan(dtype, B, Cin, Cout, Tin, Tout, K, stride = 1, dil = 1, x_ld = 0, dy_ld = 0):
+	"""Which kernel conv1d_wgrad (or, with pitches x_ld / dy_ld, convasr_conv1d_wgrad_ld) would launch for this geometry under the current
+	convasr_debug_set_conv_v2 state, and its plan: dict(route = one of WGRAD_ROUTES, splits, chunks_per_split, chunks_per_b, tap_groups, x_rows);
+	a refused geometry has the route alone.  No launch, no GPU, and not cached (the answer follows the debug switch): the tests ask it so
+	that their shapes follow the library's cost model, like scan_tile()."""
+	out = (ctypes.c_int * 5)()
+	route = _lib.load().convasr_conv1d_wgrad_plan(dtype_code(dtype), B, Cin, Cout, Tin, Tout, K, stride, dil, x_ld, dy_ld, out)
+	plan = dict(route = WGRAD_ROUTES[route])
+	if route:
+		plan.update(zip(('splits', 'chunks_per_split', 'chunks_per_b', 'tap_groups', 'x_rows'), out))
+	return plan
+
+
+def wgrad1x1_grouped_plan(dtype, cins, couts, B, T):
+	"""(splits, chunks_per_split) common to the problems of a wgrad1x1_grouped launch, or None where it would be refused.  No launch, no GPU."""
+	out = (ctypes.c_int * 2)()
+	ok = _lib.load().convasr_wgrad1x1_grouped_plan(len(cins), _int_array(cins), _int_array(couts), dtype_code(dtype), B, T, out)
+	return (out[0], out[1]) if ok else None
+
+
 # ------------------------------------------------------------------------------------------------ grouped conv (the separable block's first half)
 
 def grouped_conv1d(x, w, bias, groups, stride = 1, pad = 0, relu = True):

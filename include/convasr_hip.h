@@ -160,6 +160,12 @@ int convasr_conv1d_wgrad(const void* x, const void* dy, float* dw, float* dbias,
                          int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil, int pad,
                          int accumulate, int dw_layout, void* stream);
 
+/* Which kernel convasr_conv1d_wgrad (x_ld = dy_ld = 0) or convasr_conv1d_wgrad_ld (frames x_ld / dy_ld elements apart) would launch for this
+ * geometry under the current convasr_debug_set_conv_v2 state: 0 = the call would be refused, 1 = the general kernel, 2 = the LDS-DMA kernel.
+ * out[5] = splits, chunks_per_split, chunks_per_b, tap_groups, x_rows of the plan that launch would use (untouched when 0 is returned).
+ * Launches nothing and needs no GPU: the tests ask it which shapes reach which edge of the kernels. */
+int convasr_conv1d_wgrad_plan(int dtype, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil, int x_ld, int dy_ld, int* out);
+
 /* ---- grouped Conv1d: models.py:50-64 (ConvSamePadding(separable = True): nn.Conv1d(Cin, Cout, K, groups = G) -> ReLU -> 1x1 conv), ---------
  * ---- JasperNetSeparable (models.py:1372-1374, G = 128).  The 1x1 half is convasr_conv1d_*; this is the grouped half. ------------------ */
 
@@ -386,6 +392,9 @@ int convasr_conv1x1_grouped(int n, const void* const* x, const void* const* w, v
  * ahead of a train-mode batch norm.  accumulate (array or NULL): add into dw_i.  workspace: convasr_wgrad1x1_grouped_workspace_bytes()
  * bytes.  cin[i] % 128 == 0 and cout[i] % 128 == 0, else CONVASR_EUNSUPPORTED. */
 int64_t convasr_wgrad1x1_grouped_workspace_bytes(int n, const int* cin, const int* cout, int B, int T);
+/* out[2] = splits, chunks_per_split common to the n problems of a convasr_wgrad1x1_grouped launch; returns 1, or 0 where that launch would be
+ * refused (more than 12 problems, channel counts not multiples of 128, fp32).  Launches nothing and needs no GPU. */
+int convasr_wgrad1x1_grouped_plan(int n, const int* cin, const int* cout, int dtype, int B, int T, int* out);
 int convasr_wgrad1x1_grouped(int n, const void* const* x, const void* const* dy, float* const* dw, float* const* zero, const int* cin, const int* cout,
                              const int* accumulate, void* workspace, int dtype, int B, int T, void* stream);
 /* The batch norms of those branches (nn.BatchNorm1d at models.py:110, one per branch, all of the block's channel count C), grouped the same
