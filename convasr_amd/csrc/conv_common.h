@@ -26,6 +26,7 @@ struct ConvParams {
 	float act_lo, act_hi;
 	int m_tiles_per_b, n_tiles, total_tiles;
 	int full_tiles;  // conv_v2s only: tiles [0, full_tiles) are 256 x 128; each later one is computed as two 256 x 64 halves by two workgroups
+	int narrow_parts;  // conv_v2s only: 2, or 4 = the tiles from full_tiles on are computed as four 256 x 32 quarters
 	int x_rows;  // LDS rows of one X tile (even)
 	int tail128;  // conv_v2s only: the last m tile of every utterance covers at most 128 frames and runs as a 128-row tile (half the MFMA work of a padded 256-row one)
 	// conv_v2s only, optional (bn_y != NULL): this launch is the dgrad that produces dz of a Conv+BN+activation layer, and its

@@ -27,14 +27,27 @@ extern "C" int convasr_debug_read_stamps(unsigned long long* host, int count) {
 #else
 #define STAMPI(var)  // -DCONVASR_STAMPS=2: only the two stamps around the whole tile (tile cycles and in-kernel clock of the otherwise untouched kernel)
 #endif
+#if CONVASR_STAMPS == 1 || CONVASR_STAMPS == 3
+#define STAMPX(var) STAMP(var)
+#else
+#define STAMPX(var)
+#endif
+#if CONVASR_STAMPS == 3
+#define STAMPE(var) STAMP(var)  // -DCONVASR_STAMPS=3: the epilogue's segments only, the main loop untouched (scratch/stamps.py epi)
+#else
+#define STAMPE(var)
+#endif
 #else
 #define STAMP(var)
 #define STAMPI(var)
+#define STAMPX(var)
+#define STAMPE(var)
 #endif
 
-// NB = 16-column blocks per wave: 4 -> the 256 x 128 tile, 2 -> a 256 x 64 half tile (same X tile, half the W rows).  The last
-// partial round of a launch (total_tiles mod 256 workgroups on 256 CUs) is cut into half tiles so that it occupies all CUs for
-// ~0.6 of a round instead of a fraction of them for a whole one; per-element sums are unchanged (same k order).
+// NB = 16-column blocks per wave: 4 -> the 256 x 128 tile, 2 -> a 256 x 64 half tile, 1 -> a 256 x 32 quarter tile (same X tile, half /
+// a quarter of the W rows).  The last partial round of a launch (total_tiles mod 256 workgroups on 256 CUs) is cut into half tiles --
+// quarter tiles when it would fill at most a quarter of the CUs -- so that it occupies all CUs for a fraction of a round instead of
+// a fraction of them for a whole one; per-element sums are unchanged (same k order).
 // BM_ = rows (frames) of the tile: 256; 192 (three 16-row blocks per wave instead of four) exists for A/B runs only (see the dispatcher).
 // BNF: 0 = plain epilogue; 1 = fused BN-backward sums, g re-derived per element on the vector ALU (any activation, no stored gates);
 // 2 = fused BN-backward sums from the stored one-bit gates, summed on the MATRIX pipe (below, "Fused pass 1 ... form 2").
@@ -43,12 +56,21 @@ template <> struct HalfOnes<bf16_t> { static constexpr unsigned pair = 0x3F803F8
 template <> struct HalfOnes<f16_t> { static constexpr unsigned pair = 0x3C003C00u; };
 template <> struct HalfOnes<float> { static constexpr unsigned pair = 0u; };  // (never used: the fused epilogues exist for 16-bit outputs only)
 
+// Chunk permutation of row r of the y tile in LDS (CPR 16-byte chunks per row; fused epilogue, form 2): bits 0-1 and 3-4 of the row -- the
+// 16 rows one column read (ds_read_b64_tr_b16) touches -- select 16 different chunk positions.
+template <int CPR> __device__ __forceinline__ int y_swz(int r) { return (((r & 3) << 2) | (((r >> 3) & 1) << 1) | ((r >> 4) & 1)) & (CPR - 1); }
+
 template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __device__ __forceinline__ void v2s_tile(const ConvParams& p, char* smem, const int mtile, const int ntile, const int half, const int bm_full, const int split) {
 	constexpr int BN_ = 32 * NB, MI = BM_ / 64, WROWS = 16 * MI;  // MI 16-row blocks = WROWS rows per wave
 	// LDS map of the epilogue (everything the main loop used is dead by then): output tile, BN-statistics scratch, and for BNF == 2 the
 	// consumer layer's y tile (row-major, BN_ * 2 bytes per row, brought in by the loader waves) and the 256-entry gate -> mask table
-	constexpr int EPI_OPITCH = BN_ * (int)sizeof(O) + 16, EPI_YOFF = BM_ * EPI_OPITCH + 8 * BN * (int)sizeof(float), EPI_YBYTES = BM_ * BN_ * 2, EPI_LUT = EPI_YOFF + EPI_YBYTES;
-	static_assert(BNF != 2 || (EPI_YOFF % 1024 == 0 && EPI_LUT + 4096 <= 160 * 1024), "fused epilogue (form 2): LDS map");
+	// BNF == 2 moves all of it up by epi_o (below) and keeps the consumer layer's y tile UNDER it, one half of its rows (row-major, BN_ * 2
+	// bytes per row) at the start of each of the first two X slab buffers: the half that sits in the buffer the last slab does not use
+	// is brought in by the loader waves during that slab's intervals, the other half when the loop has ended.  Above the output tile and
+	// its statistics scratch: the 256-entry gate -> mask table and the tile's gate bytes (16 per row).
+	constexpr bool BNM = BNF == 2 && sizeof(O) == 2;
+	constexpr int EPI_OPITCH = BN_ * (int)sizeof(O) + 16, EPI_LUT = BM_ * EPI_OPITCH + 8 * BN * (int)sizeof(float), EPI_GATES = EPI_LUT + 4096, EPI_YBYTES = BM_ * BN_ * 2, EPI_YH = EPI_YBYTES / 2;
+	static_assert(!BNM || (EPI_YH % 4096 == 0 && EPI_LUT % 16 == 0), "fused epilogue (form 2): LDS map");
 	const int tid = threadIdx.x, lane = tid & 63;
 	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 	const int r16 = lane & 15, kb = lane >> 4, wm = wave >> 1, wn = wave & 1;
@@ -60,6 +82,7 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 
 	const int x_rows = p.x_rows - (bm_full - BM_);  // (a multiple of 16 either way)
 	const int xbytes = x_rows * ROW_BYTES;
+	const int epi_o = BNM ? xbytes + EPI_YH : 0;  // (x_rows >= BM_: half a y tile fits in an X slab buffer)
 	// X slab buffers: two (the slab being read + the next one landing); K = 1 has ONE interval per slab, so reading the next interval's first
 	// fragments ahead of the barrier needs the next slab resident one interval earlier: three buffers (and only the 3-slot weight ring)
 	const bool k1 = p.K == 1;
@@ -144,12 +167,14 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 	// second MFMA or two reads per MFMA measured no better than the unhinted schedule; MI355X_MICROARCH.md, LDS: up to two
 	// ds_read_b128 per MFMA gap are hidden).
 	auto interleave = [&]() {
+		constexpr int PAIRS = MI + NB < MI * NB ? MI + NB : MI * NB;  // (a quarter tile has more fragment reads than MFMAs)
 #pragma unroll
-		for (int i = 0; i < MI + NB; ++i) {
+		for (int i = 0; i < PAIRS; ++i) {
 			__builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
 			__builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
 		}
-		if (MI * NB > MI + NB) __builtin_amdgcn_sched_group_barrier(0x008, MI * NB - (MI + NB), 0);
+		if (MI + NB > PAIRS) __builtin_amdgcn_sched_group_barrier(0x100, MI + NB - PAIRS, 0);
+		if (MI * NB > PAIRS) __builtin_amdgcn_sched_group_barrier(0x008, MI * NB - PAIRS, 0);
 	};
 	auto mma_frag = [&](const Frag& f) {
 #pragma unroll
@@ -173,6 +198,44 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 		const int npb = (p.K + 1) >> 1, P = n_cib * npb;
 		auto e_slot = [](int s_) { return (unsigned)((s_ % 3) * V2_WSLOT); };
 		auto o_slot = [](int s_) { return (unsigned)((3 + (s_ & 1)) * V2_WSLOT); };
+		// BNF == 2, the loaders' share of the epilogue: the y tile (1-KiB pieces of whole rows, lane-linear; same (b, t, channel) coordinates
+		// as the output tile; rows past the utterance read as zeros through the descriptor's range check) and the tile's gate bytes.
+		// Fetched when the loop has ended, a tile's 64 KiB + 4 KiB -- 16 MB for the 256 tiles of a round at the same moment -- kept every
+		// vector-memory instruction of the workgroup waiting for 7-9 K cycles (in-kernel stamps, profiles/r13_epilogue_stamps.md).  So each
+		// loader wave trickles its PW pieces of the early half, two per interval of the last slab, and fetches its rows' gate bytes into a
+		// register there; they stay in flight over the interval's counted wait and have the next interval to land.
+		constexpr int YROW = BN_ * 2, RPP = 1024 / YROW, YP_HALF = EPI_YH / 1024, PW = YP_HALF / 4, GB = BN_ / 8;  // bytes per tile row, rows per piece, pieces per half / per wave of it, gate bytes per tile row
+		const int y_row_bytes = p.Cout * 2;
+		const int he = n_cib & 1;  // the half whose X slab buffer the last slab leaves idle
+		v4i32 ysrc = {0, 0, 0, 0};
+		if (BNM && loader) ysrc = make_srd(reinterpret_cast<const char*>(p.bn_y) + (int64_t)b * p.Tout * y_row_bytes, (unsigned)(p.Tout * y_row_bytes));
+		// (a row's 16-byte chunks are permuted by y_swz(row), on the source address like the X and W tiles: the sums' column reads
+		// -- 16 rows, the same two chunks of each -- would otherwise all fall on the same 8 banks of a 256-byte row pitch)
+		auto issue_y = [&](int h, int j) {  // piece lw + 4 j of half h
+			const int u = lw + 4 * j;
+			const int r = (h * YP_HALF + u) * RPP + (lane * 16) / YROW, c = (((lane * 16) % YROW) >> 4) ^ y_swz<YROW / 16>(r);
+			dma16(ysrc, __builtin_amdgcn_readfirstlane(lds_base + h * xbytes + u * 1024), (t0 + r) * y_row_bytes + co0 * 2 + c * 16);
+		};
+		// gate bytes of tile row (tid - V2_THREADS): one aligned GB-byte load when every row's bytes are (Cout a multiple of the tile width)
+		const int grow = tid - V2_THREADS;
+		const bool gate_fast = BNM && (p.Cout % BN_) == 0 && (reinterpret_cast<size_t>(p.bn_gate) & 15) == 0;
+		const bool gate_in = BNM && loader && grow < BM_ && t0 + grow < p.Tout && co0 < p.Cout;
+		const bool gate_wave = BNM && loader && lw * 64 < BM_ && t0 + lw * 64 < p.Tout && co0 < p.Cout;  // (wave-uniform: this wave's first row, hence at least one of its lanes, has gate bytes -- the wave issues the load)
+		uint4 gq = make_uint4(0, 0, 0, 0);
+		auto load_gates = [&]() {
+			if (!gate_in) return;
+			const uint8_t* const gp = p.bn_gate + ((((int64_t)b * p.Tout + t0 + grow) * p.Cout + co0) >> 3);
+			if (gate_fast) {
+				if (GB == 16) gq = *reinterpret_cast<const uint4*>(gp);
+				else if (GB == 8) { const uint2 v2 = *reinterpret_cast<const uint2*>(gp); gq.x = v2.x; gq.y = v2.y; }
+				else gq.x = *reinterpret_cast<const unsigned*>(gp);
+			} else {
+				unsigned wds[4] = {0, 0, 0, 0};
+#pragma unroll
+				for (int i = 0; i < GB; ++i) if (co0 + 8 * i < p.Cout) wds[i >> 2] |= (unsigned)gp[i] << (8 * (i & 3));  // (a frame past the utterance, a channel past Cout: no gradient passes)
+				gq = make_uint4(wds[0], wds[1], wds[2], wds[3]);
+			}
+		};
 		if (loader) {
 			issue_x(0);
 			if (k1 && n_cib > 1) issue_x(1);
@@ -181,7 +244,8 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 			if (P > 1) { if (npb > 1) issue_w(0, 2, 1); else issue_w(1, 0, 1); }
 			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 			__builtin_amdgcn_s_barrier();
-			int cib = 0, pi = 0;
+			int cib = 0, pi = 0, yj = 0;  // (yj: pieces of the early y half this wave has issued)
+			bool gates_loaded = false;
 			for (int sidx = 0; sidx < P; ++sidx) {
 				int cib1 = cib, pi1 = pi + 1;  // interval sidx + 1
 				if (pi1 == npb) { pi1 = 0; ++cib1; }
@@ -191,23 +255,37 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 				if (sidx + 1 < P && 2 * pi1 + 1 < p.K) issue_w(cib1, 2 * pi1 + 1, 3 + ((sidx + 1) & 1));
 				if (k1) { if (cib + 2 < n_cib) issue_x(cib + 2); }
 				else if (pi == 0 && cib + 1 < n_cib) issue_x(cib + 1);
-				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+				// (the counted waits below leave exactly this interval's trailing y / gate loads in flight: everything the barrier is for was issued before them)
+				int trail = 0;
+				if (BNM && !k1 && cib == n_cib - 1) {
+					if (yj + 2 <= PW) { issue_y(he, yj); issue_y(he, yj + 1); yj += 2; trail = 2; }
+					else if (yj < PW) { issue_y(he, yj); yj += 1; trail = 1; }
+					if (gate_fast && !gates_loaded) { load_gates(); gates_loaded = true; if (gate_wave) trail += 1; }  // (a wave whose rows all lie past the tile or the utterance issues no load: counting one would leave this interval's last weight piece in flight)
+				}
+				if (trail == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+				else if (trail == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+				else if (trail == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+				else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
 				__builtin_amdgcn_s_barrier();
 				cib = cib1; pi = pi1;
 			}
-			// the epilogue's workgroup barriers.  BNF == 2: the loaders first bring in the consumer layer's y tile (same (b, t, channel)
-			// coordinates as the output tile; rows past the utterance read as zeros through the descriptor's range check), 1 KiB pieces of
-			// whole rows, lane-linear: it lands under the compute waves' accumulator staging and store loop
-			if (BNF == 2 && sizeof(O) == 2) {
-				constexpr int YROW = BN_ * 2, RPP = 1024 / YROW;  // bytes per tile row, rows per piece
-				const int y_row_bytes = p.Cout * 2;
-				const v4i32 ysrc = make_srd(reinterpret_cast<const char*>(p.bn_y) + (int64_t)b * p.Tout * y_row_bytes, (unsigned)(p.Tout * y_row_bytes));
-				const int ylane = ((lane * 16) / YROW) * y_row_bytes + (lane * 16) % YROW + co0 * 2;
-				for (int u = lw; u < EPI_YBYTES / 1024; u += 4)
-					dma16(ysrc, __builtin_amdgcn_readfirstlane(lds_base + EPI_YOFF + u * 1024), (t0 + u * RPP) * y_row_bytes + ylane);
+			// the epilogue's workgroup barriers.  BNF == 2: the loaders first put the gate bytes where the store loop reads them and issue
+			// what is left of the y tile (the late half, whose X slab buffer the loop read to its end): it lands under the compute waves'
+			// accumulator staging and store loop
+			if (BNM) {
+				if (!gates_loaded) load_gates();
+				if (grow < BM_) {
+					char* const gdst = smem + epi_o + EPI_GATES + grow * 16;
+					if (GB == 16) *reinterpret_cast<uint4*>(gdst) = gq;
+					else if (GB == 8) *reinterpret_cast<uint2*>(gdst) = make_uint2(gq.x, gq.y);
+					else *reinterpret_cast<unsigned*>(gdst) = gq.x;
+				}
+				for (; yj < PW; ++yj) issue_y(he, yj);
+				for (int j = 0; j < PW; ++j) issue_y(he ^ 1, j);
+				asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 			}
 			__builtin_amdgcn_s_barrier();
-			if (BNF == 2 && sizeof(O) == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			if (BNM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 			if (BNF && sizeof(O) == 2) __builtin_amdgcn_s_barrier();
 			return;
 		}
@@ -267,13 +345,13 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 	}
 
 #ifdef CONVASR_STAMPS
-	unsigned long long t_epi0 = 0;
-	STAMPI(t_epi0)
+	unsigned long long t_epi0 = 0, t_s0 = 0, t_l1 = 0, t_b2 = 0;
+	STAMPX(t_epi0)
 #endif
 	// ---------------- epilogue: C/D layout of 16x16 blocks: col = lane & 15, row = (lane >> 4) * 4 + reg
 	constexpr int OPITCH = EPI_OPITCH;
-	char* const otile = smem;
-	float* const red = reinterpret_cast<float*>(smem + BM_ * OPITCH);  // [2][4 (wm)][BN_]
+	char* const otile = smem + epi_o;
+	float* const red = reinterpret_cast<float*>(otile + BM_ * OPITCH);  // [2][4 (wm)][BN_]
 	const int nvalid = valid_len(p.xlen, b, p.Tout);
 	const ActConst ac = act_const(p.act, p.act_lo, p.act_hi), bn_ac = act_const(p.bn_act, p.bn_lo, p.bn_hi);
 	// fused BN-backward epilogue (see below): the consumer layer's y tile is fetched now, 16 B per lane and store-loop trip, so
@@ -281,22 +359,17 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 	constexpr int OEPC_ = 16 / sizeof(O), OCH_ = BN_ / OEPC_, TRIPS = BM_ * OCH_ / V2_THREADS;
 	static_assert(BM_ * OCH_ % V2_THREADS == 0, "the store loop covers the tile in whole trips");
 	constexpr bool bnf = BNF == 1 && sizeof(O) == 2;  // separate instantiations: the plain launches do not carry the epilogue's registers and code
-	constexpr bool bnm = BNF == 2 && sizeof(O) == 2;  // form 2: gates + matrix-pipe sums
+	constexpr bool bnm = BNM;  // form 2: gates + matrix-pipe sums
 	typedef typename std::conditional<sizeof(O) == 2, O, I>::type H;  // the 16-bit storage type of the fused epilogue's operands (= O there)
 	uint4 ypre[bnf ? TRIPS : 1];
-	unsigned gpre[TRIPS];  // the chunk's eight one-bit gradient gates (when the forward pass stored them: bn_gate)
+	unsigned gpre[bnf ? TRIPS : 1];  // form 1: the chunk's eight one-bit gradient gates (when the forward pass stored them: bn_gate); form 2 reads them from LDS, where the loaders put them
 	if (bnm) {
-#pragma unroll
-		for (int i = 0; i < TRIPS; ++i) {
-			const int e = tid + i * V2_THREADS, row = e / OCH_, t = t0 + row, co = co0 + (e % OCH_) * OEPC_;
-			gpre[i] = (t < p.Tout && co < p.Cout) ? p.bn_gate[(((int64_t)b * p.Tout + t) * p.Cout + co) >> 3] : 0u;  // (a frame past the utterance, a masked frame: no gradient passes)
-		}
 		// gate byte -> the four dword masks of its 8-element chunk (element 2 i in the low half of word i), once per tile
 		if (tid < 256) {
 			unsigned m[4];
 #pragma unroll
 			for (int i = 0; i < 4; ++i) m[i] = (((tid >> (2 * i)) & 1) ? 0x0000FFFFu : 0u) | (((tid >> (2 * i + 1)) & 1) ? 0xFFFF0000u : 0u);
-			*reinterpret_cast<uint4*>(smem + EPI_LUT + tid * 16) = make_uint4(m[0], m[1], m[2], m[3]);
+			*reinterpret_cast<uint4*>(otile + EPI_LUT + tid * 16) = make_uint4(m[0], m[1], m[2], m[3]);
 		}
 	}
 	if (bnf) {
@@ -312,6 +385,7 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 			}
 		}
 	}
+	STAMPE(t_s0)
 	// Accumulators -> bf16 / fp32 output tile in LDS (+ the BN statistics of a forward launch).  64 values per lane: this phase is
 	// VALU-issue bound (in-kernel stamps: ~6,500 cycles per tile in its general form), so the launches of a training step -- no bias,
 	// no folded scale / shift, no activation, no length mask in the conv itself -- take a specialised instantiation that does
@@ -362,10 +436,10 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 	}
 #ifdef CONVASR_STAMPS
 	unsigned long long t_e1 = 0, t_e2 = 0, t_e3 = 0;
-	STAMPI(t_e1)
+	STAMPX(t_e1)
 #endif
 	__syncthreads();
-	STAMPI(t_e2)
+	STAMPX(t_e2)
 	if (p.stats && tid < BN_ && co0 + tid < p.Cout) {
 		double a = 0, q2 = 0;
 #pragma unroll
@@ -374,7 +448,7 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 		prow[co0 + tid] = a;
 		prow[p.Cout + co0 + tid] = q2;
 	}
-	STAMPI(t_e3)
+	STAMPX(t_e3)
 	O* const yb = reinterpret_cast<O*>(p.y) + (SK ? (int64_t)split * p.split_stride : 0) + (int64_t)b * p.Tout * p.Cout;
 	constexpr int OEPC = 16 / sizeof(O), OCHUNKS = BN_ / OEPC;
 	const bool vec_ok = ((p.Cout * sizeof(O)) & 15) == 0;
@@ -399,7 +473,8 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 		const int t = t0 + row, co = co0 + ch * OEPC;
 		if (bnm) {  // form 2: the chunk, masked by its gates, goes back into the tile in place: G = gate ? dz : 0 (exact: no arithmetic on the values)
 			uint4* const cell = reinterpret_cast<uint4*>(otile + row * OPITCH + ch * 16);
-			const uint4 dzv = *cell, m = *reinterpret_cast<const uint4*>(smem + EPI_LUT + gpre[it] * 16);
+			const unsigned gbyte = *reinterpret_cast<const uint8_t*>(otile + EPI_GATES + row * 16 + ch);
+			const uint4 dzv = *cell, m = *reinterpret_cast<const uint4*>(otile + EPI_LUT + gbyte * 16);
 			if (t < p.Tout && co < p.Cout) {
 				O* dst = yb + (int64_t)t * p.Cout + co;
 				if (vec_ok && co + OEPC <= p.Cout) *reinterpret_cast<uint4*>(dst) = dzv;
@@ -437,8 +512,9 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 			for (int k = 0; k < 8; ++k) { bs1[k] += g[k]; bs2[k] = fmaf(g[k], yv[k] - bmean[k], bs2[k]); }  // sum g * (y - mean): centred per element (no cancellation for |mean| >> std), scaled once per tile below
 		}
 	}
+	STAMPE(t_l1)
 	if (bnf) {
-		float* const bnred = reinterpret_cast<float*>(smem + BM_ * OPITCH + 8 * BN * sizeof(float));  // [V2_THREADS][17], past the output tile and `red`
+		float* const bnred = reinterpret_cast<float*>(otile + BM_ * OPITCH + 8 * BN * sizeof(float));  // [V2_THREADS][17], past the output tile and `red`
 #pragma unroll
 		for (int k = 0; k < 8; ++k) { bnred[tid * 17 + k] = bs1[k]; bnred[tid * 17 + 8 + k] = bs2[k] * bistd[k]; }  // sum g * xhat of this thread's rows
 		__syncthreads();
@@ -460,6 +536,7 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 		// are fp32 chains over the tile's 256 rows, like the vector-ALU form's.  That form spent ~56 vector instructions per 8 elements
 		// (unpack, gate, two accumulations) and ~12.4 K cycles per tile; this one masks a chunk with four v_and.
 		__syncthreads();  // G complete; the loaders have waited for the y tile's DMA before arriving here
+		STAMPE(t_b2)
 		typedef __attribute__((address_space(3))) s16x4* lp;
 		typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
 		auto tr8 = [](unsigned addr, unsigned row_stride) {
@@ -472,15 +549,23 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 		if (wave < BN_ / 16) {
 			// 16-lane group g4 = the MFMA operand's k block (8 rows); lane 4 q + pc of the group supplies row q, columns 4 pc .. 4 pc + 3
 			const int g4 = lane >> 4, q = (lane >> 2) & 3, pc = lane & 3;
-			const unsigned ga = lds_base + (8 * g4 + q) * OPITCH + (16 * wave + 4 * pc) * 2;
-			const unsigned ya = lds_base + EPI_YOFF + (8 * g4 + q) * (BN_ * 2) + (16 * wave + 4 * pc) * 2;
+			const unsigned ga = lds_base + epi_o + (8 * g4 + q) * OPITCH + (16 * wave + 4 * pc) * 2;
+			const unsigned ya = lds_base + (8 * g4 + q) * (BN_ * 2) + (((2 * wave + (pc >> 1)) ^ y_swz<BN_ / 8>(8 * g4 + q)) << 4) + 8 * (pc & 1);  // (y_swz ignores bit 2 and the bits from 5 up: the same for every row this lane reads)
 			u32x4_ ones; ones[0] = ones[1] = ones[2] = ones[3] = HalfOnes<O>::pair;
 			f32x4 a1 = f32x4{0.f, 0.f, 0.f, 0.f}, a2 = f32x4{0.f, 0.f, 0.f, 0.f};
+			// all column reads first, then the two chains of MFMAs (same order of the sums): the reads' latency is paid once, not per 32-row step
+			constexpr int KS = BM_ / 32;
+			u32x4_ gf[KS], yf[KS];
 #pragma unroll
-			for (int ks = 0; ks < BM_ / 32; ++ks) {
-				const u32x4_ gf = tr8(ga + ks * 32 * OPITCH, OPITCH), yf = tr8(ya + ks * 32 * (BN_ * 2), BN_ * 2);
-				a1 = Mma16<H>::run(gf, ones, a1);
-				a2 = Mma16<H>::run(gf, yf, a2);
+			for (int ks = 0; ks < KS; ++ks) {
+				constexpr int HS = KS / 2;  // 32-row steps per half of the y tile
+				gf[ks] = tr8(ga + ks * 32 * OPITCH, OPITCH);
+				yf[ks] = tr8(ya + (ks / HS) * xbytes + (ks % HS) * 32 * (BN_ * 2), BN_ * 2);
+			}
+#pragma unroll
+			for (int ks = 0; ks < KS; ++ks) {
+				a1 = Mma16<H>::run(gf[ks], ones, a1);
+				a2 = Mma16<H>::run(gf[ks], yf[ks], a2);
 			}
 			// D[i][j] sits in lane (j, i >> 2), register i & 3: the diagonal in the 16 lanes with (lane >> 4) == ((lane & 15) >> 2)
 			const int c16 = lane & 15, co = co0 + 16 * wave + c16;
@@ -498,7 +583,12 @@ template <typename I, typename O, int NB, int BNF, int BM_, bool SK = false> __d
 	STAMP(t_end)
 	if (blockIdx.x < 256 && lane == 0) {
 		unsigned long long* o = g_v2s_stamps + (blockIdx.x * 8 + wave) * 8;
+#if CONVASR_STAMPS == 3
+		// gate and LUT set-up | accumulator staging | first barrier | realtime | store(-and-mask) loop | y-tile DMA wait + second barrier | MFMA sums + partial rows | tile
+		o[0] = t_s0 - t_epi0; o[1] = t_e1 - t_s0; o[2] = t_e2 - t_e1; o[3] = __builtin_amdgcn_s_memrealtime() - rt_start; o[4] = t_l1 - t_e3; o[5] = t_b2 ? t_b2 - t_l1 : 0; o[6] = t_end - (t_b2 ? t_b2 : t_l1); o[7] = t_end - t_start;
+#else
 		o[0] = t_loop0 - t_start; o[1] = t_e1 - t_epi0; o[2] = acc_work; o[3] = __builtin_amdgcn_s_memrealtime() - rt_start; o[4] = acc_bar; o[5] = CONVASR_STAMPS == 2 ? rt_start : t_e3 - t_e2; o[6] = t_end - t_e3; o[7] = t_end - t_start;
+#endif
 	}
 #endif
 }
@@ -509,11 +599,12 @@ template <typename I, typename O, int BNF, int BM_, bool SK = false> __global__ 
 	const int bid = blockIdx.x;
 	int v, half = 0;
 	const bool narrow = bid >= p.full_tiles;
+	const bool quarters = narrow && p.narrow_parts == 4;
 	if (!narrow) v = xcd_remap(bid, p.full_tiles);
-	else {  // full_tiles is a multiple of 8, so (bid - full_tiles) keeps the workgroup's XCD; the two halves of a tile share an XCD (and its X tile in L2)
-		const int h = xcd_remap(bid - p.full_tiles, 2 * (p.total_tiles - p.full_tiles));
-		v = p.full_tiles + (h >> 1);
-		half = h & 1;
+	else {  // full_tiles is a multiple of 8, so (bid - full_tiles) keeps the workgroup's XCD; the pieces of a tile share an XCD (and its X tile in L2)
+		const int h = xcd_remap(bid - p.full_tiles, p.narrow_parts * (p.total_tiles - p.full_tiles));
+		v = p.full_tiles + (quarters ? h >> 2 : h >> 1);
+		half = quarters ? h & 3 : h & 1;
 	}
 	int ntile, mtile;
 #ifdef CONVASR_AB_BLOCK
@@ -536,10 +627,12 @@ template <typename I, typename O, int BNF, int BM_, bool SK = false> __global__ 
 	const int split = SK ? blockIdx.y : 0;  // (a split-K launch: grid.y = number of splits)
 	if (!tail) {
 		if (!narrow) v2s_tile<I, O, 4, BNF, BM_, SK>(p, smem, mtile, ntile, 0, BM_, split);
-		else v2s_tile<I, O, 2, BNF, BM_, SK>(p, smem, mtile, ntile, half, BM_, split);
+		else if (!quarters) v2s_tile<I, O, 2, BNF, BM_, SK>(p, smem, mtile, ntile, half, BM_, split);
+		else v2s_tile<I, O, 1, BNF, BM_, SK>(p, smem, mtile, ntile, half, BM_, split);
 	} else {
 		if (!narrow) v2s_tile<I, O, 4, BNF, 128, SK>(p, smem, mtile, ntile, 0, bm_full, split);
-		else v2s_tile<I, O, 2, BNF, 128, SK>(p, smem, mtile, ntile, half, bm_full, split);
+		else if (!quarters) v2s_tile<I, O, 2, BNF, 128, SK>(p, smem, mtile, ntile, half, bm_full, split);
+		else v2s_tile<I, O, 1, BNF, 128, SK>(p, smem, mtile, ntile, half, bm_full, split);
 	}
 }
 
@@ -587,7 +680,8 @@ int convasr_conv1d_v2_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s,
 	size_t smem = 2 * (size_t)p.x_rows * ROW_BYTES + 5 * V2_WSLOT;  // two X slab buffers + the 3 + 2 weight slots
 	if (p.K == 1) smem = 3 * (size_t)p.x_rows * ROW_BYTES + 3 * V2_WSLOT;  // K = 1: three X slab buffers + the 3-slot ring
 	const bool mfma_sums = p.bn_y && p.bn_gate && !(p.debug & 256);  // (debug bit 256: the vector-ALU form of the fused epilogue even with gates: A/B runs)
-	const size_t epi = (size_t)bm * (BN * osz + 16) + 8 * BN * sizeof(float) + (p.bn_y ? (mfma_sums ? (size_t)bm * BN * 2 + 4096 : (size_t)V2_THREADS * 17 * sizeof(float)) : 0);
+	// (form 2 of the fused epilogue: half a y tile at the start of each of the first two X slab buffers, then output tile, statistics scratch, gate -> mask table, gate bytes)
+	const size_t epi = (size_t)bm * (BN * osz + 16) + 8 * BN * sizeof(float) + (p.bn_y ? (mfma_sums ? (size_t)p.x_rows * ROW_BYTES + (size_t)bm * BN + 4096 + (size_t)bm * 16 : (size_t)V2_THREADS * 17 * sizeof(float)) : 0);
 	if (epi > smem) smem = epi;
 	if (smem > 160 * 1024) return 0;
 	if ((int64_t)p.Tin * p.Cin * 2 >= (1ll << 31) || (int64_t)p.K * p.CoutPad * p.Cin * 2 >= (1ll << 31) || (int64_t)(p.Tout + bm) * p.Cout * 2 >= (1ll << 31)) return 0;
@@ -606,13 +700,18 @@ int convasr_conv1d_v2_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s,
 #endif
 	static unsigned long long attr_set[2][2][5] = {};
 	convasr_allow_160k_lds(kern, attr_set[f16][bi][ki]);
-	// a last partial round that would occupy at most half of the CUs is cut into half-width tiles (debug bit 32: off)
+	// a last partial round that would occupy at most half of the CUs is cut into half-width tiles (debug bit 32: off); into quarter-width
+	// tiles when it follows at least one whole round and would occupy at most a quarter of the CUs (debug bit 16: halves there too)
 	p.full_tiles = p.total_tiles;
+	p.narrow_parts = 2;
 	if (!(p.debug & 32)) {
 		const int rest = p.total_tiles % n_cu;
-		if (rest > 0 && 2 * rest <= n_cu && ((p.total_tiles - rest) & 7) == 0) p.full_tiles = p.total_tiles - rest;
+		if (rest > 0 && 2 * rest <= n_cu && ((p.total_tiles - rest) & 7) == 0) {
+			p.full_tiles = p.total_tiles - rest;
+			if (p.full_tiles > 0 && 4 * rest <= n_cu && !(p.debug & 16)) p.narrow_parts = 4;
+		}
 	}
-	const int grid = p.full_tiles + 2 * (p.total_tiles - p.full_tiles);
+	const int grid = p.full_tiles + p.narrow_parts * (p.total_tiles - p.full_tiles);
 	const int splits = p.cib_per_split ? ((p.Cin >> 6) + p.cib_per_split - 1) / p.cib_per_split : 1;
 	void* args[] = {&p};
 	if (hipLaunchKernel(kern, dim3(grid, splits), dim3(V2S_THREADS), args, smem, s) != hipSuccess) { (void)hipGetLastError(); return 0; }  // (the caller's fallback starts from a clean error state)

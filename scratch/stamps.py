@@ -7,6 +7,36 @@ import numpy as np, torch
 from convasr_amd import ops, _lib
 d = torch.device('cuda:0'); dt = torch.bfloat16
 lib = _lib.load()
+def epilogue_segments():
+	"""Build -DCONVASR_STAMPS=3 (`python scratch/stamps.py epi`): the segments of the epilogue of a dgrad tile, plain (BNF = 0) next to the
+	fused BN-backward form with stored gates (BNF = 2), main loop untouched.  Mean cycles per computing wave over the first 256 workgroups."""
+	names = ['gate + LUT set-up', 'accumulator staging', 'first barrier', 'store(-and-mask) loop', 'y-tile DMA wait + second barrier', 'MFMA sums + partial rows', 'tile']
+	cols = [0, 1, 2, 4, 5, 6, 7]
+	B, T = 64, 751
+	act = (_lib.ACT_HARDTANH, 0.0, 20.0)
+	print('| layer (dgrad) | epilogue | ' + ' | '.join(names) + ' | epilogue total | GHz |\n|' + '---|' * (len(names) + 4))
+	for (c, k, cdy, dil) in [(768, 11, 768, 1), (256, 11, 256, 1), (768, 29, 896, 2)]:
+		dy = ops.as_cl(torch.randn(B, cdy, T, device = d), dt)
+		w = torch.randn(cdy, c, k, device = d) / (cdy * k) ** 0.5
+		_, dgr = ops.pack_weight(w, dt, None)
+		yb = ops.as_cl(torch.randn(B, c, T, device = d) * 4 + 2, dt)
+		sc, sh, mean, istd = (torch.rand(c, device = d) + 0.5 for _ in range(4))
+		xl = torch.ones(B, device = d)
+		gate = torch.zeros(B * T * c // 8, dtype = torch.uint8, device = d)
+		ops.bn_act(yb, sc, sh, act, xlen = xl, dropout_p = 0.2, seed = 1, offset = 0, gate = gate)
+		sums = ops.ConvStats(c, B, T, d)
+		pad = dil * (k - 1) - dil * (k // 2)
+		for form, run in (('BNF = 0', lambda: ops.conv1d(dy, dgr, c, k, 1, dil, pad)), ('BNF = 2', lambda: ops.conv1d_dgrad_bn_reduce(dy, dgr, c, k, dil, pad, yb, sc, sh, mean, istd, act, 0.2, 1, 0, xl, sums, gate = gate))):
+			for _ in range(10): run()
+			torch.cuda.synchronize()
+			buf = np.zeros(256 * 8 * 8, dtype = np.uint64)
+			assert lib.convasr_debug_read_stamps(buf.ctypes.data_as(ctypes.c_void_p), buf.size) == 0
+			m = buf.reshape(256, 8, 8).astype(np.float64).mean(axis = (0, 1))
+			print(f'| {cdy}->{c} K = {k} | {form} | ' + ' | '.join(f'{m[i]:.0f}' for i in cols) + f' | {sum(m[i] for i in cols[:-1]):.0f} | {m[7] / max(m[3], 1) * 0.1:.2f} |', flush = True)
+
+if len(sys.argv) > 1 and sys.argv[1] == 'epi':
+	epilogue_segments()
+	sys.exit(0)
 for (cin, cout, k, dil) in [(768, 768, 11, 1), (256, 256, 11, 1), (512, 512, 11, 1), (768, 896, 29, 2)]:
 	B, T = 64, 751
 	x = ops.as_cl(torch.randn(B, cin, T, device = d).clamp_(0, 20), dt)  # like the network's activations: half zeros
