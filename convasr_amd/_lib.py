@@ -153,7 +153,16 @@ _SIGNATURES = dict(
 	convasr_resample_out_len = (c_i64, [c_i64, c_int, c_int]),
 	convasr_resample_taps = (c_int, [c_int, c_int, ctypes.c_double, ctypes.c_double]),
 	convasr_resample = (c_int, [c_p, c_int, c_i64, c_int, c_int, c_p, c_int, c_int, c_int, c_p, c_i64, c_int, c_p]),
+	convasr_frame_peak_tile = (c_int, [c_int]),
+	convasr_frame_peak = (c_int, [c_p, c_int, c_int, c_i64, c_int, c_p, c_p]),
+	convasr_vad_frames_workspace_bytes = (c_i64, [c_int, c_i64]),
+	convasr_vad_frames = (c_int, [c_p, c_p, c_int, c_i64, c_i64, c_f32, c_f32, c_f32, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p]),
+	convasr_vad_segments_workspace_bytes = (c_i64, [c_int, c_i64]),
+	convasr_vad_segments_count = (c_int, [c_p, c_p, c_int, c_i64, c_i64, c_p, c_i64, c_p]),
+	convasr_vad_segments_write = (c_int, [c_p, c_int, c_i64, c_int, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p]),
+	convasr_gather_segments = (c_int, [c_p, c_int, c_int, c_i64, c_p, c_p, c_int, c_p, c_i64, c_p]),
 )
+VAD_MAX_CHANNELS, VAD_MAX_LEN, VAD_MAX_FRAME = 8, 1 << 28, 65536  # include/convasr_hip.h: the envelope of convasr_frame_peak and its neighbours
 SLIDE_ABS, SLIDE_NEG = 1, 2  # include/convasr_hip.h: CONVASR_SLIDE_ABS / CONVASR_SLIDE_NEG
 DIAR_MAX_LEN, DIAR_MAX_KERNEL, RLE_MAX_LEN, SPEAKER_MAX_PERMS = 1 << 28, 16384, 1 << 30, 8  # CONVASR_DIAR_MAX_LEN, ..._MAX_KERNEL, CONVASR_RLE_MAX_LEN, CONVASR_SPEAKER_MAX_PERMS
 

@@ -56,6 +56,14 @@ def rle1d(tensor):
 	return ops.rle1d(tensor)
 
 
+def silence_space_mask(log_probs, speech, blank_idx, space_idx):
+	"""models.py:768-774: a (B, C, T) bool mask, True for every class but the space at the frames that are silent twice over -- outside `speech`
+	(B, T) bool, e.g. vad.upsample's, and decoded greedily as the blank.  Plain torch."""
+	silent = (~speech) & (log_probs.argmax(dim = 1) == blank_idx)
+	not_space = torch.arange(log_probs.shape[1], device = silent.device) != space_idx
+	return silent.unsqueeze(1) & not_space.view(1, -1, 1)
+
+
 def unpad(x, lens):
 	return [e[..., :l] for e, l in zip(x, lens)]
 

@@ -1441,3 +1441,92 @@ def resample(x, sr_in, sr_out, mono = False, zeros = RESAMPLE_ZEROS, beta = RESA
 	out = torch.empty(1 if mono else C, T_out, dtype = torch.float32, device = x.device)
 	call('convasr_resample', ptr(x), dtype_code(x.dtype), T, C, int(bool(mono)), ptr(table), 0 if table is None else table.shape[0], sr_in, sr_out, ptr(out), T_out, int(route), stream_ptr())
 	return out
+
+
+# ------------------------------------------------------------------------------------------------ speech activity, segments of a long recording
+
+def frame_peak_tile(frame_len):
+	"""Frames one workgroup of convasr_frame_peak takes per step at this frame length (tests straddle it)."""
+	return _query('convasr_frame_peak_tile', int(frame_len))
+
+
+def _vad_signal(name, signal):
+	require_cuda(signal)
+	if signal.ndim != 2 or signal.dtype not in (torch.int16, torch.float32):
+		raise ValueError(f'{name}: a (C, N) int16 or float32 tensor expected, got {tuple(signal.shape)} {signal.dtype}')
+	return signal.contiguous()
+
+
+def _vad_frames_pair(name, mask, peaks):
+	require_cuda(mask, peaks)
+	if mask.ndim != 2 or mask.dtype != torch.bool or peaks.shape != mask.shape or peaks.dtype != torch.float32:
+		raise ValueError(f'{name}: a (C, frames) bool mask and float32 peaks of the same shape expected, got {tuple(mask.shape)} {mask.dtype} and {tuple(peaks.shape)} {peaks.dtype}')
+	return mask.contiguous(), peaks.contiguous()
+
+
+def frame_peaks(signal, frame_len):
+	"""convasr_frame_peak (include/convasr_hip.h): peak[c][f] = max |signal[c][f F : (f + 1) F]| of a (C, N) int16 or float32 device tensor, the
+	last, partial frame included; int16 peaks are divided by 32767 once.  Returns (C, ceil(N / F)) float32.  One launch."""
+	signal = _vad_signal('frame_peaks', signal)
+	C, N = signal.shape
+	F = int(frame_len)
+	peaks = torch.empty(C, -(-N // F) if F > 0 else 0, dtype = torch.float32, device = signal.device)
+	call('convasr_frame_peak', ptr(signal), dtype_code(signal.dtype), C, N, F, ptr(peaks), stream_ptr())
+	return peaks
+
+
+def vad_frames(peaks, n_full, abs_thr, rel_thr, eps, k, G, S, P):
+	"""The raw and the smoothed speech mask of include/convasr_hip.h from frame peaks (C, nF): level = the k-th smallest (1-based) of the first
+	n_full peaks of every channel (kth_value), raw = the threshold test on whole frames, mask = raw after the three smoothing steps of G, S, P
+	frames (convasr_vad_frames, one launch).  Returns (raw, mask), (C, nF) bool.  n_full == 0: both all False, nothing is launched."""
+	require_cuda(peaks)
+	if peaks.ndim != 2 or peaks.dtype != torch.float32:
+		raise ValueError(f'vad_frames: peaks must be a (C, frames) float32 tensor, got {tuple(peaks.shape)} {peaks.dtype}')
+	C, nF = peaks.shape
+	n_full = int(n_full)
+	if n_full == 0:
+		return torch.zeros(C, nF, dtype = torch.bool, device = peaks.device), torch.zeros(C, nF, dtype = torch.bool, device = peaks.device)
+	peaks = peaks.contiguous()
+	level = kth_value(peaks[:, :n_full], k)
+	raw = torch.empty(C, nF, dtype = torch.bool, device = peaks.device)
+	mask = torch.empty(C, nF, dtype = torch.bool, device = peaks.device)
+	ws = workspace(_query('convasr_vad_frames_workspace_bytes', C, nF), peaks.device, 'vad')
+	call('convasr_vad_frames', ptr(peaks), ptr(level), C, nF, n_full, float(abs_thr), float(rel_thr), float(eps), int(G), int(S), int(P), ptr(raw), ptr(mask), ptr(ws), ws.numel(), stream_ptr())
+	return raw, mask
+
+
+def vad_segments(mask, peaks, frame_len, N, max_frames):
+	"""The speech runs of a (C, nF) bool mask over a recording of N samples in frames of frame_len, cut at their quietest frames (peaks) into
+	pieces of at most max_frames frames (0: no cutting) -- include/convasr_hip.h.  Returns (channel, first, count): int64 device tensors, one
+	entry per segment, by channel and then time, first and count in samples.  The number of segments decides the size of the result, so it is
+	read back to the host ONCE between the two calls (convasr_vad_segments_count / _write), as in rle1d."""
+	mask, peaks = _vad_frames_pair('vad_segments', mask, peaks)
+	C, nF = mask.shape
+	ws = workspace(_query('convasr_vad_segments_workspace_bytes', C, nF), mask.device, 'vad')
+	call('convasr_vad_segments_count', ptr(mask), ptr(peaks), C, nF, int(max_frames), ptr(ws), ws.numel(), stream_ptr())
+	total = int(ws[:4 * C].view(torch.int32).sum().item())
+	channel, first, count = (torch.empty(total, dtype = torch.int64, device = mask.device) for _ in range(3))
+	if total > 0:
+		call('convasr_vad_segments_write', ptr(mask), C, nF, int(frame_len), int(N), ptr(ws), ws.numel(), total, ptr(channel), ptr(first), ptr(count), stream_ptr())
+	return channel, first, count
+
+
+def gather_segments(signal, channel, first, count, multiple = 128):
+	"""convasr_gather_segments: the segments (channel_b, first_b, count_b) -- tensors or lists of B integers, on either side -- of a (C, N) int16
+	or float32 device signal as one zero-padded float32 batch, in one launch.  Returns (x (B, Tpad), xlen (B,) float32 = count / Tpad) with
+	Tpad = ceil(max count / multiple) * multiple, AudioTextDataset.collate_fn's rule.  The library checks a host copy of the segments against
+	the signal before the launch: a segment that leaves [0, N) raises ConvasrHipError."""
+	signal = _vad_signal('gather_segments', signal)
+	C, N = signal.shape
+	rows = [torch.as_tensor(r, dtype = torch.int64).reshape(-1) for r in (channel, first, count)]
+	B = rows[0].numel()
+	if B < 1 or any(r.numel() != B for r in rows) or int(multiple) < 1:
+		raise ValueError(f'gather_segments: three lists of one length >= 1 and a multiple >= 1 expected, got {[r.numel() for r in rows]} and {multiple}')
+	host = torch.stack([r.cpu() for r in rows]).contiguous()
+	seg = torch.stack(rows).contiguous() if all(r.device == signal.device for r in rows) else host.to(signal.device)
+	longest = int(host[2].max())
+	Tpad = max(int(math.ceil(longest / int(multiple))) * int(multiple), 1)
+	x = torch.empty(B, Tpad if longest <= N else 0, dtype = torch.float32, device = signal.device)  # (a count beyond the signal: the library refuses it below, nothing that large is allocated)
+	call('convasr_gather_segments', ptr(signal), dtype_code(signal.dtype), C, N, host.data_ptr(), ptr(seg), B, ptr(x), Tpad, stream_ptr())
+	xlen = torch.tensor([l / Tpad for l in host[2].tolist()], dtype = torch.float32).to(signal.device, non_blocking = True)
+	return x, xlen

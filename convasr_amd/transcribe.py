@@ -9,6 +9,9 @@
   the per-batch body of transcribe.main: forward (every op a HIP kernel; the argmax of the greedy decode too), per-frame time
   stamps, GreedyCTCGenerator with time stamps (one segment per word), optional forced alignment of the reference text
   (ctc.alignment on the GPU) -> ref segments.
+* transcribe_file(...) / transcribe_long(...)
+  transcribe_batch on a wav / raw file: every channel as one row, or -- for a long recording -- the speech cut at silences (vad.segments) or
+  at given segments and gathered into padded batches on the GPU, the words back on the recording's clock.
 
 Out of scope: file discovery, audio decoding, the dataset, text pre/post-processing pipelines (regexes, number
 normalisation) and the json / html / csv / txt writers around this body (CER and the error analysis live in metrics).  A TextPipeline here is the tokenizer
@@ -124,3 +127,46 @@ def transcribe_file(args, text_pipeline, model, generator, audio_path, **read_au
 	signal, sample_rate = audio.read_audio(audio_path, args.sample_rate, mono = getattr(args, 'mono', True), device = args.device, **read_audio_kwargs)
 	channels, duration = signal.shape[0], signal.shape[1] / sample_rate
 	return transcribe_batch(args, text_pipeline, model, generator, signal, torch.ones(channels), torch.zeros(channels), torch.full((channels, ), duration))
+
+
+def transcribe_long(args, text_pipeline, model, generator, audio_or_signal, segments = None, **read_audio_kwargs):
+	"""A long recording as batches of utterance-sized segments instead of transcribe_file's one row per channel: the audio is read with
+	audio.read_audio at args.sample_rate and args.mono (default True) unless a (C, N) device tensor is given; it is cut into segments; the
+	segments, longest first (a stable sort by their sample counts), go in chunks of args.batch_size (default 64) through ops.gather_segments
+	-- one zero-padded batch per launch, padded to args.batch_time_padding_multiple (default 128) -- and transcribe_batch, with begin / end the
+	segments' seconds (float64 tensors: the Python floats as they are), so every word carries a time on the recording's clock, and its channel.
+	segments: None = vad.segments with args.vad_aggressiveness (default 2), args.vad_window_size (0.02) and args.vad_max_duration (15.0).  A list
+	of dicts with begin, end, channel -- a reference transcript (the reference's batched_transcript mode, datasets.py:261-262), or
+	diarization.diarize's output with channel = speaker - 1 -- is sliced by vad.segment_samples instead.
+	Returns a namespace: segments (dicts with begin, end, channel, first, count; by channel, then time), hyp_segments and hyp per segment in that
+	order, transcript (all word segments sorted by begin, end, channel) and text (per channel, the joined hypothesis in time order).  A
+	recording without speech returns empty lists and does not call the model."""
+	from . import audio, ops, vad
+	if torch.is_tensor(audio_or_signal):
+		signal, sample_rate = audio_or_signal, args.sample_rate
+	else:
+		signal, sample_rate = audio.read_audio(audio_or_signal, args.sample_rate, mono = getattr(args, 'mono', True), device = args.device, **read_audio_kwargs)
+	channels, N = signal.shape
+	if segments is None:
+		segments = vad.segments(signal, sample_rate, window_size = getattr(args, 'vad_window_size', 0.02), aggressiveness = getattr(args, 'vad_aggressiveness', 2),
+		                        max_duration = getattr(args, 'vad_max_duration', 15.0))
+	else:
+		given, segments = segments, []
+		for s in given:
+			first, count = vad.segment_samples(s['begin'], s['end'], sample_rate, N)
+			segments.append(dict(s, first = first, count = count))
+		segments.sort(key = lambda s: (s['channel'], s['first']))
+	order = sorted(range(len(segments)), key = lambda i: -segments[i]['count'])
+	batch_size, multiple = getattr(args, 'batch_size', 64), getattr(args, 'batch_time_padding_multiple', 128)
+	hyp_segments, hyp = [None] * len(segments), [None] * len(segments)
+	for at in range(0, len(order), batch_size):
+		chunk = [segments[i] for i in order[at:at + batch_size]]
+		x, xlen = ops.gather_segments(signal, [s['channel'] for s in chunk], [s['first'] for s in chunk], [s['count'] for s in chunk], multiple = multiple)
+		out = transcribe_batch(args, text_pipeline, model, generator, x, xlen, torch.tensor([s['begin'] for s in chunk], dtype = torch.float64), torch.tensor([s['end'] for s in chunk], dtype = torch.float64),
+		                       segment_extra_info = [dict(channel = s['channel']) for s in chunk])
+		for i, words, text in zip(order[at:at + batch_size], out.hyp_segments, out.hyp):
+			hyp_segments[i], hyp[i] = words, text
+	transcript = sorted((w for words in hyp_segments for w in words), key = lambda w: (w['begin'], w['end'], w['channel']))
+	by_time = sorted(range(len(segments)), key = lambda i: (segments[i]['begin'], segments[i]['end']))
+	text = [join(hyp = [dict(hyp = hyp[i]) for i in by_time if segments[i]['channel'] == c]) for c in range(channels)]
+	return types.SimpleNamespace(segments = list(segments), hyp_segments = hyp_segments, hyp = hyp, transcript = transcript, text = text)

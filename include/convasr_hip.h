@@ -913,6 +913,57 @@ int convasr_resample_taps(int sr_in, int sr_out, double zeros, double rolloff);
 int convasr_resample(const void* x, int x_dtype, int64_t T_in, int C, int mono, const float* table, int taps, int sr_in, int sr_out,
                      float* out, int64_t T_out, int route, void* stream);
 
+/* ---- Speech activity and segments of a long recording: vad.py (detect_speech; its postprocess_cut / postprocess_batching are empty stubs)
+ * and the batched_transcript slices of datasets.py:261-262.  The reference's detector is webrtcvad; the one here is DEFINED BY THIS PROJECT
+ * and unpinned against it.  Every result is exact: maxima, a selection, comparisons, integers, one IEEE add and divide per frame. ----------- */
+
+/* signal (C, N), contiguous, int16 or fp32, finite (not checked); F = frame_len; nF = ceil(N / F) frames, of which nfull = N / F (integer
+ * division) are whole.
+ *   peak[c][f] = max of |x[c][i]| over i in [f F, min((f + 1) F, N)): fp32 exact; int16 the maximum of |int32(x)|, then ONE correctly rounded
+ *     fp32 divide by 32767 (s2f_numpy, audio.py:15), so -32768 gives 32768 / 32767.  The last, partial frame has a peak too.
+ *   level[c] = the k-th smallest of peak[c][0 : nfull], k = max(1, int(percentile * nfull)) computed by the caller in double
+ *     (convasr_kth_value).  With nfull == 0 every result is empty or false and the caller launches nothing.
+ *   raw[c][f] = f < nfull and not (peak < abs_thr or peak / (eps + level) < rel_thr), in fp32, the add and the divide correctly rounded
+ *     (select_speaker's silence test); a partial last frame is never raw speech (the reference's detect_speech drops it).
+ *   mask = raw smoothed per channel in three steps of whole frames G, S, P >= 0, each on the complete result of the one before:
+ *     1. a silent run with speech on both sides and length < G becomes speech;
+ *     2. a speech run of length < S becomes silence, whether or not it touches an end of the recording;
+ *     3. every remaining speech run [s, e) becomes [max(0, s - P), min(nF, e + P)).
+ *   segments: the speech runs [a, b) of mask, by channel and then time; with M = max_frames >= 2 (0: no cutting) a run longer than M is cut:
+ *     while b - a > M: j = the lowest index that minimises peak[c][j] over [a + ceil(M / 2), a + M); emit [a, j); a = j.
+ *     Every segment then has 1 to M frames and the segments tile the mask.  first = a F, count = min(b F, N) - a F samples.
+ *   gather: out[b][t] = value(signal[channel_b][first_b + t]) for t < count_b, 0 for count_b <= t < Tpad; value = the sample (fp32) or
+ *     int16 / 32767 in fp32, correctly rounded.
+ *
+ * convasr_frame_peak: peaks (C, nF) fp32.  One launch: a group of 1 to 64 lanes per frame (about 16 samples a lane), 16-byte loads between a
+ * scalar head up to the first 16-byte boundary and a scalar tail, so rows that start unaligned (odd N) are read the same way; 64-bit
+ * indices.  convasr_frame_peak_tile(F) = frames one workgroup takes per step (256 / lanes per frame), for tests that straddle it.
+ * convasr_vad_frames: raw, mask (C, nF) bytes of 0 / 1; level (C,) fp32 on the device.  One launch, one workgroup per channel walking the
+ * frames in tiles of 8,192 with its scan state carried over; workspace: convasr_vad_frames_workspace_bytes(C, nF) bytes, 4-byte aligned,
+ * uninitialised.  n_full is nF or nF - 1, at least 1.
+ * convasr_vad_segments_count / _write: two calls around one host read, because the number of segments depends on the data.  count leaves the
+ * number of segments of channel c as int32 number c of the workspace (convasr_vad_segments_workspace_bytes(C, nF) bytes, 4-byte aligned,
+ * uninitialised); write, given the same workspace untouched and total = their sum >= 1, writes channel, first, count (total,) int64.  A wave
+ * per run makes the cuts one after the other.
+ * convasr_gather_segments: segments (3, B) int64 -- the rows channel, first, count -- once ON THE HOST (segments_host: checked here) and
+ * once on the device (read by the kernel); out (B, Tpad) fp32, Tpad >= the longest count.  One launch.
+ * None of them issues a memset or a copy: every call is one kernel node.
+ * Envelope, checked before any launch: 1 <= C <= 8, 1 <= N <= 2^28 (1 <= nF <= 2^28), 1 <= F <= 65536, G, S, P >= 0, max_frames 0 or >= 2,
+ * 1 <= B <= 65535, 0 <= channel < C, 0 <= first, 1 <= count, first + count <= N, a listed dtype, a workspace of the query's size, no NULL
+ * pointer; outside it CONVASR_EINVAL (the queries return -1 / the code). */
+int convasr_frame_peak_tile(int frame_len);
+int convasr_frame_peak(const void* signal, int dtype, int C, int64_t N, int frame_len, float* peaks, void* stream);
+int64_t convasr_vad_frames_workspace_bytes(int C, int64_t n_frames);
+int convasr_vad_frames(const float* peaks, const float* level, int C, int64_t n_frames, int64_t n_full, float abs_thr, float rel_thr, float eps,
+                       int64_t G, int64_t S, int64_t P, uint8_t* raw, uint8_t* mask, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t convasr_vad_segments_workspace_bytes(int C, int64_t n_frames);
+int convasr_vad_segments_count(const uint8_t* mask, const float* peaks, int C, int64_t n_frames, int64_t max_frames, void* workspace,
+                               int64_t workspace_bytes, void* stream);
+int convasr_vad_segments_write(const uint8_t* mask, int C, int64_t n_frames, int frame_len, int64_t N, const void* workspace,
+                               int64_t workspace_bytes, int64_t total, int64_t* channel, int64_t* first, int64_t* count, void* stream);
+int convasr_gather_segments(const void* signal, int dtype, int C, int64_t N, const int64_t* segments_host, const int64_t* segments, int B,
+                            float* out, int64_t Tpad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
