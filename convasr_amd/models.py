@@ -44,10 +44,31 @@ def temporal_mask(x, lengths):
 
 
 def entropy(log_probs, lengths = None, dim = 1, eps = 1e-9, sum = True, keepdim = False):
-	"""models.py:645-657 (the logged training metric): per-utterance mean entropy over valid frames."""
-	if dim != 1 or not sum or keepdim:
-		raise _lib.ConvasrHipError('entropy: only the dim=1, sum=True form used by train.py:756 / train.py:137 is implemented')
+	"""models.py:645-657: per-utterance mean entropy over valid frames (the logged training metric), or with sum = False the (B, T) entropy
+	of every frame, 0 at the frames t >= lengths[b] (ops.frame_uncertainty)."""
+	if dim != 1 or keepdim:
+		raise _lib.ConvasrHipError('entropy: only dim = 1 without keepdim (the forms train.py:756 / train.py:137 and vis.py:366 use) is implemented')
+	if not sum:
+		return ops.frame_uncertainty(log_probs, lengths = lengths).entropy
 	return ops.entropy(log_probs, lengths, eps)
+
+
+def margin(log_probs, dim = 1):
+	"""models.py:677-678: per frame, the largest probability minus the second largest, (B, T) (ops.frame_uncertainty; an exact tie gives 0)."""
+	if log_probs.ndim != 3 or dim != 1:
+		raise _lib.ConvasrHipError('margin: only (B, C, T) log-probs with dim = 1 are implemented')
+	return ops.frame_uncertainty(log_probs).margin
+
+
+def uncertain_spans(log_probs, lengths = None, max_entropy = 1.0):
+	"""The spans vis.py:394 shades: per utterance (starts, lengths) int64 device tensors of the runs of frames whose entropy exceeds
+	max_entropy -- rle1d of `entropy > max_entropy`, the runs that are True.  Frames t >= lengths[b] have entropy 0."""
+	ent = ops.frame_uncertainty(log_probs, lengths = lengths).entropy
+	out = []
+	for row in ent > max_entropy:
+		starts, runs, values = ops.rle1d(row)
+		out.append((starts[values], runs[values]))
+	return out
 
 
 def rle1d(tensor):

@@ -6,6 +6,7 @@ PyTorch is used for allocation, streams and dtype bookkeeping only; every arithm
 """
 import math
 import os
+import types
 
 import ctypes
 
@@ -801,6 +802,81 @@ def argmax(log_probs):
 	idx = torch.empty(B, T, dtype = torch.int64, device = lp.device)
 	call('convasr_argmax', ptr(lp), ptr(idx), B * T, C, stream_ptr())
 	return idx
+
+
+def frame_uncertainty_row_classes():
+	"""Classes up to which convasr_frame_uncertainty maps one thread to a frame; above it one wave (tests straddle it)."""
+	return _cached_query('convasr_frame_uncertainty_row_classes')
+
+
+def frame_uncertainty(log_probs, eps_id = -1, lengths = None):
+	"""Per-frame statistics of (B, C, T) log-probs in one read (include/convasr_hip.h: convasr_frame_uncertainty has the rule).  Returns a
+	namespace of (B, T) device tensors: idx int64 (ops.argmax's output, bit for bit, on every frame), and fp32 p1 (the largest probability),
+	margin (p1 minus the second largest: models.margin), entropy, entropy_nb (the entropy without the class eps_id, renormalised) and p_eps
+	(the probability of eps_id) -- 0 at the frames t >= lengths[b], NaN at a frame that holds a NaN.  Outside the envelope it raises
+	ConvasrHipError."""
+	require_cuda(log_probs)
+	if log_probs.ndim != 3:
+		raise ValueError(f'frame_uncertainty: (B, C, T) log-probs expected, got shape {tuple(log_probs.shape)}')
+	B, C, T = log_probs.shape
+	lp = as_cl(log_probs, torch.float32)
+	dev = lp.device
+	lengths = None if lengths is None else _frame_lengths('frame_uncertainty', lengths, B, T, dev)
+	if not -C <= int(eps_id) < C:
+		raise _lib.ConvasrHipError(f'frame_uncertainty: eps_id {eps_id} for {C} classes')
+	idx = torch.empty(B, T, dtype = torch.int64, device = dev)
+	p1, margin, ent, ent_nb, p_eps = torch.empty(5, B, T, dtype = torch.float32, device = dev).unbind(0)
+	call('convasr_frame_uncertainty', ptr(lp), ptr(lengths), ptr(idx), ptr(p1), ptr(margin), ptr(ent), ptr(ent_nb), ptr(p_eps), B, T, C, int(eps_id) % C, stream_ptr())
+	return types.SimpleNamespace(idx = idx, p1 = p1, margin = margin, entropy = ent, entropy_nb = ent_nb, p_eps = p_eps)
+
+
+def span_uncertainty(log_probs, stats, utt, begin, end, first = None, tokens = None, frames = None, path = None, eps = 1e-9, frame_map = None):
+	"""Statistics of N spans (words) over frame_uncertainty's arrays (include/convasr_hip.h: convasr_span_uncertainty has the rule).
+	log_probs (B, C, T) and stats = frame_uncertainty(log_probs, ...); utt, begin, end (N,): the utterance and the first and last position
+	(inclusive) of every span.  Events: first (N + 1,), tokens and frames (first[-1],) -- ops.ctc_greedy_segments' packed tokens, frames and
+	seg_first plus the total; path (B, Tp) int64 tells the inserted spaces from the asserted ones.  frame_map (B, Tp) int64: positions are
+	those of another grid (a transcript) and position p of utterance b stands for frame frame_map[b, p].  Returns a namespace of (N,) device
+	tensors: entropy, uncertainty and, with events, n_events int32, confidence, confidence_min, margin (None without).  Outside the
+	envelope it raises ConvasrHipError."""
+	require_cuda(log_probs)
+	if log_probs.ndim != 3:
+		raise ValueError(f'span_uncertainty: (B, C, T) log-probs expected, got shape {tuple(log_probs.shape)}')
+	B, C, T = log_probs.shape
+	lp = as_cl(log_probs, torch.float32)
+	dev = lp.device
+	for name in ('idx', 'p1', 'margin', 'entropy', 'p_eps'):
+		t = getattr(stats, name)
+		if tuple(t.shape) != (B, T) or t.device != dev or not t.is_contiguous():
+			raise ValueError(f'span_uncertainty: stats.{name} must be a contiguous (B, T) = ({B}, {T}) tensor on {dev}')
+	put = lambda t, dtype: None if t is None else torch.as_tensor(t).to(device = dev, dtype = dtype).contiguous()
+	utt, begin, end = put(utt, torch.int64), put(begin, torch.int32), put(end, torch.int32)
+	N = utt.numel()
+	if utt.ndim != 1 or begin.shape != utt.shape or end.shape != utt.shape:
+		raise ValueError(f'span_uncertainty: utt, begin and end must be (N,) tensors, got {tuple(utt.shape)}, {tuple(begin.shape)}, {tuple(end.shape)}')
+	given = [t is not None for t in (first, tokens, frames)]
+	if any(given) and not all(given):
+		raise ValueError('span_uncertainty: first, tokens and frames come together')
+	first, tokens, frames, path, frame_map = put(first, torch.int64), put(tokens, torch.int64), put(frames, torch.int32), put(path, torch.int64), put(frame_map, torch.int64)
+	n_events = 0
+	if all(given):
+		n_events = tokens.numel()
+		if first.shape != (N + 1,) or tokens.ndim != 1 or frames.shape != tokens.shape:
+			raise ValueError(f'span_uncertainty: first of {N + 1} entries and tokens, frames of one length expected, got {tuple(first.shape)}, {tuple(tokens.shape)}, {tuple(frames.shape)}')
+	Tp = T
+	for name, t in (('path', path), ('frame_map', frame_map)):
+		if t is not None:
+			if t.ndim != 2 or t.shape[0] != B or (frame_map is None and t.shape[1] != T) or (frame_map is not None and t.shape[1] != frame_map.shape[1]):
+				raise ValueError(f'span_uncertainty: {name} of shape {tuple(t.shape)} for {B} utterances of {T} frames')
+			Tp = t.shape[1]
+	ent, unc = torch.empty(2, max(N, 1), dtype = torch.float32, device = dev).unbind(0)
+	n_out = conf = conf_min = margin = None
+	if all(given):
+		n_out = torch.empty(max(N, 1), dtype = torch.int32, device = dev)
+		conf, conf_min, margin = torch.empty(3, max(N, 1), dtype = torch.float32, device = dev).unbind(0)
+	call('convasr_span_uncertainty', ptr(lp), ptr(stats.idx), ptr(stats.p1), ptr(stats.margin), ptr(stats.entropy), ptr(stats.p_eps), ptr(utt), ptr(begin), ptr(end),
+	     ptr(first), ptr(tokens), ptr(frames), n_events, ptr(path), ptr(frame_map), Tp, ptr(n_out), ptr(conf), ptr(conf_min), ptr(margin), ptr(ent), ptr(unc),
+	     N, B, T, C, float(eps), stream_ptr())
+	return types.SimpleNamespace(n_events = n_out, confidence = conf, confidence_min = conf_min, margin = margin, entropy = ent, uncertainty = unc)
 
 
 # ------------------------------------------------------------------------------------------------ CTC loss

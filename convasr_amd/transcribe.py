@@ -89,6 +89,8 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 	xlen (B,) fractions, begin / end (B,) seconds, optional targets y (B, L, S) / ylen (B, L) for --align.
 	Returns a namespace: log_probs, logits, olen, ts (per-frame time stamps), hyp_segments (per utterance: list of word segments with
 	begin / end / hyp), hyp (joined strings) and, when args.align and targets are given, alignment (B, S), ref_segments.
+	args.uncertainty (absent = off): every hyp and ref word segment also carries confidence, confidence_min, margin, entropy, uncertainty
+	(GreedyCTCGenerator / BeamCTCGenerator.generate's uncertainty; transcribe_file and transcribe_long pass args on, and transcribe_long's words keep the fields).
 	When args.align_words is set and targets are given, also ref (the decoded, postprocessed targets) and words: per utterance
 	metrics.align_words(*metrics.align_strings(hyp = hyp, ref = ref)) (transcribe.py:235), the strings of the whole batch aligned in two
 	GPU launches; words is None otherwise."""
@@ -99,7 +101,8 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 	duration = x.shape[-1] / args.sample_rate
 	ts = duration * torch.linspace(0, 1, steps = log_probs.shape[-1], device = log_probs.device).unsqueeze(0).expand(B, -1)
 	tokenizer = text_pipeline.tokenizer
-	hyp_segments = [alternatives[0] for alternatives in generator.generate(tokenizer = tokenizer, log_probs = log_probs, begin = begin, end = end, output_lengths = olen, time_stamps = ts, segment_text_key = 'hyp', segment_extra_info = segment_extra_info)]
+	with_uncertainty = bool(getattr(args, 'uncertainty', False))  # every word segment also carries transcript_generators.UNCERTAINTY_KEYS
+	hyp_segments = [alternatives[0] for alternatives in generator.generate(tokenizer = tokenizer, log_probs = log_probs, begin = begin, end = end, output_lengths = olen, time_stamps = ts, segment_text_key = 'hyp', segment_extra_info = segment_extra_info, **(dict(uncertainty = True) if with_uncertainty else {}))]
 	hyp_segments = [map_text(text_pipeline.postprocess, hyp = hyp) for hyp in hyp_segments]
 	out = types.SimpleNamespace(log_probs = log_probs, logits = logits, olen = olen, ts = ts, hyp_segments = hyp_segments, hyp = [join(hyp = h) for h in hyp_segments], alignment = None, ref_segments = None, ref = None, words = None)
 	if getattr(args, 'align', False) and y is not None and y.numel() > 0:
@@ -109,7 +112,9 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 		aligned_ts = ts.gather(1, out.alignment)
 		one_hot = torch.nn.functional.one_hot(y[:, 0, :], num_classes = log_probs.shape[1]).permute(0, 2, 1).to(torch.float32)
 		ref_generator = generator if isinstance(generator, GreedyCTCGenerator) else GreedyCTCGenerator()  # one-hot targets: the argmax collapse gives back y; a beam search over 0 / 1 "log-probs" would not
-		ref_segments = [alternatives[0] for alternatives in ref_generator.generate(tokenizer = tokenizer, log_probs = one_hot, begin = begin, end = end, output_lengths = ylen[:, 0], time_stamps = aligned_ts, segment_text_key = 'ref', segment_extra_info = segment_extra_info)]
+		ref_segments = [alternatives[0] for alternatives in ref_generator.generate(tokenizer = tokenizer, log_probs = one_hot, begin = begin, end = end, output_lengths = ylen[:, 0], time_stamps = aligned_ts, segment_text_key = 'ref', segment_extra_info = segment_extra_info,
+		                                                                           # a reference word's fields: what the MODEL gives its tokens at their aligned frames (a transcript that does not match the audio shows as low confidence)
+		                                                                           **(dict(uncertainty = (log_probs, out.alignment)) if with_uncertainty else {}))]
 		out.ref_segments = [map_text(text_pipeline.postprocess, ref = ref) for ref in ref_segments]
 	if getattr(args, 'align_words', False) and y is not None and y.numel() > 0:
 		from . import metrics

@@ -13,6 +13,9 @@ import types
 import torch
 
 from . import ops
+from ._lib import ConvasrHipError
+
+UNCERTAINTY_KEYS = ('confidence', 'confidence_min', 'margin', 'entropy', 'uncertainty')  # what generate(..., uncertainty = True) adds to every Segment (ops.span_uncertainty)
 
 
 class Segment(dict):
@@ -60,13 +63,33 @@ class GreedyCTCGenerator:
 			return False
 		return all(bool(tokenizer.is_start_word_token(c)) == (c == space) for c in range(log_probs.shape[1]))
 
-	def generate(self, tokenizer, log_probs, begin, end, output_lengths = None, time_stamps = None, segment_text_key = 'hyp', segment_extra_info = None):
+	def generate(self, tokenizer, log_probs, begin, end, output_lengths = None, time_stamps = None, segment_text_key = 'hyp', segment_extra_info = None, uncertainty = False):
+		"""uncertainty = True (device route only): every Segment also carries UNCERTAINTY_KEYS -- ops.span_uncertainty over the word's frames and
+		over its tokens at their frames, from ONE ops.frame_uncertainty pass whose idx is the decoded path.  uncertainty = (acoustic_log_probs,
+		frame_of_position): log_probs are decoded as always, but position p of utterance b stands for frame frame_of_position[b, p] of
+		acoustic_log_probs, where the statistics come from (the one-hot targets of --align against the model's own log-probs)."""
+		wanted = uncertainty is not False and uncertainty is not None
 		if not self.device_route(tokenizer, log_probs, output_lengths):
+			if wanted:
+				raise ConvasrHipError("GreedyCTCGenerator.generate: uncertainty needs the device decode, and device_route refuses these inputs (it takes CUDA log-probs, lengths as a tensor and a tokenizer of CharTokenizerLegacy's kind)")
 			return self.generate_host(tokenizer, log_probs, begin, end, output_lengths, time_stamps, segment_text_key, segment_extra_info)
 		B = log_probs.shape[0]
-		tokens, _, counts, seg_first, seg_begin, seg_end = ops.ctc_greedy_segments(ops.argmax(log_probs), output_lengths, tokenizer.eps_id, tokenizer.space_id,
-		                                                                           self.blank_amount_to_space, split_words = time_stamps is not None)
+		acoustic = frame_map = stats = None
+		if wanted and uncertainty is not True:
+			acoustic, frame_map = uncertainty
+			stats = ops.frame_uncertainty(acoustic, tokenizer.eps_id)
+		elif wanted:
+			acoustic, stats = log_probs, ops.frame_uncertainty(log_probs, tokenizer.eps_id, output_lengths)
+		path = stats.idx if uncertainty is True else ops.argmax(log_probs)
+		tokens, frames, counts, seg_first, seg_begin, seg_end = ops.ctc_greedy_segments(path, output_lengths, tokenizer.eps_id, tokenizer.space_id,
+		                                                                                self.blank_amount_to_space, split_words = time_stamps is not None)
 		n_seg = counts[1].tolist()
+		fields = None
+		if wanted and len(seg_first) > 0:
+			utt = torch.repeat_interleave(counts[1], output_size = len(seg_first))
+			first = torch.cat([seg_first, torch.tensor([len(tokens)], dtype = torch.int64, device = seg_first.device)])
+			span = ops.span_uncertainty(acoustic, stats, utt, seg_begin, seg_end, first, tokens, frames, path = path, frame_map = frame_map)
+			fields = torch.stack([getattr(span, key) for key in UNCERTAINTY_KEYS]).cpu().tolist()
 		tokens, seg_first = tokens.tolist(), seg_first.tolist()
 		if time_stamps is not None:  # the stamps of the segments' begin / end frames, gathered where the stamps live
 			utt = torch.repeat_interleave(counts[1], output_size = len(seg_first)).to(time_stamps.device)
@@ -84,6 +107,8 @@ class GreedyCTCGenerator:
 			for k in range(k0, k0 + n_seg[i]):
 				t_begin, t_end = (begin[i] + ts_begin[k], begin[i] + ts_end[k]) if time_stamps is not None else (begin[i], end[i])
 				seg = Segment(begin = t_begin, end = t_end, **{segment_text_key: texts[k]})
+				if fields is not None:
+					seg.update({key: column[k] for key, column in zip(UNCERTAINTY_KEYS, fields)})
 				if segment_extra_info is not None:
 					seg.update(segment_extra_info[i])
 				transcript.append(seg)
@@ -172,9 +197,13 @@ class BeamCTCGenerator:
 			return decs[labels, tokenizer.eps_id]
 		self.decoder = decoder
 
-	def generate(self, tokenizer, log_probs, begin, end, output_lengths = None, time_stamps = None, segment_text_key = 'hyp', segment_extra_info = None):
+	def generate(self, tokenizer, log_probs, begin, end, output_lengths = None, time_stamps = None, segment_text_key = 'hyp', segment_extra_info = None, uncertainty = False):
+		"""uncertainty = True: every Segment also carries UNCERTAINTY_KEYS (ops.span_uncertainty).  A word's span runs from its first token's
+		frame offset to its last one's and its events are its tokens at their offsets; a beam's token need not be its frame's argmax, so a
+		word's margin can be negative.  The spans of all alternatives are built in the host loop and uploaded once."""
 		tokens, offsets, lengths, _ = self.decoder(tokenizer).decode_with_scores(log_probs, output_lengths)
 		tokens, offsets, lengths = tokens.cpu().tolist(), offsets.cpu().tolist(), lengths.cpu().tolist()
+		spans = dict(segments = [], utt = [], begin = [], end = [], first = [0], tokens = [], frames = []) if uncertainty else None
 		ts_all = time_stamps.cpu().tolist() if time_stamps is not None else None
 		begin = torch.clamp(begin, min = 0.0).cpu().tolist() if time_stamps is not None else begin.cpu().tolist()
 		end = end.cpu().tolist()
@@ -189,9 +218,18 @@ class BeamCTCGenerator:
 				start = next((j for j, c in enumerate(toks) if c not in silence), len(toks))
 				at = lambda j: begin[i] + ts[offs[j]] if ts is not None else None
 				seg_tokens, t_begin, t_end = [], at(start) if ts is not None and start < len(toks) else begin[i], end[i]
+				j_first = start
 
-				def flush():
+				def flush(j_end):
 					seg = Segment(begin = t_begin, end = t_end, **{segment_text_key: tokenizer.decode([seg_tokens])[0]})
+					if spans is not None:  # the word = tokens [j_first, j_end) of this beam
+						spans['segments'].append(seg)
+						spans['utt'].append(i)
+						spans['begin'].append(offs[j_first])
+						spans['end'].append(offs[j_end - 1])
+						spans['tokens'] += toks[j_first:j_end]
+						spans['frames'] += offs[j_first:j_end]
+						spans['first'].append(len(spans['tokens']))
 					if segment_extra_info is not None:
 						seg.update(segment_extra_info[i])
 					transcript.append(seg)
@@ -199,12 +237,18 @@ class BeamCTCGenerator:
 				for j in range(start, len(toks)):
 					c = toks[j]
 					if ts is not None and tokenizer.is_start_word_token(c) and seg_tokens:
-						flush()
-						seg_tokens, t_begin = [], at(j)
+						flush(j)
+						seg_tokens, t_begin, j_first = [], at(j), j
 					seg_tokens.append(c)
 					t_end = at(j) if ts is not None else end[i]
 				if seg_tokens:
-					flush()
+					flush(len(toks))
 				alternatives.append(transcript)
 			result.append(alternatives)
+		if spans is not None and spans['segments']:
+			stats = ops.frame_uncertainty(log_probs, tokenizer.eps_id, output_lengths)
+			span = ops.span_uncertainty(log_probs, stats, spans['utt'], spans['begin'], spans['end'], spans['first'], spans['tokens'], spans['frames'])
+			fields = torch.stack([getattr(span, key) for key in UNCERTAINTY_KEYS]).cpu().tolist()
+			for k, seg in enumerate(spans['segments']):
+				seg.update({key: column[k] for key, column in zip(UNCERTAINTY_KEYS, fields)})
 		return result

@@ -722,6 +722,67 @@ int convasr_ctc_greedy_segments(const int64_t* path, const int64_t* lengths, int
                                 int64_t* seg_first, int32_t* seg_begin, int32_t* seg_end, void* workspace, int64_t workspace_bytes, int B, int T,
                                 int eps, int space, int blank_amount_to_space, int split_words, void* stream);
 
+/* ---- Uncertainty: how sure the model is of a frame and of a word (models.py:645-678 entropy / weighted_mean_entropy / margin in their
+ * per-frame forms, the per-frame curves of vis.py:365-369, 382) --------------------------------------------------------------------------- */
+
+/* Per-frame statistics of channels-last fp32 log-probs (B, T, C) in ONE read.  lengths (B,) int64 may be NULL (all T frames); n_b =
+ * clamp(lengths[b], 0, T).  Every output is (B, T) and any output pointer may be NULL.
+ *   idx int64: the index convasr_argmax gives, under the same total order on (value, index) pairs: NaN ranks above every number, two NaNs
+ *     are equal, among equals the lower index wins.  Written for EVERY frame, also t >= n_b: bit for bit convasr_argmax's output.
+ * For a frame t < n_b, in fp32:
+ *   p1 = expf(lp[idx]);  p2 = expf(the largest value among the classes c != idx, same order);  margin = p1 - p2 (models.margin: the
+ *     difference of the two largest probabilities; an exact tie gives exactly 0).
+ *   entropy = -sum_c expf(lp[c]) * lp[c], the product written out as in the reference: a class at -inf gives NaN (0 * inf), as
+ *     convasr_entropy and torch do.
+ *   p_eps = expf(lp[eps_id]).
+ *   entropy_nb = the entropy of log_softmax over the classes c != eps_id (vis.py:367-368), from a max-subtracted log-sum-exp of its own:
+ *     with m = max_{c != eps_id} lp[c], d_c = lp[c] - m, S = sum expf(d_c), A = sum expf(d_c) * d_c:  entropy_nb = logf(S) - A / S.
+ *     (Not derived from entropy and p_eps: that form cancels when p_eps -> 1.)  Exactly 0 when C == 2; NaN when such a class is at -inf.
+ *   A frame that holds a NaN has all five float outputs NaN.
+ * For a frame t >= n_b the five float outputs are 0 (the reference's temporal_mask multiply, as a select: nothing past the length shows).
+ * Sums run in a fixed order: C <= convasr_frame_uncertainty_row_classes() in class order, one thread per frame; above it per-lane partial
+ * sums over c = lane, lane + 64, ... and a xor butterfly over the 64 lanes, one wave per frame.  Two runs are bit-equal.
+ * One launch, no workspace, no memset or copy: the call can be captured into a graph.  Envelope, checked before any launch: B >= 1,
+ * T >= 1, B * T < 2^31, 2 <= C <= CONVASR_UNCERTAINTY_MAX_CLASSES, 0 <= eps_id < C, log_probs not NULL; outside it CONVASR_EINVAL. */
+#define CONVASR_UNCERTAINTY_MAX_CLASSES 8192
+int convasr_frame_uncertainty_row_classes(void);
+int convasr_frame_uncertainty(const float* log_probs, const int64_t* lengths, int64_t* idx, float* p1, float* margin, float* entropy,
+                              float* entropy_nb, float* p_eps, int B, int T, int C, int eps_id, void* stream);
+
+/* Statistics of N spans (words) over the per-frame arrays above.  Span k lies in utterance utt[k] (int64) and covers the positions
+ * [begin[k], end[k]] (int32, inclusive) of a grid of Tp positions per utterance.  frame_map NULL: Tp == T and position p IS frame p.
+ * frame_map (B, Tp) int64 given: position p of utterance b stands for frame frame_map[b, p] of the (B, T) arrays (a forced alignment: the
+ * positions are those of a transcript); the span then covers the frames [frame_map[begin], max(frame_map[begin], frame_map[end])].
+ * Events (optional; first, tokens and frames come together): span k owns the events j in [first[k], first[k + 1]) of n_events packed
+ * pairs (tokens[j] int64, frames[j] int32 = a position); first has N + 1 entries.  Event j COUNTS unless
+ *   (a) path (B, Tp) int64 is given and path[utt, frames[j]] != tokens[j]: an inserted space of the greedy rule, which its frame does not
+ *       assert; or
+ *   (b) j > first[k] and event j equals event j - 1 in token and position: the word-start space convasr_ctc_greedy_segments stores twice.
+ * Both are decided on the positions, before the map.  With f_j the frame of event j, l_j = log_probs[utt, f_j, tokens[j]] over the n events
+ * that count:
+ *   n_events_out int32 = n
+ *   confidence     = expf((sum_j l_j) / n)          the geometric mean of the tokens' probabilities
+ *   confidence_min = expf(min_j l_j)
+ *   margin         = min_j m_j,  m_j = margin[utt, f_j] when tokens[j] == idx[utt, f_j], else expf(l_j) - p1[utt, f_j]  (<= 0)
+ *   entropy        = the mean of entropy[utt, t] over the span's frames
+ *   uncertainty    = sum_t entropy_t (1 - p_eps_t) / (eps + sum_t (1 - p_eps_t)) over the span's frames: weighted_mean_entropy
+ *                    (models.py:660-674) of the word alone
+ * n == 0: confidence, confidence_min and margin are 0.  Without events only entropy and uncertainty are written (the other four output
+ * pointers and log_probs, idx, p1, margin may be NULL).  A NaN among the l_j or m_j makes the minimum NaN.
+ * Sums are taken in fp64 and rounded to fp32 once: thread i of the span's 256-thread workgroup adds frames begin + i, begin + i + 256, ...
+ * (events likewise), then a xor butterfly per wave, then the four waves in order.  The order depends on the span alone: a span's outputs do
+ * not change with N, with the other spans or with their order, and two runs are bit-equal.  A span may be one frame or a whole recording.
+ * One launch, no workspace, no memset or copy: the call can be captured into a graph.  Envelope: 1 <= N < 2^31, B >= 1, T >= 1, Tp >= 1,
+ * B * T and B * Tp < 2^31, Tp == T without a map, 2 <= C <= CONVASR_UNCERTAINTY_MAX_CLASSES, eps >= 0, n_events >= 0, no path without
+ * events, no NULL among the pointers a form needs: checked before the launch, CONVASR_EINVAL outside it.  What only the device sees is
+ * clamped there and never read out of bounds: utt into [0, B), begin into [0, Tp), end into [begin, Tp), first into [0, n_events] and
+ * non-decreasing, event positions into [0, Tp), tokens into [0, C) (rule (a) and (b) compare the values as given), mapped frames into [0, T). */
+int convasr_span_uncertainty(const float* log_probs, const int64_t* idx, const float* p1, const float* margin, const float* entropy,
+                             const float* p_eps, const int64_t* utt, const int32_t* begin, const int32_t* end, const int64_t* first,
+                             const int64_t* tokens, const int32_t* frames, int64_t n_events, const int64_t* path, const int64_t* frame_map,
+                             int Tp, int32_t* n_events_out, float* confidence, float* confidence_min, float* margin_out, float* entropy_out,
+                             float* uncertainty, int64_t N, int B, int T, int C, float eps, void* stream);
+
 /* ---- Alignment: metrics.py:365-407 (align_strings) and its aligner (metrics.py:447-645), the step every error analysis of the reference
  * starts with (ErrorAnalyzer.analyze, transcribe.py --align-words) ------------------------------------------------------------------------ */
 
