@@ -127,6 +127,11 @@ _SIGNATURES = dict(
 	convasr_frame_uncertainty_row_classes = (c_int, []),
 	convasr_frame_uncertainty = (c_int, [c_p] * 8 + [c_int] * 4 + [c_p]),
 	convasr_span_uncertainty = (c_int, [c_p] * 12 + [c_i64, c_p, c_p, c_int] + [c_p] * 6 + [c_i64, c_int, c_int, c_int, c_f32, c_p]),
+	convasr_ctc_keyword_search_max_labels = (c_int, []),
+	convasr_ctc_keyword_search_phrases_per_block = (c_int, []),
+	convasr_ctc_keyword_search_staged_classes = (c_int, []),
+	convasr_ctc_keyword_search_tile_frames = (c_int, [c_int]),
+	convasr_ctc_keyword_search = (c_int, [c_p] * 11 + [c_int] * 8 + [c_p]),
 	convasr_nw_align_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
 	convasr_nw_align = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_nw_align_long_tile = (c_int, []),

@@ -1,4 +1,4 @@
-"""Host mirror of the reference's ctc.py: forced alignment on the GPU."""
+"""Host mirror of the reference's ctc.py: forced alignment on the GPU; and this package's own keyword search (`search`)."""
 import torch
 
 from . import ops
@@ -29,3 +29,19 @@ def alignment_long_bct(log_probs_bct, targets, input_lengths, target_lengths, bl
 	"""Same for the model's own output layout: logical (B, C, T) whose memory is (B, T, C)."""
 	assert ops.is_cl(log_probs_bct)
 	return ops.ctc_alignment_long(log_probs_bct.permute(0, 2, 1).float().contiguous(), targets, input_lengths, target_lengths, blank, chunk_frames = chunk_frames)
+
+
+def search(log_probs, tokens, token_lengths, blank, thresholds, lengths = None, min_gap: int = 10, max_hits: int = 16, dense: bool = False):
+	"""Where each of K phrases is said in every utterance, and how sure the model is (this package's own detector; the reference has none, and it is
+	unpinned against any outside keyword spotter): log_probs (T, B, C) as `alignment` takes them, log-probs or logits; tokens (K, L_max) and
+	token_lengths (K,) the phrases' labels; thresholds a float or (K,) values; lengths (B,) frames or None; min_gap in frames.  Returns
+	ops.ctc_keyword_search's namespace: count (B, K), score / begin / end (B, K, H), dense_score / dense_begin (B, K, T) or None.  A score is the
+	log-likelihood ratio of the phrase's best alignment on [begin, end] against the greedy path there: 0 at best, not a calibrated probability.
+	include/convasr_hip.h (convasr_ctc_keyword_search) has the rule."""
+	return ops.ctc_keyword_search(log_probs.float().permute(1, 2, 0), tokens, token_lengths, blank, thresholds, lengths = lengths, min_gap = min_gap, max_hits = max_hits, dense = dense)
+
+
+def search_bct(log_probs_bct, tokens, token_lengths, blank, thresholds, lengths = None, min_gap: int = 10, max_hits: int = 16, dense: bool = False):
+	"""Same for the model's own output layout: logical (B, C, T) whose memory is (B, T, C)."""
+	assert ops.is_cl(log_probs_bct)
+	return ops.ctc_keyword_search(log_probs_bct, tokens, token_lengths, blank, thresholds, lengths = lengths, min_gap = min_gap, max_hits = max_hits, dense = dense)

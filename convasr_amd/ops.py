@@ -1025,6 +1025,72 @@ def ctc_alignment_long(log_probs_btc, targets, input_lengths, target_lengths, bl
 	return out
 
 
+# ------------------------------------------------------------------------------------------------ keyword search
+
+def ctc_keyword_search_limits():
+	"""(labels per phrase at most, phrases per workgroup, classes up to which frames are staged through LDS) of convasr_ctc_keyword_search
+	(tests straddle them)."""
+	return _cached_query('convasr_ctc_keyword_search_max_labels'), _cached_query('convasr_ctc_keyword_search_phrases_per_block'), _cached_query('convasr_ctc_keyword_search_staged_classes')
+
+
+def ctc_keyword_search_tile_frames(C):
+	"""Frames of one tile of convasr_ctc_keyword_search at C classes (tests straddle it)."""
+	return _query('convasr_ctc_keyword_search_tile_frames', int(C))
+
+
+def ctc_keyword_search(log_probs, tokens, token_lengths, blank, thresholds, lengths = None, min_gap = 10, max_hits = 16, dense = False):
+	"""Where in every utterance each of K phrases is said (include/convasr_hip.h: convasr_ctc_keyword_search has the rule).  log_probs (B, C, T)
+	log-probs or logits; tokens (K, L_max) and token_lengths (K,) integers (a tensor, an array or lists); thresholds a float or (K,) values;
+	lengths (B,) frames or None; min_gap in frames.  Returns a namespace of device tensors: count (B, K) int32, score fp32 / begin / end int32
+	(B, K, H) with the first count[b, k] entries of a row filled (the rest -inf / -1) and dense_score / dense_begin (B, K, T) or None.  H is
+	max_hits, or the largest count where that is more: the search then runs once more at that capacity, so no hit is dropped (the count is
+	read on the host: one synchronisation).  A label equal to blank or outside [0, C), an empty phrase or phrase list and shapes that do not
+	fit raise ValueError before any launch; outside the kernel's envelope (a phrase of more than 64 labels, ...) ConvasrHipError."""
+	require_cuda(log_probs)
+	if log_probs.ndim != 3:
+		raise ValueError(f'ctc_keyword_search: (B, C, T) log-probs expected, got shape {tuple(log_probs.shape)}')
+	B, C, T = log_probs.shape
+	tok, tl = torch.as_tensor(tokens).cpu(), torch.as_tensor(token_lengths).cpu()
+	if tok.ndim != 2 or tok.shape[0] < 1 or tok.shape[1] < 1 or tok.dtype.is_floating_point:
+		raise ValueError(f'ctc_keyword_search: tokens must be (K, L_max) integers with K, L_max >= 1, got shape {tuple(tok.shape)}')
+	K = tok.shape[0]
+	if tl.shape != (K,) or tl.dtype.is_floating_point or int(tl.min()) < 1 or int(tl.max()) > tok.shape[1]:
+		raise ValueError(f'ctc_keyword_search: token_lengths must be (K,) = ({K},) integers in [1, {tok.shape[1]}], got shape {tuple(tl.shape)}')
+	if not -C <= int(blank) < C:
+		raise ValueError(f'ctc_keyword_search: blank {blank} for {C} classes')
+	blank = int(blank) % C
+	if int(min_gap) < 0 or int(max_hits) < 1:
+		raise ValueError(f'ctc_keyword_search: min_gap {min_gap} must be >= 0 and max_hits {max_hits} >= 1')
+	tok = tok[:, :int(tl.max())].to(torch.int64)
+	used = torch.arange(tok.shape[1]).unsqueeze(0) < tl.unsqueeze(1)
+	if bool(((tok == blank) & used).any()):
+		raise ValueError(f'ctc_keyword_search: a phrase holds the blank {blank}')
+	if bool((((tok < 0) | (tok >= C)) & used).any()):
+		raise ValueError(f'ctc_keyword_search: a label outside [0, {C})')
+	dev = log_probs.device
+	thr = torch.as_tensor(thresholds, dtype = torch.float32)
+	thr = thr.expand(K) if thr.ndim == 0 else thr
+	if thr.shape != (K,):
+		raise ValueError(f'ctc_keyword_search: thresholds of shape {tuple(thr.shape)} for {K} phrases')
+	thr = thr.to(dev).contiguous()
+	lengths = None if lengths is None else _frame_lengths('ctc_keyword_search', lengths, B, T, dev)
+	lp = as_cl(log_probs, torch.float32)
+	tok, tl = (tok * used).to(device = dev, dtype = torch.int32).contiguous(), tl.to(device = dev, dtype = torch.int32).contiguous()
+	count = torch.empty(B, K, dtype = torch.int32, device = dev)
+	dense_score = torch.empty(B, K, T, dtype = torch.float32, device = dev) if dense else None
+	dense_begin = torch.empty(B, K, T, dtype = torch.int32, device = dev) if dense else None
+	H = int(max_hits)
+	while True:
+		score = torch.full((B, K, H), float('-inf'), dtype = torch.float32, device = dev)
+		begin, end = torch.full((2, B, K, H), -1, dtype = torch.int32, device = dev).unbind(0)
+		call('convasr_ctc_keyword_search', ptr(lp), ptr(lengths), ptr(tok), ptr(tl), ptr(thr), ptr(count), ptr(score), ptr(begin), ptr(end), ptr(dense_score), ptr(dense_begin),
+		     B, T, C, K, tok.shape[1], H, blank, int(min_gap), stream_ptr())
+		most = int(count.max())
+		if most <= H:
+			return types.SimpleNamespace(count = count, score = score, begin = begin, end = end, dense_score = dense_score, dense_begin = dense_begin)
+		H = most
+
+
 # ------------------------------------------------------------------------------------------------ decoding
 
 def _beam_route(name, args, wide):

@@ -12,6 +12,10 @@
 * transcribe_file(...) / transcribe_long(...)
   transcribe_batch on a wav / raw file: every channel as one row, or -- for a long recording -- the speech cut at silences (vad.segments) or
   at given segments and gathered into padded batches on the GPU, the words back on the recording's clock.
+* search_batch(...) / search_long(...)
+  this package's own (the reference has no keyword search): where phrases are SAID in a batch or in a long recording -- the model call of
+  transcribe_batch, then ctc.search_bct on its log-probs (ops.ctc_keyword_search: the CTC lattice of every phrase started at every frame,
+  scored against the greedy path), hits as segments on the same clock as the words.
 
 Out of scope: file discovery, audio decoding, the dataset, text pre/post-processing pipelines (regexes, number
 normalisation) and the json / html / csv / txt writers around this body (CER and the error analysis live in metrics).  A TextPipeline here is the tokenizer
@@ -84,6 +88,17 @@ def setup(args):
 	return text_pipeline, frontend, model, generator
 
 
+def _forward(args, model, x, xlen):
+	"""The model call of transcribe_batch and search_batch and the per-frame time stamps (transcribe.py:150-160): x (B, 1, T) or (B, T) waveform,
+	xlen (B,) fractions -> log_probs, logits, olen, ts (B, frames) seconds from the batch's first sample."""
+	device = torch.device(args.device)
+	x = x.squeeze(1) if x.ndim == 3 else x
+	log_probs, logits, olen = model(x.to(device), xlen.to(device))
+	duration = x.shape[-1] / args.sample_rate
+	ts = duration * torch.linspace(0, 1, steps = log_probs.shape[-1], device = log_probs.device).unsqueeze(0).expand(x.shape[0], -1)
+	return log_probs, logits, olen, ts
+
+
 def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end, y = None, ylen = None, segment_extra_info = None):
 	"""One iteration of transcribe.main's loop (transcribe.py:140-200) on a collated batch: x (B, 1, T) or (B, T) waveform,
 	xlen (B,) fractions, begin / end (B,) seconds, optional targets y (B, L, S) / ylen (B, L) for --align.
@@ -95,11 +110,7 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 	metrics.align_words(*metrics.align_strings(hyp = hyp, ref = ref)) (transcribe.py:235), the strings of the whole batch aligned in two
 	GPU launches; words is None otherwise."""
 	device = torch.device(args.device)
-	x = x.squeeze(1) if x.ndim == 3 else x
-	log_probs, logits, olen = model(x.to(device), xlen.to(device))
-	B = x.shape[0]
-	duration = x.shape[-1] / args.sample_rate
-	ts = duration * torch.linspace(0, 1, steps = log_probs.shape[-1], device = log_probs.device).unsqueeze(0).expand(B, -1)
+	log_probs, logits, olen, ts = _forward(args, model, x, xlen)
 	tokenizer = text_pipeline.tokenizer
 	with_uncertainty = bool(getattr(args, 'uncertainty', False))  # every word segment also carries transcript_generators.UNCERTAINTY_KEYS
 	hyp_segments = [alternatives[0] for alternatives in generator.generate(tokenizer = tokenizer, log_probs = log_probs, begin = begin, end = end, output_lengths = olen, time_stamps = ts, segment_text_key = 'hyp', segment_extra_info = segment_extra_info, **(dict(uncertainty = True) if with_uncertainty else {}))]
@@ -134,18 +145,10 @@ def transcribe_file(args, text_pipeline, model, generator, audio_path, **read_au
 	return transcribe_batch(args, text_pipeline, model, generator, signal, torch.ones(channels), torch.zeros(channels), torch.full((channels, ), duration))
 
 
-def transcribe_long(args, text_pipeline, model, generator, audio_or_signal, segments = None, **read_audio_kwargs):
-	"""A long recording as batches of utterance-sized segments instead of transcribe_file's one row per channel: the audio is read with
-	audio.read_audio at args.sample_rate and args.mono (default True) unless a (C, N) device tensor is given; it is cut into segments; the
-	segments, longest first (a stable sort by their sample counts), go in chunks of args.batch_size (default 64) through ops.gather_segments
-	-- one zero-padded batch per launch, padded to args.batch_time_padding_multiple (default 128) -- and transcribe_batch, with begin / end the
-	segments' seconds (float64 tensors: the Python floats as they are), so every word carries a time on the recording's clock, and its channel.
-	segments: None = vad.segments with args.vad_aggressiveness (default 2), args.vad_window_size (0.02) and args.vad_max_duration (15.0).  A list
-	of dicts with begin, end, channel -- a reference transcript (the reference's batched_transcript mode, datasets.py:261-262), or
-	diarization.diarize's output with channel = speaker - 1 -- is sliced by vad.segment_samples instead.
-	Returns a namespace: segments (dicts with begin, end, channel, first, count; by channel, then time), hyp_segments and hyp per segment in that
-	order, transcript (all word segments sorted by begin, end, channel) and text (per channel, the joined hypothesis in time order).  A
-	recording without speech returns empty lists and does not call the model."""
+def _long_batches(args, audio_or_signal, segments, read_audio_kwargs):
+	"""What transcribe_long and search_long share (their docstrings have the rules): the recording read, cut into segments (by channel, then
+	time) and gathered into padded batches, longest segments first.  Returns (channels, segments, batches); batches yields, per chunk of
+	args.batch_size segments, (their indices into segments, x, xlen, begin, end, segment_extra_info) as transcribe_batch takes them."""
 	from . import audio, ops, vad
 	if torch.is_tensor(audio_or_signal):
 		signal, sample_rate = audio_or_signal, args.sample_rate
@@ -163,15 +166,108 @@ def transcribe_long(args, text_pipeline, model, generator, audio_or_signal, segm
 		segments.sort(key = lambda s: (s['channel'], s['first']))
 	order = sorted(range(len(segments)), key = lambda i: -segments[i]['count'])
 	batch_size, multiple = getattr(args, 'batch_size', 64), getattr(args, 'batch_time_padding_multiple', 128)
+
+	def batches():
+		for at in range(0, len(order), batch_size):
+			idx = order[at:at + batch_size]
+			chunk = [segments[i] for i in idx]
+			x, xlen = ops.gather_segments(signal, [s['channel'] for s in chunk], [s['first'] for s in chunk], [s['count'] for s in chunk], multiple = multiple)
+			yield (idx, x, xlen, torch.tensor([s['begin'] for s in chunk], dtype = torch.float64), torch.tensor([s['end'] for s in chunk], dtype = torch.float64),
+			       [dict(channel = s['channel']) for s in chunk])
+	return channels, segments, batches()
+
+
+def transcribe_long(args, text_pipeline, model, generator, audio_or_signal, segments = None, **read_audio_kwargs):
+	"""A long recording as batches of utterance-sized segments instead of transcribe_file's one row per channel: the audio is read with
+	audio.read_audio at args.sample_rate and args.mono (default True) unless a (C, N) device tensor is given; it is cut into segments; the
+	segments, longest first (a stable sort by their sample counts), go in chunks of args.batch_size (default 64) through ops.gather_segments
+	-- one zero-padded batch per launch, padded to args.batch_time_padding_multiple (default 128) -- and transcribe_batch, with begin / end the
+	segments' seconds (float64 tensors: the Python floats as they are), so every word carries a time on the recording's clock, and its channel.
+	segments: None = vad.segments with args.vad_aggressiveness (default 2), args.vad_window_size (0.02) and args.vad_max_duration (15.0).  A list
+	of dicts with begin, end, channel -- a reference transcript (the reference's batched_transcript mode, datasets.py:261-262), or
+	diarization.diarize's output with channel = speaker - 1 -- is sliced by vad.segment_samples instead.
+	Returns a namespace: segments (dicts with begin, end, channel, first, count; by channel, then time), hyp_segments and hyp per segment in that
+	order, transcript (all word segments sorted by begin, end, channel) and text (per channel, the joined hypothesis in time order).  A
+	recording without speech returns empty lists and does not call the model."""
+	channels, segments, batches = _long_batches(args, audio_or_signal, segments, read_audio_kwargs)
 	hyp_segments, hyp = [None] * len(segments), [None] * len(segments)
-	for at in range(0, len(order), batch_size):
-		chunk = [segments[i] for i in order[at:at + batch_size]]
-		x, xlen = ops.gather_segments(signal, [s['channel'] for s in chunk], [s['first'] for s in chunk], [s['count'] for s in chunk], multiple = multiple)
-		out = transcribe_batch(args, text_pipeline, model, generator, x, xlen, torch.tensor([s['begin'] for s in chunk], dtype = torch.float64), torch.tensor([s['end'] for s in chunk], dtype = torch.float64),
-		                       segment_extra_info = [dict(channel = s['channel']) for s in chunk])
-		for i, words, text in zip(order[at:at + batch_size], out.hyp_segments, out.hyp):
+	for idx, x, xlen, begin, end, extra in batches:
+		out = transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end, segment_extra_info = extra)
+		for i, words, text in zip(idx, out.hyp_segments, out.hyp):
 			hyp_segments[i], hyp[i] = words, text
 	transcript = sorted((w for words in hyp_segments for w in words), key = lambda w: (w['begin'], w['end'], w['channel']))
 	by_time = sorted(range(len(segments)), key = lambda i: (segments[i]['begin'], segments[i]['end']))
 	text = [join(hyp = [dict(hyp = hyp[i]) for i in by_time if segments[i]['channel'] == c]) for c in range(channels)]
 	return types.SimpleNamespace(segments = list(segments), hyp_segments = hyp_segments, hyp = hyp, transcript = transcript, text = text)
+
+
+def encode_phrases(text_pipeline, phrases):
+	"""Phrases as search_batch searches them: text_pipeline.preprocess, then tokenizer.encode.  Returns (texts, label lists).  ValueError for an
+	empty list, a phrase that is empty or does not come back from tokenizer.decode as it went in (CharTokenizerLegacy maps a character outside
+	its alphabet to '*'), one that holds the blank, and one of more labels than the kernel takes (64)."""
+	from . import ops
+	tokenizer = text_pipeline.tokenizer
+	texts = [text_pipeline.preprocess(p) for p in phrases]
+	if not texts:
+		raise ValueError('search: no phrases')
+	labels = [list(row) for row in tokenizer.encode(texts)]
+	limit = ops.ctc_keyword_search_limits()[0]
+	for phrase, text, row in zip(phrases, texts, labels):
+		if not row or tokenizer.eps_id in row or tokenizer.decode([row])[0] != text:
+			raise ValueError(f'search: the phrase {phrase!r} cannot be encoded with this tokenizer')
+		if len(row) > limit:
+			raise ValueError(f'search: the phrase {phrase!r} has {len(row)} labels, at most {limit} can be searched')
+	return texts, labels
+
+
+def search_batch(args, text_pipeline, model, x, xlen, begin, end, phrases, threshold_per_label = -1.0, min_gap_seconds = 0.2, segment_extra_info = None):
+	"""Where each of `phrases` is said in a collated batch (x, xlen, begin, end as transcribe_batch takes them): one model call, one
+	ctc.search_bct over its log-probs with the blank tokenizer.eps_id, thresholds[k] = threshold_per_label * (labels of phrase k) and min_gap =
+	min_gap_seconds in frames (rounded).  A phrase's spaces are ordinary labels: the model has to emit them.
+	Returns a namespace: log_probs, logits, olen, ts, found (ops.ctc_keyword_search's namespace, device tensors), phrases (the preprocessed
+	texts) and hits: per utterance a list of Segment(begin, end, phrase, score, score_per_label, **segment_extra_info[b]) sorted by begin, end
+	and the phrase's position in the list.  Times follow the greedy generator's convention, max(begin[b], 0) + ts[b, frame] at the hit's first
+	and last frame.  score is the acoustic log-likelihood ratio of the best alignment against the greedy path (0 = the greedy path says the
+	phrase there), not a calibrated probability."""
+	from .transcript_generators import Segment
+	texts, labels = encode_phrases(text_pipeline, phrases)
+	log_probs, logits, olen, ts = _forward(args, model, x, xlen)
+	B, _, T = log_probs.shape
+	K, lens = len(labels), [len(row) for row in labels]
+	tokens = torch.tensor([row + [0] * (max(lens) - len(row)) for row in labels], dtype = torch.int32)
+	duration = x.shape[-1] / args.sample_rate
+	min_gap = int(round(min_gap_seconds * (T - 1) / duration)) if T > 1 and duration > 0 else 0
+	found = ctc.search_bct(log_probs, tokens, torch.tensor(lens, dtype = torch.int32), text_pipeline.tokenizer.eps_id,
+	                       torch.tensor([threshold_per_label * n for n in lens], dtype = torch.float32), lengths = olen, min_gap = min_gap)
+	H = found.score.shape[2]
+	stored = (torch.arange(H, device = found.count.device) < found.count.unsqueeze(-1)).nonzero()  # (hits, 3): utterance, phrase, slot -- in that order
+	b_idx, k_idx, j_idx = stored.unbind(1)
+	first, last = found.begin[b_idx, k_idx, j_idx].long(), found.end[b_idx, k_idx, j_idx].long()
+	t_begin, t_end = ts[b_idx, first].cpu().tolist(), ts[b_idx, last].cpu().tolist()
+	scores, begin = found.score[b_idx, k_idx, j_idx].cpu().tolist(), torch.clamp(begin, min = 0.0).cpu().tolist()
+	hits = [[] for _ in range(B)]
+	for b, k, tb, te, sc in zip(b_idx.tolist(), k_idx.tolist(), t_begin, t_end, scores):
+		hit = Segment(begin = begin[b] + tb, end = begin[b] + te, phrase = texts[k], score = sc, score_per_label = sc / lens[k])
+		if segment_extra_info is not None:
+			hit.update(segment_extra_info[b])
+		hits[b].append((hit['begin'], hit['end'], k, hit))
+	hits = [[h[3] for h in sorted(row, key = lambda h: h[:3])] for row in hits]
+	return types.SimpleNamespace(log_probs = log_probs, logits = logits, olen = olen, ts = ts, found = found, phrases = texts, hits = hits)
+
+
+def search_long(args, text_pipeline, model, audio_or_signal, phrases, segments = None, threshold_per_label = -1.0, min_gap_seconds = 0.2, **read_audio_kwargs):
+	"""search_batch over a long recording: the segmenting and batching are transcribe_long's (its docstring has the rules; segments = None cuts
+	at silences, a list of dicts with begin, end, channel is sliced as given), every batch goes through search_batch with the segments' seconds
+	as begin / end and their channel as extra field.  A phrase is found only inside a segment: one that straddles a cut is not.
+	Returns a namespace: segments (as transcribe_long's), hits_per_segment in that order and hits: every hit, on the recording's clock and with
+	its channel, sorted by (begin, end, channel).  A phrase that cannot be encoded or has more than 64 labels raises ValueError before the audio
+	is read; a recording without speech returns empty lists and does not call the model."""
+	encode_phrases(text_pipeline, phrases)
+	channels, segments, batches = _long_batches(args, audio_or_signal, segments, read_audio_kwargs)
+	per_segment = [None] * len(segments)
+	for idx, x, xlen, begin, end, extra in batches:
+		out = search_batch(args, text_pipeline, model, x, xlen, begin, end, phrases, threshold_per_label = threshold_per_label, min_gap_seconds = min_gap_seconds, segment_extra_info = extra)
+		for i, found in zip(idx, out.hits):
+			per_segment[i] = found
+	hits = sorted((h for found in per_segment for h in found), key = lambda h: (h['begin'], h['end'], h['channel']))
+	return types.SimpleNamespace(segments = list(segments), hits_per_segment = per_segment, hits = hits)

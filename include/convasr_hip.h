@@ -783,6 +783,60 @@ int convasr_span_uncertainty(const float* log_probs, const int64_t* idx, const f
                              int Tp, int32_t* n_events_out, float* confidence, float* confidence_min, float* margin_out, float* entropy_out,
                              float* uncertainty, int64_t N, int B, int T, int C, float eps, void* stream);
 
+/* ---- Keyword search: where in an utterance is a phrase said, and how sure is the model.  The project's own detector (the reference has
+ * none): unpinned against any outside keyword spotter ------------------------------------------------------------------------------------- */
+
+/* The CTC lattice of each of K phrases, started at every frame of every utterance and scored against the frame-wise best path; one launch.
+ * Inputs: log_probs (B, T, C) channels-last fp32 (only differences within a frame matter, so logits give the same result); lengths (B,)
+ * int64 or NULL (all T frames), n_b = clamp(lengths[b], 0, T); tokens (K, L_max) int32 with token_lengths (K,) int32 labels each, every
+ * label in [0, C) and != blank; thresholds (K,) fp32; min_gap >= 0 frames; a capacity of H >= 1 hits per (utterance, phrase).
+ * Frame scores: m_t = the largest lp[t, c] over c, NaNs ignored (fmaxf); d_t(c) = lp[t, c] - m_t in ONE fp32 subtraction, a NaN result
+ *   counts as -inf.  So d <= 0 and d = 0 on the frame's argmax: the sum of d along a path is the log-likelihood ratio of that path
+ *   against the greedy path.
+ * Values: a value is a pair (score fp32, begin int32).  better(...) takes the largest score, among equal finite scores the smallest begin; a
+ *   score of -inf always carries begin -1.  v + x adds x to the score in ONE fp32 addition and keeps begin; a result of -inf resets begin
+ *   to -1.
+ * Recurrence, for a phrase y_0 .. y_{L-1} over the frames t = 0 .. n_b - 1, everything (-inf, -1) before frame 0:
+ *   A_0(t) = better(A_0(t-1), (0, t))                                             + d_t(y_0)
+ *   A_i(t) = better(A_i(t-1), Z_{i-1}(t-1), A_{i-1}(t-1) only if y_i != y_{i-1})  + d_t(y_i)     0 < i < L
+ *   Z_i(t) = better(Z_i(t-1), A_i(t-1))                                           + d_t(blank)   0 <= i < L - 1
+ *   E(t)   = A_{L-1}(t)
+ *   A_i is the label, Z_i the blank after it; no blank before the first label or after the last one, so a span is tight.  E(t) is the best
+ *   occurrence that ends at frame t, with its first frame: the maximum over all start frames and all CTC alignments of the phrase on
+ *   [begin, t], ties to the earliest begin.  A phrase's spaces are ordinary labels: the model has to emit them.
+ * Hit picker, per (utterance, phrase), sequential in t, with cand = none and last_end = -1:
+ *   (s, b) = E(t)
+ *   if s >= threshold and b > last_end and (cand is none or s > cand.score or (s == cand.score and b == cand.begin)): cand = (s, b, t)
+ *   if cand is not none and t - cand.end >= min_gap: emit cand; last_end = cand.end; cand = none
+ *   after the last frame: emit cand if there is one
+ *   Hits come out in the order of their end frames and are disjoint.
+ * Outputs: count (B, K) int32 counts EVERY hit; hit_score fp32, hit_begin, hit_end int32, each (B, K, H), hold the first H of them and are
+ *   untouched beyond (an utterance of length 0: count 0, rows untouched).  dense_score fp32 / dense_begin int32 (B, K, T), both or neither
+ *   (NULL): E(t), and (-inf, -1) at the frames t >= n_b.
+ * Every score is a chain of fp32 additions along one path in time order, with no multiplication, and the maximum does not depend on order:
+ * the result is independent of how the kernel maps work to lanes, bit-equal to a float32 restatement (tests/_kws_ref.py) on any finite or
+ * -inf input, and two runs are bit-equal.  Scores are acoustic log-likelihood ratios, not calibrated probabilities.
+ * Mapping: one wave per (utterance, phrase), lane i holds A_i and Z_i; the waves of a workgroup take phrases of one utterance and share its
+ * frames, staged through LDS in tiles up to the staging limit of classes, gathered from global memory above it (csrc/kws.hip).  One launch, no
+ * workspace, no memset or copy: the call can be captured into a graph.
+ * Envelope, checked before the launch: 1 <= L_max <= CONVASR_KWS_MAX_LABELS, 2 <= C <= CONVASR_KWS_MAX_CLASSES, 1 <= T <=
+ * CONVASR_KWS_MAX_FRAMES, 1 <= B, K <= 65535; outside it CONVASR_EUNSUPPORTED with a message and nothing written.  Any other bad argument
+ * (NULL, H < 1, min_gap < 0, blank outside [0, C), one dense pointer without the other) CONVASR_EINVAL.  What only the device sees is clamped
+ * there and never read out of bounds: token_lengths into [0, L_max] (0: count 0, no hit), labels into [0, C).
+ * Pure queries (what the tests straddle): the label limit; the phrases (= waves) of one workgroup; the class count up to which frames are
+ * staged through LDS; the frames of one tile at C classes (negative outside the envelope of C). */
+#define CONVASR_KWS_MAX_LABELS 64
+#define CONVASR_KWS_MAX_CLASSES 8192
+#define CONVASR_KWS_MAX_FRAMES (1 << 20)
+int convasr_ctc_keyword_search_max_labels(void);
+int convasr_ctc_keyword_search_phrases_per_block(void);
+int convasr_ctc_keyword_search_staged_classes(void);
+int convasr_ctc_keyword_search_tile_frames(int C);
+int convasr_ctc_keyword_search(const float* log_probs, const int64_t* lengths, const int32_t* tokens, const int32_t* token_lengths,
+                               const float* thresholds, int32_t* count, float* hit_score, int32_t* hit_begin, int32_t* hit_end,
+                               float* dense_score, int32_t* dense_begin, int B, int T, int C, int K, int L_max, int H, int blank, int min_gap,
+                               void* stream);
+
 /* ---- Alignment: metrics.py:365-407 (align_strings) and its aligner (metrics.py:447-645), the step every error analysis of the reference
  * starts with (ErrorAnalyzer.analyze, transcribe.py --align-words) ------------------------------------------------------------------------ */
 
