@@ -19,7 +19,7 @@ W_REFERENCE, W_KMAJOR = 0, 1  # include/convasr_hip.h: memory layout of a (Cout,
 METRIC_CHARS, METRIC_WORDS = 0, 1  # include/convasr_hip.h: CONVASR_METRIC_CHARS / CONVASR_METRIC_WORDS
 METRIC_MAX_LEN = 16383  # CONVASR_METRIC_MAX_LEN
 
-c_int, c_i64, c_u64, c_f32, c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
+c_int, c_i64, c_u64, c_f32, c_p, c_u32 = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32
 
 _SIGNATURES = dict(
 	convasr_abi_version = (c_int, []),
@@ -169,6 +169,15 @@ _SIGNATURES = dict(
 	convasr_vad_segments_count = (c_int, [c_p, c_p, c_int, c_i64, c_i64, c_p, c_i64, c_p]),
 	convasr_vad_segments_write = (c_int, [c_p, c_int, c_i64, c_int, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p]),
 	convasr_gather_segments = (c_int, [c_p, c_int, c_int, c_i64, c_p, c_p, c_int, c_p, c_i64, c_p]),
+	convasr_philox = (c_int, [c_p, c_i64, c_u32, c_u32, c_p, c_p]),
+	convasr_augment_tile = (c_int, []),
+	convasr_augment_phases = (c_int, []),
+	convasr_augment_parts = (c_int, []),
+	convasr_augment_params = (c_int, [c_p, c_p, c_p, c_int, c_i64, c_u64, c_i64, ctypes.POINTER(c_u64), c_int, c_u32, c_int, c_u32, c_i64, c_i64, c_int, c_u32, c_p, c_p, c_p]),
+	convasr_augment_waveform = (c_int, [c_p, c_int, c_int, c_i64, c_p, c_p, c_int, c_int, c_p, c_int, c_p, c_i64, c_i64, c_p, c_p, c_p]),
+	convasr_augment_mix = (c_int, [c_p, c_int, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_int, c_p, c_p, c_p]),
+	convasr_spec_augment_tile = (c_int, []),
+	convasr_spec_augment = (c_int, [c_p, c_p, c_p, c_p, c_u64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_u32, c_int, c_f32, c_p, c_p, c_p, c_p]),
 )
 VAD_MAX_CHANNELS, VAD_MAX_LEN, VAD_MAX_FRAME = 8, 1 << 28, 65536  # include/convasr_hip.h: the envelope of convasr_frame_peak and its neighbours
 SLIDE_ABS, SLIDE_NEG = 1, 2  # include/convasr_hip.h: CONVASR_SLIDE_ABS / CONVASR_SLIDE_NEG

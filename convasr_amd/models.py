@@ -446,6 +446,7 @@ class JasperNet(nn.Module):
 		self.backbone = nn.ModuleList(blocks)
 		self.num_epilogue_modules = 2
 		self.frontend = frontend
+		self.feature_transform = None  # e.g. augment.SpecAugment: applied to the frontend's features in train() mode only
 		self.normalize_features = MaskedInstanceNorm1d(num_input_features, affine = False, eps = normalize_features_eps, track_running_stats = normalize_features_track_running_stats, temporal_mask = normalize_features_temporal_mask, legacy = normalize_features_legacy) if normalize_features else None
 		self.decoder = Decoder(width(out_width_factors_large[1]), num_classes, type = decoder_type)
 		self.residual, self.dict, self.bpe_only, self.check_time_dim_padded = residual, dict, bpe_only, check_time_dim_padded
@@ -488,6 +489,8 @@ class JasperNet(nn.Module):
 			assert (not self.check_time_dim_padded) or (x.shape[-1] % (32 / 2) == 0), 'Shape of input signal is not divisible by 16 '
 			x = x.squeeze(1)
 			x = self.frontend(x, xlen = xlen) if isinstance(self.frontend, LogFilterBankFrontend) else self.frontend(x, mask = temporal_mask(x, compute_output_lengths(x, xlen)) if xlen is not None else None)
+			if self.feature_transform is not None and self.training:
+				x = self.feature_transform(x, xlen)
 		assert (not self.check_time_dim_padded) or (x.shape[-1] % 32 == 0), 'Shape of features after frontend is not divisible by 32'
 		assert x.ndim == 3
 		if self.normalize_features is not None:

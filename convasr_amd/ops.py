@@ -1672,3 +1672,163 @@ def gather_segments(signal, channel, first, count, multiple = 128):
 	call('convasr_gather_segments', ptr(signal), dtype_code(signal.dtype), C, N, host.data_ptr(), ptr(seg), B, ptr(x), Tpad, stream_ptr())
 	xlen = torch.tensor([l / Tpad for l in host[2].tolist()], dtype = torch.float32).to(signal.device, non_blocking = True)
 	return x, xlen
+
+
+# ------------------------------------------------------------------------------------------------ training-time augmentation (the project's own, unpinned: include/convasr_hip.h)
+
+AUG_ONE = 1 << 32  # speed 1.0 in the 32.32 fixed point of convasr_augment_params
+AUG_FIELDS = ('speed', 'step', 'gain', 'noise_row', 'noise_offset', 'snr', 'len', 'out_len')  # the columns of the (B, 8) parameter tensor
+
+
+def philox(counters, key):
+	"""convasr_philox: the raw Philox4x32-10 blocks of the augmentation generator.  counters (N, 4) int64 holding 32-bit words on the device,
+	key two 32-bit words.  Returns (N, 4) int64, the four output words of every block."""
+	require_cuda(counters)
+	if counters.ndim != 2 or counters.shape[1] != 4 or counters.dtype != torch.int64:
+		raise ValueError(f'philox: (N, 4) int64 counters expected, got {tuple(counters.shape)} {counters.dtype}')
+	counters = counters.contiguous()
+	out = torch.empty_like(counters)
+	call('convasr_philox', ptr(counters), counters.shape[0], int(key[0]) & 0xffffffff, int(key[1]) & 0xffffffff, ptr(out), stream_ptr())
+	return out
+
+
+def augment_tile():
+	"""Outputs per tile of convasr_augment_waveform (tests straddle it)."""
+	return _cached_query('convasr_augment_tile')
+
+
+def augment_phases():
+	"""Tabulated phases per input sample of the speed filter."""
+	return _cached_query('convasr_augment_phases')
+
+
+def prob_threshold(p):
+	"""floor(p * 2^24): a draw fires when its top 24 bits are below it."""
+	if not 0.0 <= float(p) <= 1.0:
+		raise ValueError(f'a probability in [0, 1] expected, got {p}')
+	return int(math.floor(float(p) * (1 << 24)))
+
+
+def augment_steps(speeds):
+	"""round(speed * 2^32) per speed, the fixed-point steps of include/convasr_hip.h (halves round up; speed * 2^32 is exact in float64)."""
+	return [int(math.floor(float(s) * AUG_ONE + 0.5)) for s in speeds]
+
+
+def augment_table(steps, zeros = RESAMPLE_ZEROS, beta = RESAMPLE_BETA, rolloff = RESAMPLE_ROLLOFF):
+	"""The (n_speeds, taps, phases + 1) fp32 filter table of convasr_augment_waveform, computed in float64 on the host and rounded once, and its
+	taps.  (None, 0) when every speed is 1.0: nothing is filtered."""
+	import numpy as np
+	if all(s == AUG_ONE for s in steps):
+		return None, 0
+	P = augment_phases()
+	cut = [float(rolloff) * min(1.0, AUG_ONE / s) for s in steps]
+	H = int(math.floor(float(zeros) / min(cut)))
+	taps = 2 * H + 2
+	d = (np.arange(taps, dtype = np.float64)[:, None] - H) - np.arange(P + 1, dtype = np.float64)[None, :] / P
+	tab = np.zeros((len(steps), taps, P + 1), dtype = np.float32)
+	for i, c in enumerate(cut):
+		v = d * c / float(zeros)
+		h = c * np.sinc(c * d) * np.i0(float(beta) * np.sqrt(np.clip(1.0 - v * v, 0.0, None))) / np.i0(float(beta))
+		tab[i] = np.where(np.abs(d) * c <= float(zeros), h, 0.0).astype(np.float32)
+	return torch.from_numpy(tab), taps
+
+
+def db_table(lo_db, hi_db, steps, sign = 1.0):
+	"""`steps` values 10^(sign * dB / 20), dB evenly spaced from lo_db to hi_db (one step: lo_db), in float64, rounded once to fp32."""
+	import numpy as np
+	db = np.linspace(float(lo_db), float(hi_db), int(steps), dtype = np.float64) if int(steps) > 1 else np.full(int(steps), float(lo_db), dtype = np.float64)
+	return torch.from_numpy((10.0 ** (sign * db / 20.0)).astype(np.float32))
+
+
+def _augment_batch(name, x):
+	require_cuda(x)
+	if x.ndim != 2 or x.dtype not in (torch.int16, torch.float32):
+		raise ValueError(f'{name}: a (B, T) int16 or float32 batch expected, got {tuple(x.shape)} {x.dtype}')
+	if x.shape[1] >= 1 << 31:
+		raise _lib.ConvasrHipError(f'{name}: T {x.shape[1]} >= 2^31')
+	return x.contiguous()
+
+
+def _same_device(name, dev, **tensors):
+	for what, t in tensors.items():
+		if t is not None and t.device != dev:
+			raise _lib.ConvasrHipError(f'{name}: {what} lives on {t.device}, the batch on {dev}')
+
+
+def augment_params(xlen, keys, T, seed, epoch, steps, speed_thr = 1 << 24, gain_steps = 0, gain_thr = 0, noise_shape = None, snr_steps = 1, noise_thr = 0, min_out_len = None):
+	"""convasr_augment_params: every random decision of the waveform augmentation as integers.  xlen (B,) float32 fractions of T, keys (B,) int64,
+	steps a list of fixed-point speeds (augment_steps), the thresholds from prob_threshold, noise_shape = (rows, samples) of the noise bank or
+	None.  Returns (params (B, 8) int64 with the columns AUG_FIELDS, xlen_out (B,) float32 = out_len / T).  One launch; B == 0 or T == 0: none."""
+	require_cuda(xlen, keys)
+	dev = xlen.device
+	B, T = xlen.shape[0], int(T)
+	_same_device('augment_params', dev, keys = keys, min_out_len = min_out_len)
+	if keys.shape != (B,) or keys.dtype != torch.int64 or (min_out_len is not None and (min_out_len.shape != (B,) or min_out_len.dtype != torch.int64)):
+		raise ValueError(f'augment_params: keys and min_out_len must be ({B},) int64 tensors')
+	xlen, keys = xlen_f32(xlen, dev), keys.contiguous()
+	min_out_len = None if min_out_len is None else min_out_len.contiguous()
+	rows, samples = (0, 0) if noise_shape is None else (int(noise_shape[0]), int(noise_shape[1]))
+	params = torch.zeros(B, len(AUG_FIELDS), dtype = torch.int64, device = dev) if B == 0 or T == 0 else torch.empty(B, len(AUG_FIELDS), dtype = torch.int64, device = dev)
+	xlen_out = xlen.clone() if B == 0 or T == 0 else torch.empty(B, dtype = torch.float32, device = dev)
+	arr = (ctypes.c_uint64 * max(len(steps), 1))(*[int(s) for s in steps])
+	call('convasr_augment_params', ptr(xlen), ptr(keys), ptr(min_out_len), B, T, int(seed) & 0xffffffffffffffff, int(epoch), arr, len(steps), int(speed_thr), int(gain_steps), int(gain_thr),
+	     rows, samples, int(snr_steps), int(noise_thr), ptr(params), ptr(xlen_out), stream_ptr())
+	return params, xlen_out
+
+
+def augment_waveform(x, params, table = None, gain_table = None, noise = None, snr_table = None):
+	"""convasr_augment_waveform + convasr_augment_mix: x (B, T) float32 or int16 (scaled by 1 / 32767) -> (out (B, T) float32 of the same padded
+	length, scales (B,) float32, the factor each utterance's noise was added with; 0 = none).  params: augment_params' tensor; table
+	(n_speeds, taps, phases + 1), gain_table, noise (N, L) and snr_table float32 device tensors (None: no speeds other than 1.0 / no gain / no
+	noise).  Two launches, a third with a noise bank; B == 0 or T == 0 launches nothing."""
+	x = _augment_batch('augment_waveform', x)
+	dev = x.device
+	B, T = x.shape
+	_same_device('augment_waveform', dev, params = params, table = table, gain_table = gain_table, noise = noise, snr_table = snr_table)
+	if params.shape != (B, len(AUG_FIELDS)) or params.dtype != torch.int64:
+		raise ValueError(f'augment_waveform: params must be ({B}, {len(AUG_FIELDS)}) int64, got {tuple(params.shape)} {params.dtype}')
+	for what, t, nd in (('table', table, 3), ('gain_table', gain_table, 1), ('noise', noise, 2), ('snr_table', snr_table, 1)):
+		if t is not None and (t.ndim != nd or t.dtype != torch.float32):
+			raise ValueError(f'augment_waveform: {what} must be a {nd}-d float32 tensor, got {tuple(t.shape)} {t.dtype}')
+	if table is not None and table.shape[2] != augment_phases() + 1:
+		raise ValueError(f'augment_waveform: a table of {augment_phases() + 1} columns expected, got {tuple(table.shape)}')
+	if noise is not None and snr_table is None:
+		raise ValueError('augment_waveform: a noise bank needs an SNR table')
+	params, table, gain_table, noise, snr_table = (None if t is None else t.contiguous() for t in (params, table, gain_table, noise, snr_table))
+	out = torch.empty(B, T, dtype = torch.float32, device = dev)
+	scales = torch.zeros(B, dtype = torch.float32, device = dev) if noise is None or B == 0 or T == 0 else torch.empty(B, dtype = torch.float32, device = dev)
+	ws = workspace(max(B, 1) * _cached_query('convasr_augment_parts') * 16, dev, 'augment')
+	rows, samples = (0, 0) if noise is None else noise.shape
+	call('convasr_augment_waveform', ptr(x), dtype_code(x.dtype), B, T, ptr(params), ptr(table), 0 if table is None else table.shape[0], 0 if table is None else table.shape[1], ptr(gain_table),
+	     0 if gain_table is None else gain_table.numel(), ptr(noise), rows, samples, ptr(out), ptr(ws), stream_ptr())
+	if noise is not None:
+		call('convasr_augment_mix', ptr(out), B, T, ptr(params), ptr(noise), rows, samples, ptr(snr_table), snr_table.numel(), ptr(ws), ptr(scales), stream_ptr())
+	return out, scales
+
+
+def spec_augment_tile():
+	"""Elements one workgroup of convasr_spec_augment takes per step (tests straddle it)."""
+	return _cached_query('convasr_spec_augment_tile')
+
+
+def spec_augment(x, xlen, keys, epoch, seed, freq_masks = 2, freq_width = 10, time_masks = 2, time_width = 50, time_fraction = 0.05, fill = 'mean', return_masks = False):
+	"""convasr_spec_augment: frequency and time masks on (B, F, T) float32 features, one launch.  xlen (B,) float32 fractions of T; keys (>= B,)
+	int64 and epoch (1,) int64 are DEVICE tensors the kernel reads, so a captured graph draws fresh masks from rewritten buffers.  fill: a number,
+	or 'mean' = each utterance's mean over all channels and valid frames.  Returns (out, fill (B,) float32) and, with return_masks, the
+	(B, freq_masks + time_masks, 2) int32 (start, width) pairs, frequency masks first."""
+	require_cuda(x, xlen, keys, epoch)
+	if x.ndim != 3 or x.dtype != torch.float32:
+		raise ValueError(f'spec_augment: (B, F, T) float32 features expected, got {tuple(x.shape)} {x.dtype}')
+	B, F, T = x.shape
+	dev = x.device
+	_same_device('spec_augment', dev, xlen = xlen, keys = keys, epoch = epoch)
+	if keys.ndim != 1 or keys.shape[0] < B or keys.dtype != torch.int64 or not keys.is_contiguous() or epoch.dtype != torch.int64 or epoch.numel() != 1:
+		raise ValueError(f'spec_augment: keys must be a contiguous int64 tensor of at least {B} entries and epoch one int64, got {tuple(keys.shape)} {keys.dtype} and {tuple(epoch.shape)} {epoch.dtype}')
+	x, xlen = x.contiguous(), xlen_f32(xlen, dev)
+	mean = fill == 'mean'
+	out = torch.empty_like(x)
+	fill_out = torch.zeros(B, dtype = torch.float32, device = dev) if B * F * T == 0 else torch.empty(B, dtype = torch.float32, device = dev)
+	masks = torch.zeros(B, int(freq_masks) + int(time_masks), 2, dtype = torch.int32, device = dev) if return_masks else None
+	call('convasr_spec_augment', ptr(x), ptr(xlen), ptr(keys), ptr(epoch), int(seed) & 0xffffffffffffffff, B, F, T, int(freq_masks), int(freq_width), int(time_masks), int(time_width),
+	     prob_threshold(time_fraction), int(mean), 0.0 if mean else float(fill), ptr(out), ptr(fill_out), ptr(masks), stream_ptr())
+	return (out, fill_out, masks) if return_masks else (out, fill_out)

@@ -1079,6 +1079,90 @@ int convasr_vad_segments_write(const uint8_t* mask, int C, int64_t n_frames, int
 int convasr_gather_segments(const void* signal, int dtype, int C, int64_t N, const int64_t* segments_host, const int64_t* segments, int B,
                             float* out, int64_t Tpad, void* stream);
 
+/* ---- Training-time augmentation of a collated batch: speed, gain, noise on the waveforms, SpecAugment on the features.  The reference has
+ * none (its frontend's dither is commented out); this augmentation is DEFINED BY THIS PROJECT and unpinned against torchaudio, NeMo or Kaldi
+ * (none of which is a dependency).  Integers (which augmentations fire, table indices, lengths, mask positions) are exact and restatable on
+ * the host; samples are fp32 sums in a fixed order. ------------------------------------------------------------------------------------ */
+
+/* The generator: Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85).  A random
+ * decision is word 0 of the block with
+ *   counter = (key & 0xffffffff, key >> 32, epoch, purpose << 16 | index),  Philox key = (seed & 0xffffffff, seed >> 32),
+ * key = the utterance's id (64 bits), epoch < 2^32, index = the number of the mask (0 elsewhere), purpose: 0 speed fires, 1 speed, 2 gain fires,
+ * 3 gain, 4 noise fires, 5 noise row, 6 noise offset, 7 SNR, 8 / 9 frequency-mask width / start, 10 / 11 time-mask width / start.  Nothing else
+ * enters: not the utterance's place in the batch, not the batch, not the rank, not the steps run before.  With r the word:
+ *   "fires with probability p": (r >> 8) < floor(p * 2^24), the threshold computed once by the caller;
+ *   a uniform integer in [0, n]: ((r >> 8) * (n + 1)) >> 24 in 64 bits (n < 2^40).
+ * No kernel of this section evaluates log, exp, sin or cos: gains, SNR factors and filters are tables the caller computed in float64 and
+ * rounded once.
+ * convasr_philox: the raw generator, for tests.  counters (n, 4) int64 holding 32-bit words, out (n, 4) int64 the four words of each block.
+ *
+ * convasr_augment_params -- one launch, one lane per utterance -- writes params (B, 8) int64 and xlen_out (B,) fp32:
+ *   len = ceil(xlen[b] * T) in fp32 (convasr_output_lengths' rule), clamped to [0, T];
+ *   speed: i = uniform in [0, n_speeds - 1], step = steps[i] = round(speed_i * 2^32), out_len = floor(len * 2^32 / step).  The utterance keeps
+ *     speed 1 (i = -1, step = 2^32, out_len = len) when the draw does not fire, when out_len > T, or when min_out_len is given and out_len <
+ *     min_out_len[b]: exact integer comparisons.
+ *   gain: index uniform in [0, gain_steps - 1] when gain_steps > 0 and the draw fires, else -1;
+ *   noise: row uniform in [0, noise_rows - 1], offset uniform in [0, noise_len - 1], SNR index uniform in [0, snr_steps - 1] when noise_rows > 0
+ *     and the draw fires, else row -1, offset 0, SNR index 0.
+ *   params[b] = (speed index, step, gain index, noise row, noise offset, SNR index, len, out_len);  xlen_out[b] = out_len / T, one fp32 divide.
+ *   steps: n_speeds 64-bit words ON THE HOST.
+ *
+ * convasr_augment_waveform -- one launch -- x (B, T) fp32 or int16 (each sample (float)v / 32767.f correctly rounded), out (B, T) fp32 of the
+ * SAME padded length.  With x[k] = 0 outside [0, len), P = convasr_augment_phases() = 128 and H = taps / 2 - 1, for n < out_len:
+ *   step == 2^32: y = x[n], bit for bit;
+ *   otherwise pos = n * step (64-bit), k0 = pos >> 32, frac = pos & 0xffffffff, p = frac >> 25, f = ((frac << 7) & 0xffffffff) >> 8 scaled by
+ *     2^-24 (exact in fp32), and y = sum over j = 0 .. taps - 1, in that order, of fma(x[k0 - H + j], c_j, .) with c_j = fma(f, t1 - t0, t0),
+ *     t0 = table[i][j][p], t1 = table[i][j][p + 1]: LINEAR INTERPOLATION between the two neighbouring of P tabulated phases;
+ *   then y = y * gain_table[gain index] when the index is >= 0.
+ *   out[b][n] = y for n < out_len and 0 for out_len <= n < T.
+ *   table: (n_speeds, taps, P + 1) fp32 on the device, table[i][j][p] = h_i((j - H) - p / P), h(d) = c * sinc(c * d) * w(d * c / Z) where
+ *     |d| * c <= Z and 0 elsewhere, c = rolloff * min(1, 1 / speed_i), sinc and the Kaiser window w as in convasr_resample, taps = 2 * floor(Z /
+ *     c_min) + 2 for the smallest c of the table.  taps == 0: no table, every utterance is copied (its step must be 2^32).
+ *   partials: (B, convasr_augment_parts(), 2) float64 workspace, uninitialised.  A workgroup owns the tiles part, part + nparts, ... of an
+ *     utterance (tiles of convasr_augment_tile() = 1024 outputs, nparts = min(tiles, parts)) and leaves (sum of y^2, sum of v^2) over its outputs
+ *     n < out_len, v = noise[row][(offset + n) mod noise_len] (0 without a row): float64 products and sums per lane, then a fixed tree.
+ * convasr_augment_mix -- one launch, only with a noise bank -- Ex, En = the partial pairs added in index order in float64;
+ *   scale = (float)(snr_table[SNR index] * sqrt(Ex / En)) in float64 when the utterance has a row and Ex > 0 and En > 0, else 0 (nothing is
+ *   added); out[b][n] = fma(scale, v_n, out[b][n]) for n < out_len; scales (B,) fp32 is an output.  Two runs are bit-equal.
+ * Three plain launches (two without noise), no memset, no copy, no host synchronisation, no atomics.  B == 0 or T == 0 launches nothing.
+ * Envelope, checked before any launch: B <= 65535, T < 2^31, 1 <= n_speeds <= 32, every step in [2^31, 2^33] (speeds in [0.5, 2]), gain_steps and
+ * snr_steps <= 4096, noise rows and samples < 2^31 each, the table of one speed and a tile's input span within 160 KiB of LDS (taps <= 298);
+ * outside it CONVASR_EUNSUPPORTED; any other bad argument (odd taps, a threshold above 2^24, epoch outside [0, 2^32), NULL) CONVASR_EINVAL.
+ * A params tensor of the caller's own making is read defensively: indices outside their tables mean "none". */
+int convasr_philox(const int64_t* counters, int64_t n, uint32_t key0, uint32_t key1, int64_t* out, void* stream);
+int convasr_augment_tile(void);
+int convasr_augment_phases(void);
+int convasr_augment_parts(void);
+int convasr_augment_params(const float* xlen, const int64_t* keys, const int64_t* min_out_len, int B, int64_t T, uint64_t seed, int64_t epoch,
+                           const uint64_t* steps, int n_speeds, uint32_t speed_thr, int gain_steps, uint32_t gain_thr, int64_t noise_rows,
+                           int64_t noise_len, int snr_steps, uint32_t noise_thr, int64_t* params, float* xlen_out, void* stream);
+int convasr_augment_waveform(const void* x, int x_dtype, int B, int64_t T, const int64_t* params, const float* table, int n_speeds, int taps,
+                             const float* gain_table, int gain_steps, const float* noise, int64_t noise_rows, int64_t noise_len, float* out,
+                             double* partials, void* stream);
+int convasr_augment_mix(float* out, int B, int64_t T, const int64_t* params, const float* noise, int64_t noise_rows, int64_t noise_len,
+                        const float* snr_table, int snr_steps, const double* partials, float* scales, void* stream);
+
+/* SpecAugment (Park et al. 2019, without time warping) on x (B, F, T) fp32 log-mel features, out of the same shape, x != out.
+ *   valid = ceil(xlen[b] * T) in fp32, clamped to [0, T];
+ *   frequency mask i < freq_masks: w = uniform in [0, min(freq_width, F)], start = uniform in [0, F - w];
+ *   time mask i < time_masks: w = uniform in [0, min(time_width, (valid * time_fraction_q24) >> 24)] -- floor(time_fraction * valid) with the
+ *     fraction in 24-bit fixed point, time_fraction_q24 = floor(time_fraction * 2^24) by the caller -- start = uniform in [0, valid - w];
+ *   out[b][f][t] = fill where t < valid and (f lies in a frequency mask or t in a time mask); every other value, the frames past valid
+ *     included, is copied bit for bit.  No mask leaves the valid region.
+ *   fill: fill_mean == 0: fill_value; otherwise the mean of x[b] over all channels and the valid frames (0 when there is none): float64 sums
+ *     per lane over the elements lane, lane + 1024, ... of the valid region in (channel, frame) order, a fixed tree, one divide, one rounding
+ *     to fp32.  fill_out (B,) fp32 receives the fill used; masks_out (optional) (B, freq_masks + time_masks, 2) int32 the (start, width) pairs.
+ *   keys (>= B int64) and epoch (one int64) are DEVICE buffers read by the kernel: a captured graph that holds the launch draws fresh masks
+ *   on every replay when the caller rewrote them beforehand in stream order.
+ * One launch -- 1 to 8 workgroups per utterance, each forming the same mean in the same order and writing its share in steps of
+ * convasr_spec_augment_tile() = 1024 elements -- no workspace, no memset or copy: one kernel node.  B, F or T == 0 launches nothing.
+ * Envelope: B <= 65535, F * T < 2^31, at most 16 masks of each kind; outside it CONVASR_EUNSUPPORTED; negative widths, a fraction above 2^24,
+ * x == out or NULL: CONVASR_EINVAL. */
+int convasr_spec_augment_tile(void);
+int convasr_spec_augment(const float* x, const float* xlen, const int64_t* keys, const int64_t* epoch, uint64_t seed, int B, int F, int T,
+                         int freq_masks, int freq_width, int time_masks, int time_width, uint32_t time_fraction_q24, int fill_mean,
+                         float fill_value, float* out, float* fill_out, int32_t* masks_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
