@@ -37,6 +37,7 @@ _SIGNATURES = dict(
 	convasr_fold2_unfold_wgrad = (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_conv1d_fwd = (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_f32, c_f32, c_p, c_p, c_p]),
 	convasr_conv_stats_max_rows = (c_int, [c_int, c_int]),
+	convasr_conv1d_fwd_route = (c_int, [c_int] * 15 + [ctypes.POINTER(c_int)]),
 	convasr_grouped_conv1d_fwd = (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_grouped_conv1d_dgrad = (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_grouped_conv1d_wgrad_workspace_bytes = (c_i64, [c_int, c_int, c_int, c_int, c_int]),
@@ -207,7 +208,7 @@ def load():
 		for name, (res, args) in _SIGNATURES.items():
 			fn = getattr(lib, name)
 			fn.restype, fn.argtypes = res, args
-		if lib.convasr_abi_version() != 10:
+		if lib.convasr_abi_version() != 11:
 			raise ConvasrHipError('ABI version mismatch')
 		_lib = lib
 	return _lib

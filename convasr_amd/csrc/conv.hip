@@ -411,21 +411,43 @@ template <typename T, typename O, int XI, bool AL, bool SK = false> static int l
 	return 0;
 }
 
-template <typename T, typename O, bool SK = false> static int dispatch_conv(const ConvParams& p, size_t smem, hipStream_t s) {
+// The plan half of the register-staged dispatch: the XI instantiation and ALIGNED_X for a row of `esize`-byte elements, or the refusal.
+static int plan_conv(const ConvParams& p, size_t esize, ConvPlan& pl) {
 	const int xi = (p.x_rows * 8 + NTHREADS - 1) / NTHREADS;
-	const bool al = ((p.Cin * sizeof(T)) & 15) == 0;
+	const bool al = ((p.Cin * esize) & 15) == 0;
+	pl.aligned = al;
+	pl.tile_rows = BM;
+	pl.rows = p.B * p.m_tiles_per_b;
 	if (!al) {
-		if (xi <= 9) return launch_conv<T, O, 9, false, SK>(p, smem, s);
+		if (xi <= 9) { pl.xi = 9; return 0; }
 		return convasr_fail(CONVASR_EUNSUPPORTED, "conv1d: halo too large (x_rows %d)", p.x_rows);
 	}
-	if (xi <= 5) return launch_conv<T, O, 5, true, SK>(p, smem, s);
-	if (xi <= 9) return launch_conv<T, O, 9, true, SK>(p, smem, s);
-	if (xi <= 16) return launch_conv<T, O, 16, true, SK>(p, smem, s);
+	if (xi <= 5) { pl.xi = 5; return 0; }
+	if (xi <= 9) { pl.xi = 9; return 0; }
+	if (xi <= 16) { pl.xi = 16; return 0; }
 	return convasr_fail(CONVASR_EUNSUPPORTED, "conv1d: halo too large (x_rows %d)", p.x_rows);
 }
 
-int convasr_conv1d_v2_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s, int* m_tiles_out);  // conv_v2s.hip
-int convasr_conv1x1_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s, int* rows_out);        // conv1x1.hip
+// The launch half, of a plan plan_conv accepted.
+template <typename T, typename O, bool SK = false> static int launch_planned_conv(const ConvParams& p, const ConvPlan& pl, hipStream_t s) {
+	if (!pl.aligned) return launch_conv<T, O, 9, false, SK>(p, pl.smem, s);
+	if (pl.xi == 5) return launch_conv<T, O, 5, true, SK>(p, pl.smem, s);
+	if (pl.xi == 9) return launch_conv<T, O, 9, true, SK>(p, pl.smem, s);
+	return launch_conv<T, O, 16, true, SK>(p, pl.smem, s);
+}
+
+template <typename T, typename O, bool SK = false> static int dispatch_conv(const ConvParams& p, size_t smem, hipStream_t s) {
+	ConvPlan pl = {};
+	pl.smem = smem;
+	const int rc = plan_conv(p, sizeof(T), pl);
+	return rc ? rc : launch_planned_conv<T, O, SK>(p, pl, s);
+}
+
+int convasr_conv1d_v2_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s, int* m_tiles_out);  // conv_v2s.hip: plan + launch
+int convasr_conv1d_v2_plan(ConvParams& p, int x_dtype, int y_dtype, ConvPlan& pl);
+int convasr_conv1d_v2_launch(ConvParams& p, const ConvPlan& pl, int x_dtype, hipStream_t s);
+int convasr_conv1x1_plan(ConvParams& p, int x_dtype, int y_dtype, ConvPlan& pl);                       // conv1x1.hip
+int convasr_conv1x1_launch(ConvParams& p, const ConvPlan& pl, int x_dtype, hipStream_t s);
 int convasr_wgrad_v2_try(WgradParams& p, int dtype, hipStream_t s);      // wgrad_v2.hip
 int convasr_wgrad_v2_supports(const WgradParams& p);
 int convasr_wgrad_v2_query(WgradParams& p);
@@ -435,11 +457,17 @@ static int g_conv_debug = 0;
 int convasr_conv_debug_bits() { return g_conv_debug; }  // (for the other translation units' host entries)
 extern "C" int convasr_debug_set_conv_v2(int enable) { const int prev = g_conv_use_v2; g_conv_use_v2 = enable & 1; g_conv_debug = enable >> 8; return prev; }
 
-static int conv1d_run(const void* x, const void* wp, void* y, int x_dtype, int y_dtype, int B, int Cin, int Cout, int Tin, int Tout, int K,
-                      int stride, int dil, int pad, const float* bias, double* stats, const float* scale, const float* shift, int act,
-                      float act_lo, float act_hi, const float* xlen, const ConvParams* bn_fusion, int* rows_out, void* stream) {
-	CONVASR_CHECK_ARG(x && wp && y && B > 0 && Cin > 0 && Cout > 0 && Tin > 0 && Tout > 0 && K > 0 && stride > 0 && dil > 0, "conv1d_fwd: bad arguments");
-	CONVASR_CHECK_ARG((scale == nullptr) == (shift == nullptr), "conv1d_fwd: scale and shift go together");
+enum { CONV_ROUTE_NONE = 0, CONV_ROUTE_GENERAL = 1, CONV_ROUTE_LDS_DMA = 2, CONV_ROUTE_ONE_TAP = 3 };  // convasr_conv1d_fwd_route's answer
+
+// Everything conv1d_run decides, with no launch: `p` comes in with the caller's pointers (only whether scale, xlen and the bn_* fields
+// are NULL is looked at) and leaves as the chosen kernel is given it; *kernel = one of CONV_ROUTE_* (NONE with a return of 0: a fused
+// BN-backward launch outside the LDS-DMA kernel's envelope, the caller runs the two steps apart).  deny: bit 0 = not the one-tap
+// kernel, bit 1 = not the LDS-DMA kernel (the runtime refused that launch).  Returns 0 or the error code of the refusal.
+static int conv1d_route(ConvParams& p, int x_dtype, int y_dtype, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil, int pad,
+                        int act, float act_lo, float act_hi, int deny, int* kernel, ConvPlan& pl) {
+	*kernel = CONV_ROUTE_NONE;
+	CONVASR_CHECK_ARG(B > 0 && Cin > 0 && Cout > 0 && Tin > 0 && Tout > 0 && K > 0 && stride > 0 && dil > 0, "conv1d_fwd: bad arguments");
+	CONVASR_CHECK_ARG((p.scale == nullptr) == (p.shift == nullptr), "conv1d_fwd: scale and shift go together");
 	const int64_t expect = ((int64_t)Tin + 2 * (int64_t)pad - (int64_t)dil * (K - 1) - 1) / stride + 1;
 	// a caller may ask for the first Tout < expect frames only (the stride-2 fold below needs one frame less than its even folded kernel yields)
 	CONVASR_CHECK_ARG(Tout <= expect, "conv1d_fwd: Tout %d inconsistent with Tin %d K %d stride %d dil %d pad %d (at most %lld)", Tout, Tin, K, stride, dil, pad, (long long)expect);
@@ -447,14 +475,11 @@ static int conv1d_run(const void* x, const void* wp, void* y, int x_dtype, int y
 	// A one-tap, stride-1, unpadded conv has no temporal coupling: without per-utterance length masks the batch is ONE sequence of
 	// B * T frames, and the tiles need not stop at utterance ends (32 utterances of 626 frames: 79 tiles of 256 rows instead of 96).
 	// Same k order per element; the BN partial rows are grouped by the new tiles.  (debug bit 512: off, A/B runs)
-	if (K == 1 && stride == 1 && pad == 0 && Tin == Tout && B > 1 && !xlen && !(bn_fusion && bn_fusion->bn_xlen) && !(g_conv_debug & 512) &&
+	if (K == 1 && stride == 1 && pad == 0 && Tin == Tout && B > 1 && !p.xlen && !p.bn_xlen && !(g_conv_debug & 512) &&
 	    (int64_t)B * Tin * (Cin > Cout ? Cin : Cout) * 4 < (1ll << 31)) {
 		Tin = Tout = B * Tin;
 		B = 1;
 	}
-	ConvParams p = {};
-	if (bn_fusion) p = *bn_fusion;  // only the bn_* fields are set in it
-	p.x = x; p.w = wp; p.y = y; p.bias = bias; p.stats = stats; p.scale = scale; p.shift = shift; p.xlen = xlen;
 	p.B = B; p.Cin = Cin; p.Cout = Cout; p.CoutPad = convasr_conv_cout_pad(Cout); p.Tin = Tin; p.Tout = Tout; p.K = K; p.stride = stride; p.dil = dil; p.pad = pad;
 	p.act = act; p.act_lo = act_lo; p.act_hi = act_hi; p.debug = g_conv_debug;
 	p.m_tiles_per_b = (Tout + BM - 1) / BM;
@@ -467,30 +492,81 @@ static int conv1d_run(const void* x, const void* wp, void* y, int x_dtype, int y
 	const size_t epi = (size_t)BM * (BN * osz + 16) + 4 * BN * sizeof(float);
 	if (epi > smem) smem = epi;
 	CONVASR_CHECK_ARG(smem <= 160 * 1024, "conv1d_fwd: tile needs %zu B of LDS", smem);
-	hipStream_t s = (hipStream_t)stream;
-	int v2_rows = 0;
-	if (convasr_is_half(x_dtype) && g_conv_use_v2 && convasr_conv1x1_try(p, x_dtype, y_dtype, s, &v2_rows)) {  // one-tap training launches with short reductions
-		CONVASR_CHECK_LAUNCH("conv1d_fwd (1x1)");
-		if (rows_out) *rows_out = v2_rows;
-		return 0;
+	if (convasr_is_half(x_dtype) && g_conv_use_v2) {
+		ConvParams q = p;
+		if (!(deny & 1) && convasr_conv1x1_plan(q, x_dtype, y_dtype, pl)) { p = q; *kernel = CONV_ROUTE_ONE_TAP; return 0; }  // one-tap training launches with short reductions
+		q = p;
+		if (!(deny & 2) && convasr_conv1d_v2_plan(q, x_dtype, y_dtype, pl)) { p = q; *kernel = CONV_ROUTE_LDS_DMA; return 0; }
 	}
-	if (convasr_is_half(x_dtype) && g_conv_use_v2 && convasr_conv1d_v2_try(p, x_dtype, y_dtype, s, &v2_rows)) {
-		CONVASR_CHECK_LAUNCH("conv1d_fwd (v2)");
-		if (rows_out) *rows_out = v2_rows;
-		return 0;
-	}
-	if (p.bn_y) return 1;  // the fused epilogue lives in the LDS-DMA kernel only: nothing was launched, the caller runs the two steps apart
-	int rc;
-	if (x_dtype == CONVASR_F32 && y_dtype == CONVASR_F32) rc = dispatch_conv<float, float>(p, smem, s);
-	else if (x_dtype == CONVASR_BF16 && y_dtype == CONVASR_BF16) rc = dispatch_conv<bf16_t, bf16_t>(p, smem, s);
-	else if (x_dtype == CONVASR_BF16 && y_dtype == CONVASR_F32) rc = dispatch_conv<bf16_t, float>(p, smem, s);
-	else if (x_dtype == CONVASR_F16 && y_dtype == CONVASR_F16) rc = dispatch_conv<f16_t, f16_t>(p, smem, s);
-	else if (x_dtype == CONVASR_F16 && y_dtype == CONVASR_F32) rc = dispatch_conv<f16_t, float>(p, smem, s);
-	else return convasr_fail(CONVASR_EUNSUPPORTED, "conv1d_fwd: dtype %d -> %d", x_dtype, y_dtype);
+	if (p.bn_y) return 0;  // the fused epilogue lives in the LDS-DMA kernel only
+	const bool pair = (x_dtype == CONVASR_F32 && y_dtype == CONVASR_F32) || (convasr_is_half(x_dtype) && (y_dtype == x_dtype || y_dtype == CONVASR_F32));
+	if (!pair) return convasr_fail(CONVASR_EUNSUPPORTED, "conv1d_fwd: dtype %d -> %d", x_dtype, y_dtype);
+	pl.smem = smem;
+	const int rc = plan_conv(p, x_dtype == CONVASR_F32 ? 4 : 2, pl);
 	if (rc) return rc;
-	CONVASR_CHECK_LAUNCH("conv1d_fwd");
-	if (rows_out) *rows_out = B * p.m_tiles_per_b;
+	*kernel = CONV_ROUTE_GENERAL;
 	return 0;
+}
+
+static int conv1d_run(const void* x, const void* wp, void* y, int x_dtype, int y_dtype, int B, int Cin, int Cout, int Tin, int Tout, int K,
+                      int stride, int dil, int pad, const float* bias, double* stats, const float* scale, const float* shift, int act,
+                      float act_lo, float act_hi, const float* xlen, const ConvParams* bn_fusion, int* rows_out, void* stream) {
+	CONVASR_CHECK_ARG(x && wp && y, "conv1d_fwd: bad arguments");
+	hipStream_t s = (hipStream_t)stream;
+	for (int deny = 0;;) {
+		ConvParams p = {};
+		if (bn_fusion) p = *bn_fusion;  // only the bn_* fields are set in it
+		p.x = x; p.w = wp; p.y = y; p.bias = bias; p.stats = stats; p.scale = scale; p.shift = shift; p.xlen = xlen;
+		ConvPlan pl = {};
+		int kernel = CONV_ROUTE_NONE;
+		int rc = conv1d_route(p, x_dtype, y_dtype, B, Cin, Cout, Tin, Tout, K, stride, dil, pad, act, act_lo, act_hi, deny, &kernel, pl);
+		if (rc) return rc;
+		if (kernel == CONV_ROUTE_NONE) return 1;  // nothing was launched, the caller runs the two steps apart
+		if (kernel == CONV_ROUTE_ONE_TAP) {
+			if (!convasr_conv1x1_launch(p, pl, x_dtype, s)) { deny |= 1; continue; }
+			CONVASR_CHECK_LAUNCH("conv1d_fwd (1x1)");
+		} else if (kernel == CONV_ROUTE_LDS_DMA) {
+			if (!convasr_conv1d_v2_launch(p, pl, x_dtype, s)) { deny |= 3; continue; }
+			CONVASR_CHECK_LAUNCH("conv1d_fwd (v2)");
+		} else {
+			if (x_dtype == CONVASR_F32) rc = launch_planned_conv<float, float>(p, pl, s);
+			else if (x_dtype == CONVASR_BF16 && y_dtype == CONVASR_BF16) rc = launch_planned_conv<bf16_t, bf16_t>(p, pl, s);
+			else if (x_dtype == CONVASR_BF16) rc = launch_planned_conv<bf16_t, float>(p, pl, s);
+			else if (y_dtype == CONVASR_F16) rc = launch_planned_conv<f16_t, f16_t>(p, pl, s);
+			else rc = launch_planned_conv<f16_t, float>(p, pl, s);
+			if (rc) return rc;
+			CONVASR_CHECK_LAUNCH("conv1d_fwd");
+		}
+		if (rows_out) *rows_out = pl.rows;
+		return 0;
+	}
+}
+
+// Which kernel convasr_conv1d_fwd would launch for this geometry under the current convasr_debug_set_conv_v2 state, and what it would be
+// given.  Asks conv1d_run's own decision code; launches nothing, touches no GPU memory.
+extern "C" int convasr_conv1d_fwd_route(int x_dtype, int y_dtype, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil, int pad,
+                                        int has_scale_shift, int act, int has_xlen, int has_stats, int* out) {
+	static const float present = 0.f;  // (never read: the plan looks only at which optional operands are there)
+	static double present64 = 0.;
+	ConvParams p = {};
+	if (has_scale_shift) p.scale = p.shift = &present;
+	if (has_xlen) p.xlen = &present;
+	if (has_stats) p.stats = &present64;
+	ConvPlan pl = {};
+	int kernel = CONV_ROUTE_NONE;
+	const int rc = conv1d_route(p, x_dtype, y_dtype, B, Cin, Cout, Tin, Tout, K, stride, dil, pad, act, 0.f, 0.f, 0, &kernel, pl);
+	if (out) {
+		for (int i = 0; i < CONVASR_CONV_ROUTE_INTS; ++i) out[i] = 0;
+		out[0] = rc;
+		if (!rc) {
+			const bool v2 = kernel == CONV_ROUTE_LDS_DMA, gen = kernel == CONV_ROUTE_GENERAL, one = kernel == CONV_ROUTE_ONE_TAP;
+			out[1] = p.B; out[2] = p.Tout; out[3] = pl.tile_rows; out[4] = one ? pl.rows : p.m_tiles_per_b; out[5] = p.n_tiles; out[6] = p.total_tiles;
+			out[7] = v2 ? p.full_tiles : p.total_tiles; out[8] = v2 ? p.narrow_parts : 0; out[9] = v2 ? p.tail128 : 0;
+			out[10] = one ? 0 : p.x_rows; out[11] = gen ? pl.xi : 0; out[12] = gen ? pl.aligned : 0; out[13] = one ? (pl.one_stage ? 1 : 2) : 0;
+			out[14] = (int)pl.smem; out[15] = has_stats ? pl.rows : 0;
+		}
+	}
+	return rc ? CONV_ROUTE_NONE : kernel;
 }
 
 extern "C" int convasr_conv1d_fwd(const void* x, const void* wp, void* y, int x_dtype, int y_dtype, int B, int Cin, int Cout, int Tin, int Tout, int K,
@@ -581,7 +657,10 @@ extern "C" int convasr_conv1d_fwd_splitk(const void* x, const void* wp, void* y,
 	p.cib_per_split = cps; p.split_stride = (long long)B * Tout * Cout;
 	hipStream_t s = (hipStream_t)stream;
 	if (half) {
-		if (!convasr_conv1d_v2_try(p, x_dtype, CONVASR_F32, s, nullptr)) return convasr_fail(CONVASR_EUNSUPPORTED, "conv1d_fwd_splitk: the geometry is outside the LDS-DMA kernel's envelope");
+		// outside the LDS-DMA kernel's envelope at 256-row tiles ((K - 1) dil > 64: the plan never sees the halo): the unsplit launch serves the
+		// request, through 128-row tiles or the register-staged kernel, with the caller's epilogue
+		if (!convasr_conv1d_v2_try(p, x_dtype, CONVASR_F32, s, nullptr))
+			return conv1d_run(x, wp, y, x_dtype, y_dtype, B, Cin, Cout, Tin, Tout, K, 1, dil, pad, bias, nullptr, scale, shift, act, act_lo, act_hi, xlen, nullptr, nullptr, stream);
 	} else {  // the exact-fp32 kernel (two-level sums: fp64 totals per workgroup, rounded once into its fp32 partial tile)
 		p.m_tiles_per_b = (Tout + BM - 1) / BM;
 		p.total_tiles = B * p.m_tiles_per_b * p.n_tiles;

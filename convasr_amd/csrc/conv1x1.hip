@@ -186,8 +186,9 @@ template <typename I, int NS> __global__ __launch_bounds__(C11_THREADS, NS == 1 
 	conv1x1_tile<I, NS>(g.prob[q], local / nt, local % nt, smem);
 }
 
-// Returns 1 if this kernel took the launch (rows_out = partial statistics rows written), 0 if the shape is outside its envelope.
-int convasr_conv1x1_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s, int* rows_out) {
+// The plan half: 1 if this kernel takes the launch (p.n_tiles / p.total_tiles and `pl` filled), 0 if the shape is outside its envelope.
+// Launches nothing (convasr_conv1d_fwd_route asks it too).
+int convasr_conv1x1_plan(ConvParams& p, int x_dtype, int y_dtype, ConvPlan& pl) {
 	if (p.K != 1 || p.stride != 1 || p.pad != 0 || p.Tin != p.Tout || (p.Cin & 63) != 0 || (p.Cout & 127) != 0 || p.CoutPad != p.Cout) return 0;
 	if (!convasr_is_half(x_dtype) || y_dtype != x_dtype || p.scale || p.act != CONVASR_ACT_NONE || p.xlen || p.bn_y) return 0;
 	// Measured against conv_v2s.hip on every one-tap shape of the two bench workloads (profiles/r04_ab_conv1x1.json, scratch/ab_conv1x1.py:
@@ -205,14 +206,22 @@ int convasr_conv1x1_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s, i
 	// (640 -> 768 at 32 x 376: 27.3 -> 20.9 us; 896 -> 1024 at 64 x 753: 114.6 -> 97.5 us).  debug bit 16384 inverts the choice (A/B runs).
 	const bool one_stage = (p.Cin < 3 * p.Cout) != ((p.debug & 16384) != 0);
 	const size_t epi = (size_t)C11_BM * (BN * 2 + 16) + 4 * BN * sizeof(float);  // the epilogue's output tile + sums: 36.9 KB
-	const size_t smem = one_stage ? (epi > C11_STAGE ? epi : C11_STAGE) : 2 * (size_t)C11_STAGE;
+	pl.smem = one_stage ? (epi > C11_STAGE ? epi : C11_STAGE) : 2 * (size_t)C11_STAGE;
+	pl.one_stage = one_stage;
+	pl.tile_rows = C11_BM;
+	pl.rows = m_tiles;
+	return 1;
+}
+
+// The launch half, of a plan convasr_conv1x1_plan accepted: 1 if the launch went out, 0 if the runtime refused it.
+int convasr_conv1x1_launch(ConvParams& p, const ConvPlan& pl, int x_dtype, hipStream_t s) {
+	const bool one_stage = pl.one_stage != 0;
 	const bool f16 = x_dtype == CONVASR_F16;
 	const void* kern = one_stage ? (f16 ? (const void*)conv1x1_kernel<f16_t, 1> : (const void*)conv1x1_kernel<bf16_t, 1>) : (f16 ? (const void*)conv1x1_kernel<f16_t, 2> : (const void*)conv1x1_kernel<bf16_t, 2>);
 	static unsigned long long set[2][2] = {};
 	convasr_allow_160k_lds(kern, set[one_stage][f16]);
 	void* args[] = {&p};
-	if (hipLaunchKernel(kern, dim3(p.total_tiles), dim3(C11_THREADS), args, smem, s) != hipSuccess) { (void)hipGetLastError(); return 0; }
-	if (rows_out) *rows_out = m_tiles;
+	if (hipLaunchKernel(kern, dim3(p.total_tiles), dim3(C11_THREADS), args, pl.smem, s) != hipSuccess) { (void)hipGetLastError(); return 0; }
 	return 1;
 }
 

@@ -42,6 +42,17 @@ struct ConvParams {
 	long long split_stride;
 };
 
+// What a dispatcher decided for one launch, apart from the ConvParams fields it filled: the plan half of each *_try (no launch, no GPU
+// memory touched), shared by the launch and by convasr_conv1d_fwd_route.
+struct ConvPlan {
+	size_t smem;     // dynamic LDS bytes of the launch
+	int tile_rows;   // rows of an m tile (LDS-DMA: 256 or 128; register-staged and one-tap: 128)
+	int rows;        // per-m-tile partial statistics rows the launch writes
+	int ki;          // LDS-DMA: the kernel's epilogue instantiation (v2s_kernel)
+	int one_stage;   // one-tap: one LDS stage (1) or two (0)
+	int xi, aligned; // register-staged: the XI instantiation and ALIGNED_X
+};
+
 // Two 128-B rows share one 256-B bank row; 16-B slot = (row parity, chunk ^ row-pair index): 16 consecutive rows at the same
 // chunk land on 16 distinct slots -> ds_read_b128 fragments are bank-conflict free.
 __device__ __forceinline__ int lds_off(int row, int chunk) { return ((row >> 1) << 8) | ((((row & 1) << 3) | (chunk ^ ((row >> 1) & 7))) << 4); }

@@ -646,9 +646,10 @@ template <typename I, int BM_> static const void* v2s_kernel(int ki) {
 	return (const void*)conv1d_igemm_v2s_kernel<I, float, 0, BM_>;
 }
 
-// Returns 1 if the LDS-DMA kernel took the launch, 0 if the shape is outside its envelope (the caller falls back to conv.hip's
-// register-staged kernel).  x_dtype: CONVASR_BF16 or CONVASR_F16; y_dtype: the same, or CONVASR_F32 (the decoder head).
-int convasr_conv1d_v2_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s, int* m_tiles_out) {
+// The plan half: 1 if the LDS-DMA kernel takes the launch (the tile fields of `p` and `pl` filled), 0 if the shape is outside its envelope
+// (the caller falls back to conv.hip's register-staged kernel).  x_dtype: CONVASR_BF16 or CONVASR_F16; y_dtype: the same, or CONVASR_F32
+// (the decoder head).  Launches nothing (convasr_conv1d_fwd_route asks it too).
+int convasr_conv1d_v2_plan(ConvParams& p, int x_dtype, int y_dtype, ConvPlan& pl) {
 	if (p.stride != 1 || (p.Cin & 63) != 0 || !convasr_is_half(x_dtype) || (y_dtype != x_dtype && y_dtype != CONVASR_F32)) return 0;
 	const int n_cu = convasr_cu_count();  // (per device ordinal: common.h)
 	// Tile height: 256 rows.  A 192-row build of the same kernel (BM_ = 192: 256 x n tiles for 64 x 751 frames = whole rounds on 256
@@ -689,17 +690,13 @@ int convasr_conv1d_v2_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s,
 	p.total_tiles = p.B * p.m_tiles_per_b * p.n_tiles;
 	const int tail_rows = p.Tout - (p.m_tiles_per_b - 1) * bm;
 	p.tail128 = all_short ? 2 : ((bm == V2_BM && tail_rows <= 128 && !(p.debug & 128)) ? 1 : 0);  // (debug bit 128: short tails off, A/B runs)
-	const bool f16 = x_dtype == CONVASR_F16, wide = y_dtype == CONVASR_F32, fused = p.bn_y != nullptr;
+	const bool wide = y_dtype == CONVASR_F32, fused = p.bn_y != nullptr;
 	if (fused && wide) return 0;  // the fused BN-backward epilogue reads dz back in the storage type
 	if (p.cib_per_split && !wide) return 0;  // (split-K partial tiles are fp32)
-	const int ki = p.cib_per_split ? 4 : (wide ? 2 : (fused ? (mfma_sums ? 3 : 1) : 0)), bi = bm == 192 ? 1 : 0;  // (bm == 128 runs the 256-row kernel's 128-row instantiation)
-#ifdef CONVASR_AB_TILE192
-	const void* kern = f16 ? (bi ? v2s_kernel<f16_t, 192>(ki) : v2s_kernel<f16_t, V2_BM>(ki)) : (bi ? v2s_kernel<bf16_t, 192>(ki) : v2s_kernel<bf16_t, V2_BM>(ki));
-#else
-	const void* kern = f16 ? v2s_kernel<f16_t, V2_BM>(ki) : v2s_kernel<bf16_t, V2_BM>(ki);
-#endif
-	static unsigned long long attr_set[2][2][5] = {};
-	convasr_allow_160k_lds(kern, attr_set[f16][bi][ki]);
+	pl.ki = p.cib_per_split ? 4 : (wide ? 2 : (fused ? (mfma_sums ? 3 : 1) : 0));
+	pl.smem = smem;
+	pl.tile_rows = bm;
+	pl.rows = p.B * p.m_tiles_per_b;
 	// a last partial round that would occupy at most half of the CUs is cut into half-width tiles (debug bit 32: off); into quarter-width
 	// tiles when it follows at least one whole round and would occupy at most a quarter of the CUs (debug bit 16: halves there too)
 	p.full_tiles = p.total_tiles;
@@ -711,10 +708,32 @@ int convasr_conv1d_v2_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s,
 			if (p.full_tiles > 0 && 4 * rest <= n_cu && !(p.debug & 16)) p.narrow_parts = 4;
 		}
 	}
+	return 1;
+}
+
+// The launch half, of a plan convasr_conv1d_v2_plan accepted: 1 if the launch went out, 0 if the runtime refused it.
+int convasr_conv1d_v2_launch(ConvParams& p, const ConvPlan& pl, int x_dtype, hipStream_t s) {
+	const bool f16 = x_dtype == CONVASR_F16;
+	const int ki = pl.ki, bi = pl.tile_rows == 192 ? 1 : 0;  // (128-row tiles run the 256-row kernel's 128-row instantiation)
+	const size_t smem = pl.smem;
+#ifdef CONVASR_AB_TILE192
+	const void* kern = f16 ? (bi ? v2s_kernel<f16_t, 192>(ki) : v2s_kernel<f16_t, V2_BM>(ki)) : (bi ? v2s_kernel<bf16_t, 192>(ki) : v2s_kernel<bf16_t, V2_BM>(ki));
+#else
+	const void* kern = f16 ? v2s_kernel<f16_t, V2_BM>(ki) : v2s_kernel<bf16_t, V2_BM>(ki);
+#endif
+	static unsigned long long attr_set[2][2][5] = {};
+	convasr_allow_160k_lds(kern, attr_set[f16][bi][ki]);
 	const int grid = p.full_tiles + p.narrow_parts * (p.total_tiles - p.full_tiles);
 	const int splits = p.cib_per_split ? ((p.Cin >> 6) + p.cib_per_split - 1) / p.cib_per_split : 1;
 	void* args[] = {&p};
 	if (hipLaunchKernel(kern, dim3(grid, splits), dim3(V2S_THREADS), args, smem, s) != hipSuccess) { (void)hipGetLastError(); return 0; }  // (the caller's fallback starts from a clean error state)
-	if (m_tiles_out) *m_tiles_out = p.B * p.m_tiles_per_b;
+	return 1;
+}
+
+// plan + launch (convasr_conv1d_fwd_splitk's 16-bit launches)
+int convasr_conv1d_v2_try(ConvParams p, int x_dtype, int y_dtype, hipStream_t s, int* m_tiles_out) {
+	ConvPlan pl = {};
+	if (!convasr_conv1d_v2_plan(p, x_dtype, y_dtype, pl) || !convasr_conv1d_v2_launch(p, pl, x_dtype, s)) return 0;
+	if (m_tiles_out) *m_tiles_out = pl.rows;
 	return 1;
 }

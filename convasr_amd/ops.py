@@ -280,6 +280,22 @@ class ConvStats:
 		return out
 
 
+CONV_ROUTES = ('refused', 'general', 'lds_dma', 'one_tap')  # convasr_conv1d_fwd_route's answer
+CONV_ROUTE_FIELDS = ('error', 'B', 'T', 'tile_rows', 'm_tiles_per_b', 'n_tiles', 'total_tiles', 'full_tiles', 'narrow_parts', 'tail128', 'x_rows', 'xi', 'aligned_x', 'stages', 'lds_bytes', 'stats_rows')
+
+
+def conv_route(x_dtype, y_dtype, B, Cin, Cout, Tin, Tout, K, stride = 1, dil = 1, pad = 0, scale = False, act = _lib.ACT_NONE, xlen = False, stats = False):
+	"""Which kernel conv1d (convasr_conv1d_fwd) would launch for this geometry and these optional operands under the current
+	convasr_debug_set_conv_v2 state, and what the kernel would be given: dict(route = one of CONV_ROUTES, **CONV_ROUTE_FIELDS); a refused
+	geometry has the route and the error code alone.  The launch's own decision code; no launch, no GPU, not cached (it follows the debug switch)."""
+	out = (ctypes.c_int * 16)()
+	route = _lib.load().convasr_conv1d_fwd_route(dtype_code(x_dtype), dtype_code(y_dtype), B, Cin, Cout, Tin, Tout, K, stride, dil, pad, int(bool(scale)), act, int(bool(xlen)), int(bool(stats)), out)
+	plan = dict(route = CONV_ROUTES[route], error = out[0])
+	if route:
+		plan.update(zip(CONV_ROUTE_FIELDS, out))
+	return plan
+
+
 SPLITK = os.environ.get('CONVASR_NO_SPLITK') != '1'  # A/B hook: small-batch inference launches cut over the input channels
 
 
@@ -300,6 +316,13 @@ def _conv_timer_label(v2s, flops, nbytes, same_width, one_tap = False, suffix = 
 	if memory_bound(flops, nbytes):
 		return 'hbm:conv1d_igemm_v2s_kernel (memory-bound launches: the 38-class decoder)', symbol
 	return 'conv1d_igemm_v2s_kernel<bf16>' + suffix, symbol
+
+
+def _conv_label_route(x_dtype, out_dtype, B, Cin, Cout, Tin, Tout, K, stride, dil, pad, scale, act, xlen, stats):
+	"""(the LDS-DMA family takes the launch -- conv1x1.hip's kernel is booked as one of it --, the one-tap kernel takes it) for conv1d's timer
+	label: the dispatcher's own answer (convasr_conv1d_fwd_route), not a copy of its conditions.  A split-K launch is booked like the unsplit one."""
+	route = conv_route(x_dtype, out_dtype, B, Cin, Cout, Tin, Tout, K, stride, dil, pad, scale, act[0], xlen, stats)['route']
+	return route in ('lds_dma', 'one_tap'), route == 'one_tap'
 
 
 def conv1d(x, wp, Cout, K, stride = 1, dil = 1, pad = 0, out_dtype = None, bias = None, stats = None, scale = None, shift = None, act = (_lib.ACT_NONE, 0.0, 0.0), xlen = None, Tout = None, work = None, family = None, splitk = False):
@@ -328,8 +351,8 @@ def conv1d(x, wp, Cout, K, stride = 1, dil = 1, pad = 0, out_dtype = None, bias 
 		# which kernel the C side picks (conv.hip: convasr_conv1d_fwd -> convasr_conv1d_v2_try)
 		es, osz = x.element_size(), (2 if out_dtype in HALF_DTYPES else 4)
 		flops, nbytes_ = 2.0 * B * Tout * Cout * Cin * K if work is None else work, float(B * Tin * Cin * es + K * Cout * Cin * es + B * Tout * Cout * osz)
-		one_tap = K == 1 and pad == 0 and Cout % 128 == 0 and out_dtype == x.dtype and scale is None and act[0] == _lib.ACT_NONE and xlen is None  # conv1x1.hip takes these (csrc/conv.hip: conv1d_run)
-		kernel, symbol = _conv_timer_label(x.dtype in HALF_DTYPES and stride == 1 and Cin % 64 == 0, flops, nbytes_, out_dtype == x.dtype, one_tap)
+		v2s, one_tap = _conv_label_route(x.dtype, out_dtype, B, Cin, Cout, Tin, Tout, K, stride, dil, pad, scale is not None, act, xlen is not None, part is not None)
+		kernel, symbol = _conv_timer_label(v2s, flops, nbytes_, out_dtype == x.dtype, one_tap)
 		_lib.timed(family or kernel, flops, launch, nbytes = nbytes_, symbol = symbol)
 	if part is not None:
 		part.rows = rows.value

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CONVASR_ABI_VERSION 10
+#define CONVASR_ABI_VERSION 11
 
 enum { CONVASR_F32 = 0, CONVASR_BF16 = 1, CONVASR_I16 = 2, CONVASR_F16 = 3 };
 enum { CONVASR_ACT_NONE = 0, CONVASR_ACT_RELU = 1, CONVASR_ACT_HARDTANH = 2, CONVASR_ACT_LEAKY_RELU = 3 };
@@ -116,6 +116,18 @@ int convasr_conv1d_fwd(const void* x, const void* wp, void* y, int x_dtype, int 
                        int act, float act_lo, float act_hi, const float* xlen, int* stats_rows, void* stream);
 int convasr_conv_stats_max_rows(int B, int Tout);
 
+/* Which kernel convasr_conv1d_fwd would launch for this geometry and these optional operands (has_* / act: what conv1d_fwd would be given)
+ * under the current convasr_debug_set_conv_v2 state: 0 = the call would be refused (out[0] = the error code, convasr_last_error() the
+ * message), 1 = the register-staged kernel, 2 = the LDS-DMA kernel, 3 = the one-tap kernel.  out[CONVASR_CONV_ROUTE_INTS] = error code,
+ * B and Tout as the kernel is given them (a one-tap batch may be flattened to 1 x B T), tile rows, m tiles per utterance (one-tap: m
+ * tiles), n tiles, total tiles, full tiles, narrow parts and tail128 (LDS-DMA only: tiles from `full tiles` on run as 2 or 4 column
+ * pieces; 1 = the last m tile of an utterance is a 128-row tile, 2 = every tile is), x_rows, XI and ALIGNED_X (register-staged only),
+ * LDS stages (one-tap only), dynamic LDS bytes, partial statistics rows.  It is the decision code of the launch itself, not a copy;
+ * it launches nothing and needs no GPU: the tests ask it which shapes reach which instantiation. */
+#define CONVASR_CONV_ROUTE_INTS 16
+int convasr_conv1d_fwd_route(int x_dtype, int y_dtype, int B, int Cin, int Cout, int Tin, int Tout, int K, int stride, int dil, int pad,
+                             int has_scale_shift, int act, int has_xlen, int has_stats, int* out);
+
 /* Split-K form of convasr_conv1d_fwd for launches of a few tiles -- online inference, transcribe.py:140 / benchmark_online.py:125 (B = 1 x 6 s is
  * 4-16 workgroups per layer on 256 CUs, each reducing all of Cin x K alone): the reduction is cut over the 64-channel input blocks, workgroup
  * (tile, split) stores an fp32 partial tile into `workspace`, a second streaming kernel adds the partials in split order (deterministic) and
@@ -123,7 +135,8 @@ int convasr_conv_stats_max_rows(int B, int Tout);
  * kernel, 64-channel blocks) or fp32 in and out (the exact-fp32 kernel, 32-channel slabs; the partials are added in fp64).
  *   convasr_conv1d_fwd_splitk_plan: the number of splits for this geometry (1: not worth it -- from a quarter of the CUs' worth of tiles up -- or
  *     outside the envelope: call convasr_conv1d_fwd) and the workspace bytes (splits x B x Tout x Cout fp32);
- *   convasr_conv1d_fwd_splitk: `splits` must be the plan's answer (>= 2). */
+ *   convasr_conv1d_fwd_splitk: `splits` must be the plan's answer (>= 2).  The plan does not see the dilation: a 16-bit geometry whose halo
+ *     the LDS-DMA kernel cannot hold at 256-row tiles ((K - 1) dil > 64) runs as the unsplit convasr_conv1d_fwd, same epilogue. */
 int convasr_conv1d_fwd_splitk_plan(int x_dtype, int B, int Cin, int Cout, int Tout, int K, int64_t* workspace_bytes);
 int convasr_conv1d_fwd_splitk(const void* x, const void* wp, void* y, int x_dtype, int y_dtype,
                               int B, int Cin, int Cout, int Tin, int Tout, int K, int dil, int pad,

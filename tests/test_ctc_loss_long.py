@@ -70,4 +70,4 @@ def test_ops_route_and_tiles_are_exported():
 	assert ops.CTC_LONG_WORKSPACE_CAP == 16 << 30
 	lib = _lib.load()
 	assert ops.ctc_loss_long_tiles() == (lib.convasr_ctc_loss_long_states_per_block(), lib.convasr_ctc_loss_long_chunk_frames())
-	assert lib.convasr_abi_version() == 10
+	assert lib.convasr_abi_version() == 11

@@ -146,7 +146,7 @@ def test_wiring():
 	for name in NEW:
 		assert re.search(r'\b' + name + r'\s*\(', header), name
 		assert name in _lib._SIGNATURES and hasattr(lib, name), name
-	assert 'CONVASR_ABI_VERSION 10' in header and lib.convasr_abi_version() == 10
+	assert 'CONVASR_ABI_VERSION 11' in header and lib.convasr_abi_version() == 11
 	assert lib.convasr_ctc_keyword_search_max_labels() == 64 and lib.convasr_ctc_keyword_search_phrases_per_block() >= 1
 	staged = lib.convasr_ctc_keyword_search_staged_classes()
 	for C in (2, 38, 64, 65, staged, staged + 1, 8192):
