@@ -120,6 +120,20 @@ _SIGNATURES = dict(
 	convasr_ctc_beam_search_lm_wide_workspace_bytes = (c_i64, [c_int] * 6),
 	convasr_ctc_beam_search_lm_wide = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int,
 	                                           c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_p]),
+	convasr_ctc_beam_search_hot_workspace_bytes = (c_i64, [c_int] * 6),
+	convasr_ctc_beam_search_hot = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int,
+	                                       c_p, c_p, c_p, c_int, c_int, c_int, ctypes.c_double, c_p]),
+	convasr_ctc_beam_search_hot_wide_workspace_bytes = (c_i64, [c_int] * 6),
+	convasr_ctc_beam_search_hot_wide = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int,
+	                                            c_p, c_p, c_p, c_int, c_int, c_int, ctypes.c_double, c_p]),
+	convasr_ctc_beam_search_lm_hot_workspace_bytes = (c_i64, [c_int] * 6),
+	convasr_ctc_beam_search_lm_hot = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int,
+	                                          c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
+	                                          c_p, c_p, c_p, c_int, c_int, ctypes.c_double, c_p]),
+	convasr_ctc_beam_search_lm_hot_wide_workspace_bytes = (c_i64, [c_int] * 6),
+	convasr_ctc_beam_search_lm_hot_wide = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int,
+	                                               c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
+	                                               c_p, c_p, c_p, c_int, c_int, ctypes.c_double, c_p]),
 	convasr_edit_distance = (c_int, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_i64, c_p]),
 	convasr_ctc_greedy_collapse = (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_ctc_greedy_segments_chunk_frames = (c_int, []),

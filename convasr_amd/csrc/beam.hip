@@ -27,6 +27,12 @@
 // the utterance's region of the workspace instead of LDS (bs_wide_layout).  LDS keeps the sort buffer and the per-frame
 // class arrays.  A thread makes up to W / 1024 beams in step 4, so the beam state is double-buffered there, and the tie pass of the radix
 // select covers the 27-bit candidate key.  Every difference sits under `if constexpr (WIDE)`: the LDS kernels are unchanged.
+//
+// With hot phrases (convasr_ctc_beam_search_hot / _lm_hot and their wide forms; tables built by convasr_amd/hotwords.py, restated by
+// tests/_ctc_beam_hot_ref.py) the body runs as bs_body<LM, WIDE, true>.  Each beam also keeps the node of the phrase trie it has matched up
+// to (or DEAD), the number of labels matched since the last completed phrase, and that node's child mask; a candidate's score gets +w when
+// its class continues the match and gives the pending labels' bonus back when it does not (the header states the rule).  Every hot
+// statement sits under `if constexpr (HOT)`: the four kernels above are bs_body<*, *, false> and compile as before.
 #include <cmath>
 
 #include "common.h"
@@ -52,6 +58,16 @@ struct BsLm {
 	double alpha, beta;
 };
 
+// The hot-phrase trie (convasr_amd/hotwords.py documents it; the header states the rule); MW mask words per node as above.
+#define BS_HOT_DEAD (-1)
+struct BsHot {
+	const unsigned* mask;  // (n_nodes, MW)
+	const int* child;      // (n_nodes,)
+	const int* term;       // (n_nodes,): 1 when a phrase ends at the node
+	int n_nodes, space;
+	double w;
+};
+
 __host__ __device__ static inline int bs_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
 struct BsSel {
@@ -69,11 +85,13 @@ struct BsLayout {
 	size_t last, node, len, fold, sk, htab, pc, hist, pos;                   // 4- / 2-byte arrays
 	size_t lmsp, lnode, lstate, lmask;                                       // LM only: fp64 term, trie node, LM state, MW mask words
 	int MW;
+	size_t hu, hk, hmask, hroot;                                             // hot phrases only: trie node, pending count, HMW mask words; the root's mask (always LDS)
+	int HMW;
 	size_t bytes;               // LDS
 	size_t dbl, gbytes;         // wide form: the distance between the two copies of the beam state / the workspace bytes per utterance
 };
 
-__host__ __device__ static inline BsLayout bs_layout(int W, int N, int C, bool lm = false) {
+__host__ __device__ static inline BsLayout bs_layout(int W, int N, int C, bool lm = false, bool hot = false) {
 	BsLayout L;
 	L.W = W; L.NW = (N + 31) / 32; L.C = C;
 	L.S = bs_pow2(W > BS_MAX_N ? W : BS_MAX_N);
@@ -108,6 +126,15 @@ __host__ __device__ static inline BsLayout bs_layout(int W, int N, int C, bool l
 		L.lstate = o; o += 4 * (size_t)W;
 		L.lmask = o; o += 4 * (size_t)W * L.MW;
 	}
+	L.HMW = 0; L.hu = L.hk = L.hmask = L.hroot = 0;
+	if (hot) {
+		L.HMW = (C + 31) / 32;
+		o = (o + 3) & ~(size_t)3;
+		L.hu = o; o += 4 * (size_t)W;
+		L.hk = o; o += 4 * (size_t)W;
+		L.hmask = o; o += 4 * (size_t)W * L.HMW;
+		L.hroot = o; o += 4 * (size_t)L.HMW;
+	}
 	L.bytes = (o + 15) & ~(size_t)15;
 	L.dbl = L.gbytes = 0;
 	return L;
@@ -116,7 +143,7 @@ __host__ __device__ static inline BsLayout bs_layout(int W, int N, int C, bool l
 // The wide form.  LDS: the sort buffer (pow2(W) entries), the selection state and the per-frame class arrays, 117,328 bytes at most
 // (W = 8192, C = 8192).  Workspace, per utterance, at offsets from its region: the beam state written in step 4, twice (copy 1 at +dbl),
 // then own_*, fold and the hash table, rebuilt every frame.
-__host__ __device__ static inline BsLayout bs_wide_layout(int W, int N, int C, bool lm = false) {
+__host__ __device__ static inline BsLayout bs_wide_layout(int W, int N, int C, bool lm = false, bool hot = false) {
 	BsLayout L;
 	L.W = W; L.NW = (N + 31) / 32; L.C = C;
 	L.S = bs_pow2(W > BS_MAX_N ? W : BS_MAX_N);
@@ -130,6 +157,12 @@ __host__ __device__ static inline BsLayout bs_wide_layout(int W, int N, int C, b
 	L.pc = o; o += 4 * (size_t)BS_MAX_N;
 	L.hist = o; o += 4 * 256;
 	L.pos = o; o += 2 * (size_t)C;
+	L.HMW = 0; L.hu = L.hk = L.hmask = L.hroot = 0;
+	if (hot) {
+		L.HMW = (C + 31) / 32;
+		o = (o + 3) & ~(size_t)3;
+		L.hroot = o; o += 4 * (size_t)L.HMW;
+	}
 	L.bytes = (o + 15) & ~(size_t)15;
 	o = 0;
 	L.lpb = o; o += 8 * (size_t)W;
@@ -145,6 +178,11 @@ __host__ __device__ static inline BsLayout bs_wide_layout(int W, int N, int C, b
 	L.lstate = o; if (lm) o += 4 * (size_t)W;
 	L.lmask = o; o += 4 * (size_t)W * L.MW;
 	if (!lm) L.lmsp = L.lnode = L.lstate = L.lmask = 0;
+	if (hot) {
+		L.hu = o; o += 4 * (size_t)W;
+		L.hk = o; o += 4 * (size_t)W;
+		L.hmask = o; o += 4 * (size_t)W * L.HMW;
+	}
 	L.dbl = (o + 15) & ~(size_t)15;
 	o = 2 * L.dbl;
 	L.own_nb = o; o += 8 * (size_t)W;
@@ -343,13 +381,37 @@ __device__ int bs_lm_advance(const BsLm& lm, int s, int word) {
 	return word;
 }
 
-template <bool LM, bool WIDE>
+// ---- hot phrases: the state (node, pending) of l + c from that of l (the header's rule).  pmask: the MW mask words cached for l's node
+// (zero for a DEAD one), hroot: the root's.  The child index is checked against n_nodes, so a table that breaks hotwords.py's invariants
+// gives a wrong state, not a read outside the tables; there is no loop over the tables.
+__device__ __forceinline__ void bs_hot_step(const BsHot& hot, const unsigned* pmask, const unsigned* hroot, int MW, int pu, int pk, int plast, int c, int& nu, int& nk) {
+	const unsigned* m = nullptr;
+	int base = 0;
+	nk = 0;
+	if ((pmask[c >> 5] >> (c & 31)) & 1u) { m = pmask; base = pu; nk = pk + 1; }
+	else if (plast == hot.space && ((hroot[c >> 5] >> (c & 31)) & 1u)) { m = hroot; base = 0; nk = 1; }
+	if (m == nullptr) { nu = c == hot.space ? 0 : BS_HOT_DEAD; return; }
+	int below = 0;
+#pragma unroll
+	for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+		if (k < MW) {
+			const unsigned bits = m[k];
+			if (32 * k + 32 <= c) below += __popc(bits);
+			else if (32 * k <= c) below += __popc(bits & ((1u << (c & 31)) - 1u));
+		}
+	const int v = hot.child[base] + below;
+	if ((unsigned)v >= (unsigned)hot.n_nodes) { nu = BS_HOT_DEAD; nk = 0; return; }
+	nu = v;
+	if (hot.term[v]) nk = 0;
+}
+
+template <bool LM, bool WIDE, bool HOT>
 __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths, int64_t* __restrict__ out_tokens,
                                         int* __restrict__ out_offsets, int64_t* __restrict__ out_lengths, void* __restrict__ out_logp,
                                         int2* __restrict__ arena_all, unsigned char* __restrict__ state_all, int T, int C, int blank, int W, int N,
-                                        float cutoff_prob, int topk, const BsLm& lm) {
+                                        float cutoff_prob, int topk, const BsLm& lm, const BsHot& hot) {
 	extern __shared__ __align__(16) unsigned char bs_smem[];
-	const BsLayout Ly = WIDE ? bs_wide_layout(W, N, C, LM) : bs_layout(W, N, C, LM);
+	const BsLayout Ly = WIDE ? bs_wide_layout(W, N, C, LM, HOT) : bs_layout(W, N, C, LM, HOT);
 	unsigned char* bm = bs_smem;  // the per-beam arrays: LDS, or in the wide form the utterance's region of the workspace
 	if constexpr (WIDE) bm = state_all + (int64_t)blockIdx.x * Ly.gbytes;
 	BsSel& s = *(BsSel*)(bs_smem + Ly.sel);  // (dynamic: static LDS would stop the 160 KiB opt-in)
@@ -376,6 +438,18 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 	int* lnode = (int*)(bm + Ly.lnode);
 	int* lstate = (int*)(bm + Ly.lstate);
 	unsigned* lmask = (unsigned*)(bm + Ly.lmask);
+	int* hu = (int*)(bm + Ly.hu);
+	int* hk = (int*)(bm + Ly.hk);
+	unsigned* hmask = (unsigned*)(bm + Ly.hmask);
+	unsigned* hroot = (unsigned*)(bs_smem + Ly.hroot);
+	const int HMW = HOT ? Ly.HMW : 0;
+	// delta(l_i, c) of the header: +w on a match; otherwise the pending labels give their bonus back, and a match restarts at a word start
+	auto hot_delta = [&](int i, int c) -> double {
+		if ((hmask[i * HMW + (c >> 5)] >> (c & 31)) & 1u) return hot.w;
+		const double back = -__dmul_rn(hot.w, (double)hk[i]);
+		if (last[i] == hot.space && ((hroot[c >> 5] >> (c & 31)) & 1u)) return __dadd_rn(back, hot.w);
+		return back;
+	};
 	int64_t dbl = (int64_t)Ly.dbl;  // wide form: from the copy of the beam state being read to the one step 4 writes
 	const int MW = LM ? Ly.MW : 0;
 	const int space = LM ? lm.space : -1;
@@ -395,6 +469,10 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 	if constexpr (LM) {
 		if (tid == 0) { lmsp[0] = 0.0; lnode[0] = 0; lstate[0] = lm.start; }
 		for (int k = tid; k < MW; k += nth) lmask[k] = lm.node_mask[k];  // the root's children; the space is not allowed
+	}
+	if constexpr (HOT) {
+		if (tid == 0) { hu[0] = 0; hk[0] = 0; }
+		for (int k = tid; k < HMW; k += nth) { const unsigned bits = hot.mask[k]; hmask[k] = bits; hroot[k] = bits; }
 	}
 	__syncthreads();
 
@@ -481,6 +559,7 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 					double e = plp[pl] + (last[i] == lj ? lpb[i] : tot[i]);
 					if constexpr (LM)
 						if (lj == space) e += lmsp[i];
+					if constexpr (HOT) e = __dadd_rn(e, hot_delta(i, lj));
 					nnb = bs_lae(nnb, e);
 					atomicOr(&fold[i * NW + (pl >> 5)], 1u << (pl & 31));
 				}
@@ -505,6 +584,7 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 					sc = plp[p] + (c == last[i] ? lpb[i] : tot[i]);
 					if constexpr (LM)
 						if (c == space) sc += lmsp[i];
+					if constexpr (HOT) sc = __dadd_rn(sc, hot_delta(i, c));
 					key |= (unsigned)(c + 1);
 				}
 				if (ok && sc > NEG) fn(bs_desc64(sc), key);
@@ -535,6 +615,8 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 				double nlmsp = 0.0;
 				int nlnode = 0, nlstate = 0;
 				unsigned nmask[BS_LM_MAX_C / 32];
+				int nhu = 0, nhk = 0;
+				unsigned nhmask[BS_LM_MAX_C / 32];
 				const unsigned key = (unsigned)sk[r];
 				const int i = (int)(key >> BS_KEY_C_BITS), c = (int)(key & ((1u << BS_KEY_C_BITS) - 1)) - 1;
 				ntot = bs_undesc64(su[r]);
@@ -545,10 +627,20 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 #pragma unroll
 						for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nmask[k] = k < MW ? lmask[i * MW + k] : 0u;
 					}
+					if constexpr (HOT) {
+						nhu = hu[i]; nhk = hk[i];
+#pragma unroll
+						for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nhmask[k] = k < HMW ? hmask[i * HMW + k] : 0u;
+					}
 				} else {
 					nlpb = NEG; nlpnb = ntot; nh = bs_extend_hash(hash[i], c); nph = hash[i]; nlast = c; nlen = len[i] + 1;
 					nnode = t * W + r;
 					arena[nnode] = make_int2(node[i], c);
+					if constexpr (HOT) {
+						bs_hot_step(hot, hmask + i * HMW, hroot, HMW, hu[i], hk[i], last[i], c, nhu, nhk);
+#pragma unroll
+						for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nhmask[k] = (k < HMW && nhu >= 0) ? hot.mask[(int64_t)nhu * HMW + k] : 0u;
+					}
 					if constexpr (LM) {
 						nlstate = lstate[i];
 						int word;
@@ -588,9 +680,16 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 					for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
 						if (k < MW) nx(lmask)[r * MW + k] = nmask[k];
 				}
+				if constexpr (HOT) {
+					nx(hu)[r] = nhu; nx(hk)[r] = nhk;
+#pragma unroll
+					for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+						if (k < HMW) nx(hmask)[r * HMW + k] = nhmask[k];
+				}
 			}
 			lpb = nx(lpb); lpnb = nx(lpnb); tot = nx(tot); hash = nx(hash); phash = nx(phash); last = nx(last); node = nx(node); len = nx(len);
 			if constexpr (LM) { lmsp = nx(lmsp); lnode = nx(lnode); lstate = nx(lstate); lmask = nx(lmask); }
+			if constexpr (HOT) { hu = nx(hu); hk = nx(hk); hmask = nx(hmask); }
 			dbl = -dbl;
 		} else {
 			double nlpb = 0, nlpnb = 0, ntot = 0;
@@ -599,6 +698,8 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 			double nlmsp = 0.0;
 			int nlnode = 0, nlstate = 0;
 			unsigned nmask[BS_LM_MAX_C / 32];
+			int nhu = 0, nhk = 0;
+			unsigned nhmask[BS_LM_MAX_C / 32];
 			if (tid < m) {
 				const unsigned key = (unsigned)sk[tid];
 				const int i = (int)(key >> BS_KEY_C_BITS), c = (int)(key & ((1u << BS_KEY_C_BITS) - 1)) - 1;
@@ -610,10 +711,20 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 #pragma unroll
 						for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nmask[k] = k < MW ? lmask[i * MW + k] : 0u;
 					}
+					if constexpr (HOT) {
+						nhu = hu[i]; nhk = hk[i];
+#pragma unroll
+						for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nhmask[k] = k < HMW ? hmask[i * HMW + k] : 0u;
+					}
 				} else {
 					nlpb = NEG; nlpnb = ntot; nh = bs_extend_hash(hash[i], c); nph = hash[i]; nlast = c; nlen = len[i] + 1;
 					nnode = t * W + tid;
 					arena[nnode] = make_int2(node[i], c);
+					if constexpr (HOT) {
+						bs_hot_step(hot, hmask + i * HMW, hroot, HMW, hu[i], hk[i], last[i], c, nhu, nhk);
+#pragma unroll
+						for (int k = 0; k < BS_LM_MAX_C / 32; ++k) nhmask[k] = (k < HMW && nhu >= 0) ? hot.mask[(int64_t)nhu * HMW + k] : 0u;
+					}
 					if constexpr (LM) {
 						nlstate = lstate[i];
 						int word;
@@ -657,6 +768,14 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 						if (k < MW) lmask[tid * MW + k] = nmask[k];
 				}
 			}
+			if constexpr (HOT) {
+				if (tid < m) {
+					hu[tid] = nhu; hk[tid] = nhk;
+#pragma unroll
+					for (int k = 0; k < BS_LM_MAX_C / 32; ++k)
+						if (k < HMW) hmask[tid * HMW + k] = nhmask[k];
+				}
+			}
 		}
 		if (tid == 0) s.n = m;
 		__syncthreads();
@@ -664,14 +783,20 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 
 	// ---- results: the best topk beams, walked back through the arena
 	const int n = s.n;
-	if constexpr (LM) {  // the end-of-utterance term F(l), then the beams re-ranked by lpb + lpnb + F (ties: rank); tot[] = the fused score
-		const double oov = lm.alpha * -1000.0 + lm.beta;
+	if constexpr (LM || HOT) {  // the end-of-utterance terms, then the beams re-ranked by the result (ties: rank): the LM's F(l), and with hot phrases
+		// F_hot(l) = -(w * k), a pending match giving its bonus back; su[] = the returned score
+		const double oov = LM ? lm.alpha * -1000.0 + lm.beta : 0.0;
 		const int Sn = bs_pow2(n);
 		for (int r = tid; r < Sn; r += nth) {
 			if (r < n) {
-				const bool in_v = (lmask[r * MW + (space >> 5)] >> (space & 31)) & 1u;
-				const double F = (len[r] == 0 || last[r] == space) ? 0.0 : (in_v ? lmsp[r] : oov);
-				su[r] = bs_desc64(tot[r] + F); sk[r] = r;
+				double fs = tot[r];
+				if constexpr (LM) {
+					const bool in_v = (lmask[r * MW + (space >> 5)] >> (space & 31)) & 1u;
+					const double F = (len[r] == 0 || last[r] == space) ? 0.0 : (in_v ? lmsp[r] : oov);
+					fs = fs + F;
+				}
+				if constexpr (HOT) fs = __dadd_rn(fs, -__dmul_rn(hot.w, (double)hk[r]));
+				su[r] = bs_desc64(fs); sk[r] = r;
 			} else {
 				su[r] = ~0ull; sk[r] = 0x7fffffff;
 			}
@@ -683,11 +808,11 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 	int* off_b = out_offsets + (int64_t)b * topk * T;
 	for (int64_t e = tid; e < (int64_t)topk * T; e += nth) {
 		const int k = (int)(e / T), p = (int)(e % T);
-		if (p >= (k < n ? len[LM ? sk[k] : k] : 0)) { tok_b[e] = 0; off_b[e] = 0; }
+		if (p >= (k < n ? len[(LM || HOT) ? sk[k] : k] : 0)) { tok_b[e] = 0; off_b[e] = 0; }
 	}
 	for (int k = tid; k < topk; k += nth) {
 		if (k < n) {
-			const int r = LM ? sk[k] : k;
+			const int r = (LM || HOT) ? sk[k] : k;
 			int p = len[r] - 1;
 			for (int nd = node[r]; nd >= 0 && p >= 0; --p) {
 				const int2 v = arena[nd];
@@ -696,11 +821,11 @@ __device__ __forceinline__ void bs_body(const float* __restrict__ log_probs, con
 				nd = v.x;
 			}
 			out_lengths[(int64_t)b * topk + k] = len[r];
-			if constexpr (LM) ((double*)out_logp)[(int64_t)b * topk + k] = bs_undesc64(su[k]);
+			if constexpr (LM || HOT) ((double*)out_logp)[(int64_t)b * topk + k] = bs_undesc64(su[k]);
 			else ((float*)out_logp)[(int64_t)b * topk + k] = (float)tot[k];
 		} else {
 			out_lengths[(int64_t)b * topk + k] = 0;
-			if constexpr (LM) ((double*)out_logp)[(int64_t)b * topk + k] = -INFINITY;
+			if constexpr (LM || HOT) ((double*)out_logp)[(int64_t)b * topk + k] = -INFINITY;
 			else ((float*)out_logp)[(int64_t)b * topk + k] = -INFINITY;
 		}
 	}
@@ -712,7 +837,8 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __re
                                                                 int2* __restrict__ arena_all, int T, int C, int blank, int W, int N,
                                                                 float cutoff_prob, int topk) {
 	const BsLm none{};
-	bs_body<false, false>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, nullptr, T, C, blank, W, N, cutoff_prob, topk, none);
+	const BsHot cold{};
+	bs_body<false, false, false>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, nullptr, T, C, blank, W, N, cutoff_prob, topk, none, cold);
 }
 
 __global__ __launch_bounds__(1024) void ctc_beam_search_lm_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
@@ -720,7 +846,8 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_lm_kernel(const float* _
                                                                    int64_t* __restrict__ out_lengths, double* __restrict__ out_logp,
                                                                    int2* __restrict__ arena_all, int T, int C, int blank, int W, int N,
                                                                    float cutoff_prob, int topk, BsLm lm) {
-	bs_body<true, false>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, nullptr, T, C, blank, W, N, cutoff_prob, topk, lm);
+	const BsHot cold{};
+	bs_body<true, false, false>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, nullptr, T, C, blank, W, N, cutoff_prob, topk, lm, cold);
 }
 
 __global__ __launch_bounds__(1024) void ctc_beam_search_wide_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
@@ -729,7 +856,8 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_wide_kernel(const float*
                                                                      int2* __restrict__ arena_all, unsigned char* __restrict__ state_all, int T, int C,
                                                                      int blank, int W, int N, float cutoff_prob, int topk) {
 	const BsLm none{};
-	bs_body<false, true>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, state_all, T, C, blank, W, N, cutoff_prob, topk, none);
+	const BsHot cold{};
+	bs_body<false, true, false>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, state_all, T, C, blank, W, N, cutoff_prob, topk, none, cold);
 }
 
 __global__ __launch_bounds__(1024) void ctc_beam_search_lm_wide_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
@@ -737,7 +865,8 @@ __global__ __launch_bounds__(1024) void ctc_beam_search_lm_wide_kernel(const flo
                                                                         int64_t* __restrict__ out_lengths, double* __restrict__ out_logp,
                                                                         int2* __restrict__ arena_all, unsigned char* __restrict__ state_all, int T,
                                                                         int C, int blank, int W, int N, float cutoff_prob, int topk, BsLm lm) {
-	bs_body<true, true>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, state_all, T, C, blank, W, N, cutoff_prob, topk, lm);
+	const BsHot cold{};
+	bs_body<true, true, false>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, state_all, T, C, blank, W, N, cutoff_prob, topk, lm, cold);
 }
 
 static const char* bs_envelope(int B, int T, int C, int W, int N, int topk, int* code, bool wide = false) {
@@ -911,4 +1040,144 @@ extern "C" int convasr_ctc_beam_search_lm_wide(const float* log_probs, const int
 	                   log_prob, (int2*)workspace, state, T, C, blank, W, N, cutoff_prob, topk, lm);
 	CONVASR_CHECK_LAUNCH("ctc_beam_search_lm_wide");
 	return 0;
+}
+
+// ---- with hot phrases: bs_body<LM, WIDE, true>, the score fp64 on all four
+template <bool LM, bool WIDE>
+__global__ __launch_bounds__(1024) void ctc_beam_search_hot_kernel(const float* __restrict__ log_probs, const int64_t* __restrict__ lengths,
+                                                                    int64_t* __restrict__ out_tokens, int* __restrict__ out_offsets,
+                                                                    int64_t* __restrict__ out_lengths, double* __restrict__ out_logp,
+                                                                    int2* __restrict__ arena_all, unsigned char* __restrict__ state_all, int T, int C,
+                                                                    int blank, int W, int N, float cutoff_prob, int topk, BsLm lm, BsHot hot) {
+	bs_body<LM, WIDE, true>(log_probs, lengths, out_tokens, out_offsets, out_lengths, out_logp, arena_all, state_all, T, C, blank, W, N, cutoff_prob, topk, lm, hot);
+}
+
+static const char* bs_hot_envelope(int B, int T, int C, int W, int N, int topk, bool lm, bool wide, int* code) {
+	if (const char* why = bs_envelope(B, T, C, W, N, topk, code, wide)) return why;
+	*code = CONVASR_EUNSUPPORTED;
+	if (C > BS_LM_MAX_C) return "C > 256 is outside the envelope of the hot-phrase search";
+	if (wide) {
+		if (bs_wide_layout(W, N, C, lm, true).bytes > 160 * 1024) return "the sort buffer and class arrays exceed 160 KiB of LDS";  // (never within the checks above)
+	} else if (bs_layout(W, N, C, lm, true).bytes > 160 * 1024)
+		return "the beam state exceeds 160 KiB of LDS (hot-phrase search: see the header for the largest beam width per C and N)";
+	return nullptr;
+}
+
+static int64_t bs_hot_workspace(const char* fn, int B, int T, int C, int W, int N, int topk, bool lm, bool wide) {
+	int code;
+	if (const char* why = bs_hot_envelope(B, T, C, W, N, topk, lm, wide, &code))
+		return convasr_fail(code, "%s: %s (B %d T %d C %d W %d N %d topk %d)", fn, why, B, T, C, W, N, topk);
+	if (wide) return bs_wide_arena_bytes(B, T, W) + (int64_t)B * (int64_t)bs_wide_layout(W, N, C, lm, true).gbytes;
+	return (int64_t)B * T * W * (int64_t)sizeof(int2);
+}
+
+// the hot entry points' checks after the envelope; fills *hot
+static int bs_hot_args(const char* fn, int C, int blank, int space, const uint32_t* hot_mask, const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes,
+                       int hot_mask_words, double weight, BsHot* hot) {
+	CONVASR_CHECK_ARG(hot_mask && hot_child && hot_term, "%s: NULL hot-phrase table", fn);
+	CONVASR_CHECK_ARG(blank >= 0 && blank < C, "%s: blank %d outside [0, %d)", fn, blank, C);
+	CONVASR_CHECK_ARG(space >= 0 && space < C && space != blank, "%s: space class %d must be in [0, %d) and differ from the blank %d", fn, space, C, blank);
+	CONVASR_CHECK_ARG(n_hot_nodes >= 1, "%s: empty hot-phrase tables (%d trie nodes; the root alone is 1)", fn, n_hot_nodes);
+	CONVASR_CHECK_ARG(hot_mask_words == (C + 31) / 32, "%s: %d mask words per hot-phrase node, %d classes need %d", fn, hot_mask_words, C, (C + 31) / 32);
+	CONVASR_CHECK_ARG(std::isfinite(weight) && weight >= 0.0, "%s: the hot-phrase weight must be finite and >= 0", fn);
+	hot->mask = hot_mask; hot->child = hot_child; hot->term = hot_term; hot->n_nodes = n_hot_nodes; hot->space = space; hot->w = weight;
+	return 0;
+}
+
+template <bool LM, bool WIDE>
+static int bs_hot_launch(const char* fn, const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths, double* log_prob,
+                         void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk, const BsLm& lm, const BsHot& hot, void* stream) {
+	const BsLayout Ly = WIDE ? bs_wide_layout(W, N, C, LM, true) : bs_layout(W, N, C, LM, true);
+	const int threads = W <= 256 ? 256 : 1024;
+	static unsigned long long set = 0;
+	convasr_allow_160k_lds(reinterpret_cast<const void*>(ctc_beam_search_hot_kernel<LM, WIDE>), set);
+	unsigned char* state = WIDE ? (unsigned char*)workspace + bs_wide_arena_bytes(B, T, W) : nullptr;
+	hipLaunchKernelGGL((ctc_beam_search_hot_kernel<LM, WIDE>), dim3(B), dim3(threads), Ly.bytes, (hipStream_t)stream, log_probs, lengths, tokens, offsets, out_lengths,
+	                   log_prob, (int2*)workspace, state, T, C, blank, W, N, cutoff_prob, topk, lm, hot);
+	CONVASR_CHECK_LAUNCH(fn);
+	return 0;
+}
+
+template <bool WIDE>
+static int bs_hot_call(const char* fn, const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths, double* log_prob,
+                       void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk, const uint32_t* hot_mask,
+                       const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes, int hot_mask_words, int space, double weight, void* stream) {
+	CONVASR_CHECK_ARG(log_probs && lengths && tokens && offsets && out_lengths && log_prob && workspace, "%s: NULL pointer", fn);
+	if (const int64_t rc = bs_hot_workspace(fn, B, T, C, W, N, topk, false, WIDE); rc < 0) return (int)rc;
+	CONVASR_CHECK_ARG(cutoff_prob > 0.f && cutoff_prob <= 1.f, "%s: cutoff_prob must be in (0, 1]", fn);
+	BsHot hot;
+	if (int rc = bs_hot_args(fn, C, blank, space, hot_mask, hot_child, hot_term, n_hot_nodes, hot_mask_words, weight, &hot)) return rc;
+	const BsLm none{};
+	return bs_hot_launch<false, WIDE>(fn, log_probs, lengths, tokens, offsets, out_lengths, log_prob, workspace, B, T, C, blank, W, N, cutoff_prob, topk, none, hot, stream);
+}
+
+template <bool WIDE>
+static int bs_lm_hot_call(const char* fn, const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths, double* log_prob,
+                          void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk, const uint32_t* node_mask,
+                          const int32_t* node_child, const int32_t* node_word, int n_nodes, const double* ent_pb, const int32_t* ent_sl, int n_ent,
+                          const int32_t* slots, int n_slots, int space, int order, int start_state, double alpha, double beta, const uint32_t* hot_mask,
+                          const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes, int hot_mask_words, double weight, void* stream) {
+	CONVASR_CHECK_ARG(log_probs && lengths && tokens && offsets && out_lengths && log_prob && workspace, "%s: NULL pointer", fn);
+	CONVASR_CHECK_ARG(node_mask && node_child && node_word && ent_pb && ent_sl && slots, "%s: NULL LM table", fn);
+	if (const int64_t rc = bs_hot_workspace(fn, B, T, C, W, N, topk, true, WIDE); rc < 0) return (int)rc;
+	BsLm lm;
+	if (int rc = bs_lm_args(fn, C, blank, cutoff_prob, node_mask, node_child, node_word, n_nodes, ent_pb, ent_sl, n_ent, slots, n_slots, space, order, start_state,
+	                        alpha, beta, &lm))
+		return rc;
+	BsHot hot;
+	if (int rc = bs_hot_args(fn, C, blank, space, hot_mask, hot_child, hot_term, n_hot_nodes, hot_mask_words, weight, &hot)) return rc;
+	return bs_hot_launch<true, WIDE>(fn, log_probs, lengths, tokens, offsets, out_lengths, log_prob, workspace, B, T, C, blank, W, N, cutoff_prob, topk, lm, hot, stream);
+}
+
+extern "C" int64_t convasr_ctc_beam_search_hot_workspace_bytes(int B, int T, int C, int W, int N, int topk) {
+	return bs_hot_workspace("ctc_beam_search_hot", B, T, C, W, N, topk, false, false);
+}
+extern "C" int64_t convasr_ctc_beam_search_hot_wide_workspace_bytes(int B, int T, int C, int W, int N, int topk) {
+	return bs_hot_workspace("ctc_beam_search_hot_wide", B, T, C, W, N, topk, false, true);
+}
+extern "C" int64_t convasr_ctc_beam_search_lm_hot_workspace_bytes(int B, int T, int C, int W, int N, int topk) {
+	return bs_hot_workspace("ctc_beam_search_lm_hot", B, T, C, W, N, topk, true, false);
+}
+extern "C" int64_t convasr_ctc_beam_search_lm_hot_wide_workspace_bytes(int B, int T, int C, int W, int N, int topk) {
+	return bs_hot_workspace("ctc_beam_search_lm_hot_wide", B, T, C, W, N, topk, true, true);
+}
+
+extern "C" int convasr_ctc_beam_search_hot(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                           double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                                           const uint32_t* hot_mask, const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes, int hot_mask_words,
+                                           int space, double weight, void* stream) {
+	return bs_hot_call<false>("ctc_beam_search_hot", log_probs, lengths, tokens, offsets, out_lengths, log_prob, workspace, B, T, C, blank, W, N, cutoff_prob, topk,
+	                          hot_mask, hot_child, hot_term, n_hot_nodes, hot_mask_words, space, weight, stream);
+}
+
+extern "C" int convasr_ctc_beam_search_hot_wide(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                                double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                                                const uint32_t* hot_mask, const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes,
+                                                int hot_mask_words, int space, double weight, void* stream) {
+	return bs_hot_call<true>("ctc_beam_search_hot_wide", log_probs, lengths, tokens, offsets, out_lengths, log_prob, workspace, B, T, C, blank, W, N, cutoff_prob, topk,
+	                         hot_mask, hot_child, hot_term, n_hot_nodes, hot_mask_words, space, weight, stream);
+}
+
+extern "C" int convasr_ctc_beam_search_lm_hot(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                              double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                                              const uint32_t* node_mask, const int32_t* node_child, const int32_t* node_word, int n_nodes,
+                                              const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
+                                              int space, int order, int start_state, double alpha, double beta, const uint32_t* hot_mask,
+                                              const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes, int hot_mask_words, double weight,
+                                              void* stream) {
+	return bs_lm_hot_call<false>("ctc_beam_search_lm_hot", log_probs, lengths, tokens, offsets, out_lengths, log_prob, workspace, B, T, C, blank, W, N, cutoff_prob,
+	                             topk, node_mask, node_child, node_word, n_nodes, ent_pb, ent_sl, n_ent, slots, n_slots, space, order, start_state, alpha, beta,
+	                             hot_mask, hot_child, hot_term, n_hot_nodes, hot_mask_words, weight, stream);
+}
+
+extern "C" int convasr_ctc_beam_search_lm_hot_wide(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                                   double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob,
+                                                   int topk, const uint32_t* node_mask, const int32_t* node_child, const int32_t* node_word, int n_nodes,
+                                                   const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
+                                                   int space, int order, int start_state, double alpha, double beta, const uint32_t* hot_mask,
+                                                   const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes, int hot_mask_words, double weight,
+                                                   void* stream) {
+	return bs_lm_hot_call<true>("ctc_beam_search_lm_hot_wide", log_probs, lengths, tokens, offsets, out_lengths, log_prob, workspace, B, T, C, blank, W, N,
+	                            cutoff_prob, topk, node_mask, node_child, node_word, n_nodes, ent_pb, ent_sl, n_ent, slots, n_slots, space, order, start_state, alpha,
+	                            beta, hot_mask, hot_child, hot_term, n_hot_nodes, hot_mask_words, weight, stream);
 }

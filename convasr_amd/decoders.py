@@ -12,6 +12,7 @@ import os
 
 import torch
 
+from . import hotwords as hot_mod
 from . import lm as lm_mod
 from . import ops
 
@@ -63,10 +64,17 @@ class BeamSearchDecoder:
 	labels (one model for many decoders).  With an LM the labels (a string, or a tokenizer / Labels object whose idx2char, vocab or str()
 	gives one character per class, lowercased) need exactly one space, which is not the blank; C <= 256; beam_alpha and beam_beta weigh
 	the LM term alpha * ln P(word | context) + beta, and the returned scores are the fused log p (include/convasr_hip.h).  A path that
-	cannot be read as ARPA text (a KenLM binary among them) raises NotImplementedError."""
+	cannot be read as ARPA text (a KenLM binary among them) raises NotImplementedError.
 
-	def __init__(self, labels, lm_path = None, beam_width = None, beam_alpha = 0, beam_beta = 0, cutoff_top_n = 40, cutoff_prob = 1.0, num_workers = 1, topk = 1):
-		self.lm = None
+	hotwords: None, a list of phrases, or a hotwords.HotWords already built for these labels: the search is biased towards them
+	(convasr_ctc_beam_search_hot; ops.ctc_beam_search_hot states the rule).  hotword_weight, in natural-log units per matched label, is
+	required whenever hotwords are given: no value has been tuned on speech here, so there is deliberately no default.  The labels need
+	exactly one space, which is not the blank; C <= 256; with an LM every word of every phrase must be in its vocabulary; the returned
+	scores are then fp64.  Without hotwords nothing changes."""
+
+	def __init__(self, labels, lm_path = None, beam_width = None, beam_alpha = 0, beam_beta = 0, cutoff_top_n = 40, cutoff_prob = 1.0, num_workers = 1, topk = 1,
+	             hotwords = None, hotword_weight = None):
+		self.lm = self.hot = None
 		if lm_path is not None and not isinstance(lm_path, lm_mod.NgramLM):
 			arpa = lm_path if isinstance(lm_path, lm_mod.Arpa) else lm_mod.read_arpa(os.fspath(lm_path))  # (NotImplementedError for a non-ARPA path)
 			lm_path = lm_mod.NgramLM(arpa, _labels_of(labels))
@@ -82,10 +90,26 @@ class BeamSearchDecoder:
 				raise ValueError(f'BeamSearchDecoder: beam_alpha {beam_alpha} and beam_beta {beam_beta} must be finite')
 			lm_path.tables(self.blank)  # (the vocabulary's ValueError / NotImplementedError, here rather than at the first decode)
 			self.lm = lm_path
+		if hotwords is not None:
+			if hotword_weight is None:
+				raise ValueError('BeamSearchDecoder: hotwords need a hotword_weight (natural-log units per matched label; there is no default)')
+			self.hot_weight = float(hotword_weight)
+			if not (math.isfinite(self.hot_weight) and self.hot_weight >= 0.0):
+				raise ValueError(f'BeamSearchDecoder: hotword_weight {hotword_weight} must be finite and >= 0')
+			hot = hotwords if isinstance(hotwords, hot_mod.HotWords) else hot_mod.HotWords(hotwords, _labels_of(labels))
+			hot.tables(self.blank)  # (a phrase with the blank's character: ValueError here rather than at the first decode)
+			if self.lm is not None:
+				hot.check_vocabulary(self.lm, self.blank)
+			self.hot = hot
+		elif hotword_weight is not None:
+			raise ValueError('BeamSearchDecoder: hotword_weight without hotwords')
 
 	def decode_with_scores(self, log_probs, output_lengths = None):
 		"""(tokens (B, topk, T) int64, offsets (B, topk, T) int32 frames, lengths (B, topk) int64, log_prob (B, topk)), best first; log_prob is
-		fp32 log p without an LM, fp64 fused log p with one."""
+		fp32 log p without an LM, fp64 fused log p with one, fp64 with hotwords."""
+		if self.hot is not None:
+			return ops.ctc_beam_search_hot(log_probs, output_lengths, self.blank, self.beam_width, self.hot, self.hot_weight, self.lm, getattr(self, 'alpha', 0.0),
+			                               getattr(self, 'beta', 0.0), self.cutoff_top_n, self.cutoff_prob, self.topk)
 		if self.lm is not None:
 			return ops.ctc_beam_search_lm(log_probs, output_lengths, self.blank, self.beam_width, self.lm, self.alpha, self.beta, self.cutoff_top_n, self.cutoff_prob, self.topk)
 		return ops.ctc_beam_search(log_probs, output_lengths, self.blank, self.beam_width, self.cutoff_top_n, self.cutoff_prob, self.topk)

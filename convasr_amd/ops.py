@@ -1189,6 +1189,55 @@ def ctc_beam_search_lm(log_probs_bct, lengths, blank, beam_width, lm, alpha, bet
 	return tokens, offsets, out_lengths, log_prob
 
 
+def ctc_beam_search_hot(log_probs_bct, lengths, blank, beam_width, hot, weight, lm = None, alpha = 0.0, beta = 0.0, cutoff_top_n = 40, cutoff_prob = 1.0, topk = 1, *,
+                        wide = None):
+	"""CTC prefix beam search biased towards a list of hot phrases (include/convasr_hip.h: convasr_ctc_beam_search_hot).  hot: a
+	hotwords.HotWords built for the C labels of log_probs_bct (its tables are uploaded to the device once and kept by it); weight >= 0,
+	in natural-log units per matched label: a hypothesis gains weight for every label of a listed phrase it spells in full, starting at
+	the beginning of the utterance or after a space, and nothing for a phrase it leaves unfinished.  No weight has been tuned on speech
+	here, so there is no default.  lm: None, or an lm.NgramLM for the same labels, fused as ctc_beam_search_lm does with alpha / beta
+	(convasr_ctc_beam_search_lm_hot); every word of every phrase must then be in its vocabulary (ValueError otherwise).
+	Inputs, outputs and `wide` as ctc_beam_search, except log_prob: (B, topk) fp64 with or without an LM, the ranking score lpb + lpnb
+	(+ the LM's F) + F_hot, best first.  C <= 256.  Without an LM the LDS kernel takes beam_width 1024 at every C <= 256; with an LM at
+	C <= 96 and cutoff_top_n <= 64 (C = 38 among them), and e.g. 814 at C = 256 (the header lists the widths); a width its budget refuses
+	runs the wide kernel (beam_width <= 8192), with the same results.  weight = 0
+	or an empty list is the search of ctc_beam_search / ctc_beam_search_lm.  Outside the envelope it raises ConvasrHipError."""
+	require_cuda(log_probs_bct)
+	B, C, T = log_probs_bct.shape
+	blank, weight = int(blank), float(weight)
+	if C != hot.num_classes:
+		raise ValueError(f'ctc_beam_search_hot: {C} classes, but the hot phrases were built for {hot.num_classes} labels')
+	if not (math.isfinite(weight) and weight >= 0.0):
+		raise ValueError(f'ctc_beam_search_hot: the weight {weight} must be finite and >= 0')
+	name = 'ctc_beam_search_hot'
+	if lm is not None:
+		name = 'ctc_beam_search_lm_hot'
+		if C != lm.num_classes or lm.space != hot.space:
+			raise ValueError(f'ctc_beam_search_hot: the language model was built for other labels ({lm.num_classes} classes, space {lm.space}) than the hot phrases ({C}, {hot.space})')
+		hot.check_vocabulary(lm, blank)
+	lp = as_cl(log_probs_bct, torch.float32)
+	dev = lp.device
+	h = hot.device_tables(blank, dev)  # (ValueError for a phrase with the blank's character, or a blank that is the space)
+	lengths = _frame_lengths(name, lengths, B, T, dev)
+	N = C if cutoff_top_n is None else min(int(cutoff_top_n), C)
+	W, topk = int(beam_width), int(topk)
+	fn, nbytes = _beam_route(name, (B, T, C, W, N, topk), wide)
+	tokens = torch.empty(B, topk, T, dtype = torch.int64, device = dev)
+	offsets = torch.empty(B, topk, T, dtype = torch.int32, device = dev)
+	out_lengths = torch.empty(B, topk, dtype = torch.int64, device = dev)
+	log_prob = torch.empty(B, topk, dtype = torch.float64, device = dev)
+	ws = _call_workspace(nbytes, dev)
+	hot_args = (ptr(h['hot_mask']), ptr(h['hot_child']), ptr(h['hot_term']), int(h['hot_term'].numel()), int(h['hot_mask'].shape[1]))
+	head = (ptr(lp), ptr(lengths), ptr(tokens), ptr(offsets), ptr(out_lengths), ptr(log_prob), ptr(ws), B, T, C, blank, W, N, float(cutoff_prob), topk)
+	if lm is None:
+		call(fn, *head, *hot_args, hot.space, weight, stream_ptr())
+	else:
+		t = lm.device_tables(blank, dev)
+		call(fn, *head, ptr(t['node_mask']), ptr(t['node_child']), ptr(t['node_word']), int(t['node_word'].numel()), ptr(t['ent_pb']), ptr(t['ent_sl']),
+		     int(t['ent_sl'].shape[0]), ptr(t['slots']), int(t['slots'].shape[0]), lm.space, lm.order, lm.start_state, float(alpha), float(beta), *hot_args, weight, stream_ptr())
+	return tokens, offsets, out_lengths, log_prob
+
+
 def ctc_greedy_collapse(path, lengths, eps, space, blank_amount_to_space = 10):
 	"""GreedyCTCGenerator.generate's collapse (time_stamps None, silence = {eps, space}, word start = space) on the device
 	(include/convasr_hip.h: convasr_ctc_greedy_collapse).  path: (B, T) int64 per-frame argmax (ops.argmax); lengths (B,) frames, or None

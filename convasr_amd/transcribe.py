@@ -4,7 +4,8 @@
   checkpoint -> frontend + model (the reference's class names / state-dict keys) -> eval() -> fuse_conv_bn_eval() ->
   compute dtype from args.fp16 (None / 'O0': exact fp32; 'O1'..'O3': fp16 storage + MFMA as under apex.amp, or bf16 when models.AMP_DTYPE says so) -> greedy generator,
   or with args.decoder = 'BeamSearchDecoder' the CTC prefix beam search (args.beam_width, args.decoder_topk; args.lm an ARPA n-gram model
-  weighed by args.beam_alpha / args.beam_beta).
+  weighed by args.beam_alpha / args.beam_beta; args.hotwords, a list of phrases or the path of a text file with one phrase per line, and
+  args.hotword_weight bias the search towards those phrases: this package's own, the reference has no hot words).
 * transcribe_batch(...)                                                                transcribe.py:140-200
   the per-batch body of transcribe.main: forward (every op a HIP kernel; the argmax of the greedy decode too), per-frame time
   stamps, GreedyCTCGenerator with time stamps (one segment per word), optional forced alignment of the reference text
@@ -20,6 +21,7 @@
 Out of scope: file discovery, audio decoding, the dataset, text pre/post-processing pipelines (regexes, number
 normalisation) and the json / html / csv / txt writers around this body (CER and the error analysis live in metrics).  A TextPipeline here is the tokenizer
 plus identity pre/post-processing; pass the reference's own pipeline object as args.text_pipeline to get its text handling."""
+import os
 import types
 
 import torch
@@ -47,6 +49,15 @@ def map_text(postprocess, hyp = (), ref = ()):
 def join(ref = (), hyp = ()):
 	"""transcripts.join (transcripts.py:82-83)."""
 	return ' '.join(filter(bool, [t.get('ref', '').strip() for t in ref] + [t.get('hyp', '').strip() for t in hyp]))
+
+
+def _hotwords_of(args):
+	"""args.hotwords: None, a list of phrases, or the path of a text file with one phrase per line."""
+	hot = getattr(args, 'hotwords', None)
+	if isinstance(hot, (str, os.PathLike)):
+		from . import hotwords
+		hot = hotwords.read_phrases(hot)
+	return hot
 
 
 def setup(args):
@@ -82,7 +93,8 @@ def setup(args):
 			model, *_ = models.data_parallel_and_autocast(model, opt_level = level)
 	if getattr(args, 'decoder', None) == 'BeamSearchDecoder':  # transcribe.py:323-328: --decoder, --beam-width, --decoder-topk, --lm (an ARPA file), --beam-alpha, --beam-beta
 		generator = BeamCTCGenerator(beam_width = args.beam_width, topk = getattr(args, 'decoder_topk', 1), lm_path = getattr(args, 'lm', None),
-		                             beam_alpha = getattr(args, 'beam_alpha', 0), beam_beta = getattr(args, 'beam_beta', 0))
+		                             beam_alpha = getattr(args, 'beam_alpha', 0), beam_beta = getattr(args, 'beam_beta', 0),
+		                             hotwords = _hotwords_of(args), hotword_weight = getattr(args, 'hotword_weight', None))
 	else:
 		generator = GreedyCTCGenerator()
 	return text_pipeline, frontend, model, generator

@@ -176,24 +176,28 @@ class BeamCTCGenerator:
 	of word segments built from that beam's tokens: leading silence tokens are skipped, a new segment starts at every word-start token
 	when time stamps are given, and a token's time is begin + time_stamps[its frame offset].  GPU only: log_probs must be a CUDA tensor
 	(GreedyCTCGenerator also decodes CPU tensors); for the one-hot targets of --align, transcribe_batch uses a GreedyCTCGenerator.
-	beam_width up to 8192 (the reference's default --beam-width 5000 runs the wide kernel: decoders.BeamSearchDecoder)."""
+	beam_width up to 8192 (the reference's default --beam-width 5000 runs the wide kernel: decoders.BeamSearchDecoder).
+	hotwords (a list of phrases) with hotword_weight (required with them, no default) bias the search towards the phrases
+	(decoders.BeamSearchDecoder, convasr_ctc_beam_search_hot); the tokenizer's vocabulary then needs exactly one space."""
 
-	def __init__(self, beam_width = 64, topk = 1, cutoff_top_n = 40, cutoff_prob = 1.0, lm_path = None, beam_alpha = 0, beam_beta = 0):
+	def __init__(self, beam_width = 64, topk = 1, cutoff_top_n = 40, cutoff_prob = 1.0, lm_path = None, beam_alpha = 0, beam_beta = 0, hotwords = None, hotword_weight = None):
 		from . import decoders, lm
 		self.topk = int(topk)
 		kw = dict(beam_width = beam_width, cutoff_top_n = cutoff_top_n, cutoff_prob = cutoff_prob, topk = topk)
-		if lm_path is None:
+		if (hotwords is None) != (hotword_weight is None):
+			raise ValueError('BeamCTCGenerator: hotwords and hotword_weight go together (there is no default weight)')
+		if lm_path is None and hotwords is None:
 			self.decoder = lambda tokenizer: decoders.BeamSearchDecoder(types.SimpleNamespace(blank_idx = tokenizer.eps_id), **kw)
 			self.decoder(types.SimpleNamespace(eps_id = 0))
 			return
-		model = lm_path if isinstance(lm_path, lm.NgramLM) else lm.read_arpa(lm_path)  # (a non-ARPA path raises here, at setup)
+		model = lm_path if lm_path is None or isinstance(lm_path, lm.NgramLM) else lm.read_arpa(lm_path)  # (a non-ARPA path raises here, at setup)
 		decs = {}
 
-		def decoder(tokenizer):  # one decoder (and one set of LM tables) per tokenizer alphabet
+		def decoder(tokenizer):  # one decoder (one set of LM tables, one hot-phrase trie) per tokenizer alphabet
 			labels = ''.join(tokenizer.vocab)
 			if (labels, tokenizer.eps_id) not in decs:
 				decs[labels, tokenizer.eps_id] = decoders.BeamSearchDecoder(types.SimpleNamespace(eps_id = tokenizer.eps_id, idx2char = tokenizer.vocab), lm_path = model,
-				                                                            beam_alpha = beam_alpha, beam_beta = beam_beta, **kw)
+				                                                            beam_alpha = beam_alpha, beam_beta = beam_beta, hotwords = hotwords, hotword_weight = hotword_weight, **kw)
 			return decs[labels, tokenizer.eps_id]
 		self.decoder = decoder
 

@@ -668,6 +668,75 @@ int convasr_ctc_beam_search_lm_wide(const float* log_probs, const int64_t* lengt
                                     const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
                                     int space, int order, int start_state, double alpha, double beta, void* stream);
 
+/* ---- CTC prefix beam search biased towards hot phrases (contextual biasing; this package's own, the reference has none) ---------------
+ * convasr_ctc_beam_search_hot / _lm_hot and their _wide forms are the four searches above with one more term in the score.  Everything
+ * not stated here is as above: candidates, merging, tie keys, top-N / cutoff_prob, fp64 scores, the LM rules, the output layout, the
+ * workspace (no initialisation) and graph capture (the tables are uploaded before the call).  The tables are built on the host by
+ * convasr_amd/hotwords.py (HotWords, which documents their layout); the C side keeps no state.
+ *   Labels: as for the LM: one lowercased character per class, exactly one space class s, s != blank, C <= 256.
+ *   Phrases: lowercased, stripped, inner whitespace runs reduced to one space; a non-empty sequence of classes, none the blank, that
+ *   neither begins nor ends with s.
+ *   Trie: all phrases form one trie.  Node 0 is the root; a node is terminal when a phrase ends there; the children of a node are stored
+ *   contiguously in class order; hot_mask (n_nodes, MW) has bit c of node u set when u has a child by class c, MW = ceil(C / 32);
+ *   hot_child (n_nodes,) is the index of u's first child, so child(u, c) = hot_child[u] + (set bits of u's mask below c); hot_term
+ *   (n_nodes,) is 1 for a terminal node.
+ *   Weight: one w >= 0, a double, in natural-log units per matched label.
+ *   State: every prefix l has a hot state (u, k): u a trie node or DEAD, k the number of labels matched since the last completed phrase
+ *   (the pending count).  The empty prefix has (root, 0).
+ *   Creating l + c (an extension, not the stay of a repeated last token):
+ *     match: u != DEAD and v = child(u, c) exists: delta = +w; the new state is (v, 0) if v is terminal, else (v, k + 1).
+ *     mismatch at a word start: no such child, last(l) == s and v = child(root, c) exists: delta = -(w * k) + w; the new state is (v, 0)
+ *     if v is terminal, else (v, 1).
+ *     mismatch: anything else: delta = -(w * k); the new state is (root, 0) if c == s, else (DEAD, 0).
+ *   So a match can start only at the beginning of the utterance or right after a space; a completed phrase keeps its bonus and a partial
+ *   match gives all of it back; there are no failure links; the state is a function of the prefix's labels alone, so merged prefixes
+ *   agree on it.
+ *   Fusion: delta(l, c) is added to every contribution to nnb(l + c): the candidate extension's score, and the fold of l_i + last(l_j)
+ *   into a held beam l_j.  The fp64 operations, in this order: ((lp + base) + the LM term if any) + delta, with -(w * k) formed as one
+ *   multiply and one negation (no fused multiply-add).
+ *   End of utterance: the ranking score is lpb + lpnb (+ the LM's F(l)) + F_hot(l), F_hot = -(w * k(l)); the beams are re-ranked by it
+ *   (ties: rank) and log_prob returns it, fp64 on all four entry points.
+ *   With an LM its dictionary constraint still decides which extensions exist; the hot rule only adds to scores.  Every word of every
+ *   phrase must be in V (hotwords.py raises ValueError naming the others).
+ *   w = 0 or a trie of the root alone: the search above.  Tokens, offsets and lengths are identical; with an LM the scores are identical
+ *   bit for bit, without one log_prob is the fp64 value that convasr_ctc_beam_search rounds to fp32.
+ * Arguments after those of the search above: hot_mask, hot_child, hot_term, n_hot_nodes, hot_mask_words (= MW, checked against C), for the
+ * LM-free forms the space class s (the LM forms use the LM's), and w.
+ * Envelope, checked before any launch: that of the search above, plus C <= 256, n_hot_nodes >= 1, hot_mask_words == ceil(C / 32), s in
+ * [0, C) and s != blank, w finite and >= 0.  A child index outside [0, n_hot_nodes) makes the state DEAD and no walk over the tables loops,
+ * so tables that break the builder's invariants give wrong words, not a fault.  The LDS forms keep 8 + 4 * MW more bytes per beam (and MW
+ * words for the root's mask) and stay within 160 KiB: without an LM W = 1024 fits for every C <= 256 and N <= 128; with an LM W = 1024 fits
+ * for C <= 96 (C = 38 among them) at N <= 64, and the largest W is 1003 at C = 128 (N <= 64), 948 at C = 160 (N <= 64), 814 at C = 256
+ * (N <= 64) and 778 at C = 256, N = 128.  A width the LDS form refuses runs in the wide form (W <= 8192), whose workspace per utterance
+ * has A = up16(60 * W + 4 * W * MW) without an LM and up16(76 * W + 8 * W * MW) with one.  Outside the envelope CONVASR_EINVAL /
+ * CONVASR_EUNSUPPORTED. */
+int64_t convasr_ctc_beam_search_hot_workspace_bytes(int B, int T, int C, int W, int N, int topk);
+int convasr_ctc_beam_search_hot(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                                const uint32_t* hot_mask, const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes, int hot_mask_words,
+                                int space, double weight, void* stream);
+int64_t convasr_ctc_beam_search_hot_wide_workspace_bytes(int B, int T, int C, int W, int N, int topk);
+int convasr_ctc_beam_search_hot_wide(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                     double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                                     const uint32_t* hot_mask, const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes,
+                                     int hot_mask_words, int space, double weight, void* stream);
+int64_t convasr_ctc_beam_search_lm_hot_workspace_bytes(int B, int T, int C, int W, int N, int topk);
+int convasr_ctc_beam_search_lm_hot(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                   double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob, int topk,
+                                   const uint32_t* node_mask, const int32_t* node_child, const int32_t* node_word, int n_nodes,
+                                   const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
+                                   int space, int order, int start_state, double alpha, double beta, const uint32_t* hot_mask,
+                                   const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes, int hot_mask_words, double weight,
+                                   void* stream);
+int64_t convasr_ctc_beam_search_lm_hot_wide_workspace_bytes(int B, int T, int C, int W, int N, int topk);
+int convasr_ctc_beam_search_lm_hot_wide(const float* log_probs, const int64_t* lengths, int64_t* tokens, int32_t* offsets, int64_t* out_lengths,
+                                        double* log_prob, void* workspace, int B, int T, int C, int blank, int W, int N, float cutoff_prob,
+                                        int topk, const uint32_t* node_mask, const int32_t* node_child, const int32_t* node_word, int n_nodes,
+                                        const double* ent_pb, const int32_t* ent_sl, int n_ent, const int32_t* slots, int n_slots,
+                                        int space, int order, int start_state, double alpha, double beta, const uint32_t* hot_mask,
+                                        const int32_t* hot_child, const int32_t* hot_term, int n_hot_nodes, int hot_mask_words, double weight,
+                                        void* stream);
+
 /* ---- Validation metrics: metrics.py:409-421 (cer / wer, the edit distances train.py:evaluate_model scores every validation utterance
  * with), transcript_generators.py:8-93 (the greedy collapse of GreedyCTCGenerator.generate) -------------------------------------------- */
 
