@@ -142,6 +142,9 @@ _SIGNATURES = dict(
 	convasr_frame_uncertainty_row_classes = (c_int, []),
 	convasr_frame_uncertainty = (c_int, [c_p] * 8 + [c_int] * 4 + [c_p]),
 	convasr_span_uncertainty = (c_int, [c_p] * 12 + [c_i64, c_p, c_p, c_int] + [c_p] * 6 + [c_i64, c_int, c_int, c_int, c_f32, c_p]),
+	convasr_topk_frames_max_k = (c_int, []),
+	convasr_topk_frames = (c_int, [c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_distill_kl = (c_int, [c_p, c_p, c_int, c_p, c_int, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_f32, c_p]),
 	convasr_ctc_keyword_search_max_labels = (c_int, []),
 	convasr_ctc_keyword_search_phrases_per_block = (c_int, []),
 	convasr_ctc_keyword_search_staged_classes = (c_int, []),
@@ -194,6 +197,7 @@ _SIGNATURES = dict(
 	convasr_spec_augment_tile = (c_int, []),
 	convasr_spec_augment = (c_int, [c_p, c_p, c_p, c_p, c_u64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_u32, c_int, c_f32, c_p, c_p, c_p, c_p]),
 )
+INDEX_U8, INDEX_I16, INDEX_I32, TOPK_MAX_K = 0, 1, 2, 32  # include/convasr_hip.h: CONVASR_INDEX_* (convasr_topk_frames / convasr_distill_kl), CONVASR_TOPK_MAX_K
 VAD_MAX_CHANNELS, VAD_MAX_LEN, VAD_MAX_FRAME = 8, 1 << 28, 65536  # include/convasr_hip.h: the envelope of convasr_frame_peak and its neighbours
 SLIDE_ABS, SLIDE_NEG = 1, 2  # include/convasr_hip.h: CONVASR_SLIDE_ABS / CONVASR_SLIDE_NEG
 DIAR_MAX_LEN, DIAR_MAX_KERNEL, RLE_MAX_LEN, SPEAKER_MAX_PERMS = 1 << 28, 16384, 1 << 30, 8  # CONVASR_DIAR_MAX_LEN, ..._MAX_KERNEL, CONVASR_RLE_MAX_LEN, CONVASR_SPEAKER_MAX_PERMS

@@ -1057,3 +1057,40 @@ class CtcLossFunction(torch.autograd.Function):
 
 def ctc_loss(log_probs, targets, olen, ylen, blank, norm = None):
 	return CtcLossFunction.apply(log_probs, targets, olen, ylen, blank, norm)
+
+
+def _teacher_pair(teacher):
+	"""(values, indices) of logical shape (B, k, T) from a models.sparse_topk dict over the class dimension of (B, C, T) logits, or from
+	such a pair itself."""
+	if isinstance(teacher, dict):
+		if teacher['dim'] not in (1, -2) or not teacher['largest'] or len(teacher['shape']) != 3:
+			raise ValueError(f"distill_loss: the teacher must hold the largest logits along the class dimension of (B, C, T) logits, got dim {teacher['dim']}, largest {teacher['largest']}, shape {tuple(teacher['shape'])}")
+		return teacher['values'], teacher['indices']
+	values, indices = teacher
+	return values, indices
+
+
+class DistillFunction(torch.autograd.Function):
+	"""tau^2 * KL(softmax(teacher's kept logits / tau) || softmax(logits / tau)) summed over each utterance's frames (ops.distill_kl): the
+	one launch produces the per-utterance loss and d kd / d logits; backward is a per-utterance scaling, as in CtcLossFunction."""
+
+	@staticmethod
+	def forward(ctx, logits, values, indices, olen, temperature):
+		lg = ops.as_cl(logits, torch.float32)
+		need = logits.requires_grad
+		kd, grad = ops.distill_kl(lg, values, indices, olen, temperature, need_grad = need)
+		if need:
+			ctx.save_for_backward(grad)
+		return kd
+
+	@staticmethod
+	def backward(ctx, g):
+		grad, = ctx.saved_tensors
+		return ops.scale_rows(grad, g), None, None, None, None
+
+
+def distill_loss(logits, teacher, olen, temperature = 1.0):
+	"""kd (B,): the frame-level distillation term of (B, C, T) student logits against a teacher's top-k logits -- a models.sparse_topk dict
+	(dim = 1) or a (values, indices) pair of logical shape (B, k, T) -- over the first olen[b] frames of every utterance."""
+	values, indices = _teacher_pair(teacher)
+	return DistillFunction.apply(logits, values, indices, olen, float(temperature))

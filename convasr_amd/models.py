@@ -89,6 +89,31 @@ def unpad(x, lens):
 	return [e[..., :l] for e, l in zip(x, lens)]
 
 
+def sparse_topk(x, k, dim = -1, largest = True, indices_dtype = None, values_dtype = None, fill_value = 0.0):
+	"""models.py:788-800: the k largest (smallest) entries of x along dim as a dict -- k, dim, largest, shape, dtype, device, fill_value,
+	indices, values -- that sparse_topk_todense turns back into a dense tensor.  The storage format of a teacher's logits.
+	Device fp32 (B, C, T) logits with dim = 1 / -2, largest and k <= ops.topk_frames_max_k() go through ops.topk_frames (one read; its total
+	order: ties to the lower class); any other call -- CPU tensors included -- is torch.topk and the two casts.  indices_dtype None: int64,
+	as torch.topk gives them (widened after the kernel)."""
+	kernel_index = {None: torch.int32, torch.int64: torch.int32, torch.int32: torch.int32, torch.int16: torch.int16, torch.uint8: torch.uint8}
+	if (x.is_cuda and x.dtype == torch.float32 and x.ndim == 3 and dim in (1, -2) and largest and 1 <= k <= min(x.shape[1], ops.topk_frames_max_k())
+			and values_dtype in (None, torch.float32, torch.float16) and indices_dtype in kernel_index and (indices_dtype != torch.uint8 or x.shape[1] <= 256) and x.shape[0] and x.shape[2]):
+		values, indices = ops.topk_frames(x, k, values_dtype or torch.float32, kernel_index[indices_dtype])
+		if indices_dtype in (None, torch.int64):
+			indices = indices.to(torch.int64)
+	else:
+		top = torch.topk(x, k, dim = dim, largest = largest)
+		values, indices = top.values.to(dtype = values_dtype), top.indices.to(dtype = indices_dtype)
+	return dict(k = k, dim = dim, largest = largest, shape = x.shape, dtype = x.dtype, device = x.device, fill_value = fill_value, indices = indices, values = values)
+
+
+def sparse_topk_todense(saved, device = None):
+	"""models.py:803-809: a tensor of saved['shape'] filled with fill_value, the kept values scattered to their places."""
+	device = device or saved['device']
+	dense = torch.full(saved['shape'], saved['fill_value'], dtype = saved['dtype'], device = device)
+	return dense.scatter_(saved['dim'], saved['indices'].to(device = device, dtype = torch.int64), saved['values'].to(device = device, dtype = saved['dtype']))
+
+
 def compute_capacity(model, scale = 1):
 	return sum(map(torch.numel, model.parameters())) / scale
 

@@ -853,6 +853,67 @@ def frame_uncertainty(log_probs, eps_id = -1, lengths = None):
 	return types.SimpleNamespace(idx = idx, p1 = p1, margin = margin, entropy = ent, entropy_nb = ent_nb, p_eps = p_eps)
 
 
+INDEX_CODES = {torch.uint8: _lib.INDEX_U8, torch.int16: _lib.INDEX_I16, torch.int32: _lib.INDEX_I32}  # include/convasr_hip.h: CONVASR_INDEX_*
+
+
+def topk_frames_max_k():
+	"""The largest k of topk_frames / distill_kl (CONVASR_TOPK_MAX_K)."""
+	return _cached_query('convasr_topk_frames_max_k')
+
+
+def _topk_dtypes(name, values_dtype, indices_dtype):
+	if values_dtype not in (torch.float32, torch.float16):
+		raise _lib.ConvasrHipError(f'{name}: values are float32 or float16, not {values_dtype}')
+	if indices_dtype not in INDEX_CODES:
+		raise _lib.ConvasrHipError(f'{name}: indices are uint8, int16 or int32, not {indices_dtype}')
+	return dtype_code(values_dtype), INDEX_CODES[indices_dtype]
+
+
+def topk_frames(logits, k, values_dtype = torch.float32, indices_dtype = torch.int32):
+	"""The k largest logits of every frame of (B, C, T) logits and their classes, in descending order, in one read (include/convasr_hip.h:
+	convasr_topk_frames has the order: larger first, ties to the lower class, a NaN above every number).  Returns (values, indices) of logical
+	shape (B, k, T) -- permuted views of (B, T, k) memory, as the logits are of (B, T, C).  values_dtype float32 or float16 (the bits of
+	.to(torch.float16)), indices_dtype uint8 (up to 256 classes), int16 or int32.  Outside the envelope it raises ConvasrHipError."""
+	require_cuda(logits)
+	if logits.ndim != 3:
+		raise ValueError(f'topk_frames: (B, C, T) logits expected, got shape {tuple(logits.shape)}')
+	B, C, T = logits.shape
+	vcode, icode = _topk_dtypes('topk_frames', values_dtype, indices_dtype)
+	lg = as_cl(logits, torch.float32)
+	k = int(k)
+	values = torch.empty(B, T, max(k, 0), dtype = values_dtype, device = lg.device)
+	indices = torch.empty(B, T, max(k, 0), dtype = indices_dtype, device = lg.device)
+	call('convasr_topk_frames', ptr(lg), ptr(values), vcode, ptr(indices), icode, B, T, C, k, stream_ptr())
+	return values.permute(0, 2, 1), indices.permute(0, 2, 1)
+
+
+def distill_kl(logits, values, indices, lengths, temperature = 1.0, need_grad = True, per_frame = False):
+	"""tau^2 KL(truncated teacher || student) per utterance, with its gradient, in one pass over the student's (B, C, T) logits
+	(include/convasr_hip.h: convasr_distill_kl has the rule).  values / indices: the teacher's k kept logits of every frame and their classes,
+	logical shape (B, k, T) as topk_frames returns them (float32 or float16; uint8, int16 or int32 -- int64 indices are narrowed to int32 on
+	the way in); lengths (B,): the student's frames per utterance.  Returns (kd (B,) fp32, grad (B, C, T) channels-last fp32 or None[,
+	kd_frames (B, T)]): grad = d kd[b] / d logits, exactly 0 past the lengths.  Outside the envelope it raises ConvasrHipError."""
+	require_cuda(logits, values, indices)
+	if logits.ndim != 3 or values.ndim != 3 or values.shape != indices.shape or values.shape[0] != logits.shape[0] or values.shape[2] != logits.shape[2]:
+		raise ValueError(f'distill_kl: (B, C, T) logits and (B, k, T) teacher values and indices expected, got {tuple(logits.shape)}, {tuple(values.shape)}, {tuple(indices.shape)}')
+	B, C, T = logits.shape
+	k = values.shape[1]
+	lg = as_cl(logits, torch.float32)
+	dev = lg.device
+	if values.dtype not in (torch.float32, torch.float16):
+		values = values.to(torch.float32)
+	if indices.dtype == torch.int64:
+		indices = indices.to(torch.int32)
+	vcode, icode = _topk_dtypes('distill_kl', values.dtype, indices.dtype)
+	values, indices = (t.to(dev).permute(0, 2, 1).contiguous() for t in (values, indices))  # (B, T, k) memory: no copy for topk_frames' own views
+	lengths = _frame_lengths('distill_kl', lengths, B, T, dev)
+	kd = torch.empty(B, dtype = torch.float32, device = dev)
+	frames = torch.empty(B, T, dtype = torch.float32, device = dev)
+	grad = empty_cl(B, C, T, torch.float32, dev) if need_grad else None
+	call('convasr_distill_kl', ptr(lg), ptr(values), vcode, ptr(indices), icode, ptr(lengths), ptr(kd), ptr(frames), ptr(grad), B, T, C, k, float(temperature), stream_ptr())
+	return (kd, grad, frames) if per_frame else (kd, grad)
+
+
 def span_uncertainty(log_probs, stats, utt, begin, end, first = None, tokens = None, frames = None, path = None, eps = 1e-9, frame_map = None):
 	"""Statistics of N spans (words) over frame_uncertainty's arrays (include/convasr_hip.h: convasr_span_uncertainty has the rule).
 	log_probs (B, C, T) and stats = frame_uncertainty(log_probs, ...); utt, begin, end (N,): the utterance and the first and last position

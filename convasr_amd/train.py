@@ -247,7 +247,7 @@ class _NonFinite:
 		return not bool(torch.isfinite(self.t[self.i]))
 
 
-def train_step(model, optimizer, x, xlen, y, ylen, max_norm = 100.0, accumulate_iterations = 1, iteration = 0, world_size = 1, sync_metrics = True, device_gate = True):
+def train_step(model, optimizer, x, xlen, y, ylen, max_norm = 100.0, accumulate_iterations = 1, iteration = 0, world_size = 1, sync_metrics = True, device_gate = True, teacher = None, distill_weight = 0.0, distill_temperature = 1.0, distill_head = 0):
 	"""One iteration of the reference loop, train.py:745-783.
 
 	Returns dict(loss, loss_cur, entropy, grad_norm, skipped) of 0-d device tensors (read them lazily: no forced host sync).
@@ -255,7 +255,13 @@ def train_step(model, optimizer, x, xlen, y, ylen, max_norm = 100.0, accumulate_
 	device_gate is set and there is no gradient accumulation: backward still runs, but the fused optimizer kernel reads the
 	(all-reduced) loss and leaves parameters and momentum untouched when it is not finite -- the same parameters as the
 	reference after the iteration, without draining the GPU in the middle of every step.  With accumulation (or
-	device_gate = False) the gate is the reference's host-side check."""
+	device_gate = False) the gate is the reference's host-side check.
+
+	teacher (a models.sparse_topk dict of a teacher's logits on this batch, or a (values, indices) pair: distill.teacher_from_model,
+	distill.TeacherStore.batch): the step minimises the CTC loss as above + distill_weight * mean_b(kd[b]) / accumulate_iterations, with
+	kd = functional.distill_loss(logits[distill_head], teacher, olen[distill_head], distill_temperature); one backward over both loss
+	vectors.  The result gains `distill`, the mean of kd (0-d, on the device), and both gates read non-finite when either mean is.
+	Without a teacher the step launches exactly what it launched before the argument existed."""
 	Fn.begin_step(x.device)  # the device-resident dropout key of this step (one single-thread launch; the same whether the step is launched eagerly or replayed from a graph)
 	out = model(x, xlen, y = y, ylen = ylen)
 	log_probs, olen, loss_vec = out['log_probs'], out['olen'], out['loss']
@@ -283,18 +289,38 @@ def train_step(model, optimizer, x, xlen, y, ylen, max_norm = 100.0, accumulate_
 		skipped = _NonFinite(scalars, 1, engine)
 	loss_cur = scalars[1]
 	res = dict(loss = scalars[0], loss_cur = loss_cur, entropy = scalars[2], grad_norm = None, skipped = skipped)
+	gate_source = scalars
+	losses, seeds = [loss_vec], [grad_loss_vec]
+	if teacher is not None:
+		kd = Fn.distill_loss(out['logits'][distill_head], teacher, olen[distill_head], distill_temperature)
+		distill = kd.detach().mean()
+		if reduce_metrics:
+			distill = distill / ranks
+			torch.distributed.all_reduce(distill, op = torch.distributed.ReduceOp.SUM, group = group)
+			if engine is not None:
+				engine.join_comm_stream()  # the CTC means' all-reduce runs on the engine's stream: the gate below reads its result
+		res['distill'] = distill
+		# one number that is non-finite when either mean is: what the fused optimizer step and the host-side check read (0 * inf = NaN)
+		gate_source = torch.stack([scalars[0], scalars[1] + distill * 0.0])
+		res['skipped'] = skipped = _NonFinite(gate_source, 1, engine) if reduce_metrics else skipped | ~torch.isfinite(distill)
+		if distill_weight != 0.0:
+			seed = float(distill_weight) / (kd.shape[0] * accumulate_iterations)
+			kd_seed = torch.full_like(kd, seed) if scaler is None else scaler.current[0] * seed * torch.ones_like(kd)
+			losses.append(kd)
+			seeds.append(kd_seed)
 	gate = None
 	if device_gate and accumulate_iterations == 1 and hasattr(optimizer, 'flat'):
-		gate = scalars[1:2]
+		gate = gate_source[1:2]
 	elif bool(skipped):
 		res['skipped'] = True
 		return res
 	last_of_group = iteration % accumulate_iterations == 0
+	backward = (lambda: loss_vec.backward(grad_loss_vec)) if len(losses) == 1 else (lambda: torch.autograd.backward(losses, seeds))
 	if engine is not None and not last_of_group:
 		with engine.no_sync():
-			loss_vec.backward(grad_loss_vec)
+			backward()
 	else:
-		loss_vec.backward(grad_loss_vec)
+		backward()
 	Fn.join_side_streams()  # weight gradients computed on the side stream are final from here on
 	if last_of_group:
 		if engine is not None:
@@ -503,15 +529,22 @@ class GraphedTrainStep:
 		return g['res']
 
 
-def train_epoch(model, optimizer, batches, sampler = None, scheduler = None, iteration = 0, world_size = 1, max_norm = 100.0, accumulate_iterations = 1, max_iterations = None, on_step = None, graphs = None):
+def train_epoch(model, optimizer, batches, sampler = None, scheduler = None, iteration = 0, world_size = 1, max_norm = 100.0, accumulate_iterations = 1, max_iterations = None, on_step = None, graphs = None, teacher_fn = None, distill_weight = 0.0, distill_temperature = 1.0, distill_head = 0):
 	"""The body of the reference's epoch loop (train.py:739-808) over an iterable of (meta, s, x, xlen, y, ylen) batches whose
 	tensors are already on the device (convasr_amd.datasets.gpu_batches): train_step, scheduler.step(iteration) after every
 	optimizer step (train.py:783), iteration += 1, sampler.batch_idx += world_size (train.py:807-808, what makes a resumed
 	epoch start where it stopped).  Metrics stay on the device; on_step(iteration, batch, result) may read them.
+	teacher_fn(batch) -> the teacher of train_step for the batch (meta, s, x, xlen, y, ylen), with distill_weight / distill_temperature /
+	distill_head handed on; not together with graphs (GraphedTrainStep does not distil): ValueError.
 	Returns the next iteration number."""
+	if graphs is not None and teacher_fn is not None:
+		raise ValueError('train_epoch: graphs and teacher_fn do not combine (GraphedTrainStep does not capture the distillation term)')
 	for meta, s, x, xlen, y, ylen in batches:
 		if graphs is not None and accumulate_iterations == 1 and world_size == 1:
 			res = graphs(x, xlen, y, ylen, iteration = iteration)  # a GraphedTrainStep(model, optimizer, max_norm): replayed per batch shape
+		elif teacher_fn is not None:
+			res = train_step(model, optimizer, x, xlen, y, ylen, max_norm = max_norm, accumulate_iterations = accumulate_iterations, iteration = iteration, world_size = world_size, sync_metrics = world_size > 1,
+				teacher = teacher_fn((meta, s, x, xlen, y, ylen)), distill_weight = distill_weight, distill_temperature = distill_temperature, distill_head = distill_head)
 		else:
 			res = train_step(model, optimizer, x, xlen, y, ylen, max_norm = max_norm, accumulate_iterations = accumulate_iterations, iteration = iteration, world_size = world_size, sync_metrics = world_size > 1)
 		# train.py:769-783: the scheduler steps only inside the not-skipped branch.  Where the host knows the verdict (a host-side gate
@@ -536,7 +569,7 @@ def _finite_mean(values):
 	return sum(vals) / len(vals) if vals else -1.0
 
 
-def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_space = 10, return_text = False, error_analyzer = None):
+def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_space = 10, return_text = False, error_analyzer = None, logits_topk = None, logits_dtype = torch.float16):
 	"""One validation set through the reference's apply_model + evaluate_model (train.py:119-300), for the first target head.
 
 	batches yields (meta, s, x, xlen, y, ylen) with the tensors on the device, as for train_epoch.  Per batch, under no_grad with the model
@@ -562,10 +595,17 @@ def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_sp
 	tokens ride in the same single copy) go through error_analyzer.analyze_batch(detailed = True) -- the reference's validation analysis
 	(train.py:239-300 there: alignment, word error tags, wordwise / filtered / pseudo / vocabness metrics per config), a constant number of
 	launches for the whole set.  The result gains `analysis`, error_analyzer.aggregate of the per-utterance dicts, and
-	utterances['analysis'], those dicts; with return_text also `ref`, the decoded targets.  Without one the result is what it was."""
+	utterances['analysis'], those dicts; with return_text also `ref`, the decoded targets.  Without one the result is what it was.
+
+	logits_topk = k (the reference's --logits / --logits-topk): utterances['logits'] is a list of per-utterance dicts, in batch order, each
+	with `values` (k, olen_b) in logits_dtype and `indices` (k, olen_b) (uint8 up to 256 classes, else int16): the k largest logits of
+	every frame of the utterance's own olen_b frames (ops.topk_frames on the first head's logits; the padding is cut on the device, the
+	reference's unpad) -- what distill.TeacherStore.add_utterances takes.  They reach the host in one more copy at the end.  Without it the
+	result is what it was."""
 	from . import metrics
 	training, drop_offset = model.training, Fn._DropoutState.offset
 	cols, hyp_tokens, ref_tokens, n_batches = [], [], [], 0
+	top_values, top_indices, top_olen = [], [], []
 	model.eval()
 	try:
 		with torch.no_grad():
@@ -589,6 +629,13 @@ def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_sp
 					hyp_tokens.append((tokens[:, 0], lengths[:, 0]))
 				if error_analyzer is not None:
 					ref_tokens.append((y[:, 0], ylen[:, 0].to(torch.int64)))
+				if logits_topk is not None:
+					lg = out['logits'][0]
+					top = M.sparse_topk(lg.float(), logits_topk, dim = 1, indices_dtype = torch.uint8 if lg.shape[1] <= 256 else torch.int16, values_dtype = logits_dtype)
+					keep = torch.arange(lg.shape[2], device = lg.device).unsqueeze(0) < olen.unsqueeze(1)  # (B, T): the utterance's own frames
+					top_values.append(top['values'].permute(0, 2, 1)[keep])  # (sum olen, k), utterance after utterance
+					top_indices.append(top['indices'].permute(0, 2, 1)[keep])
+					top_olen.append(olen)
 				n_batches += 1
 			if not n_batches:
 				raise ValueError('evaluate_model: no batches')
@@ -597,7 +644,11 @@ def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_sp
 			parts = [table.contiguous().view(torch.int64).flatten()]
 			for t, l in hyp_tokens + ref_tokens:
 				parts += [l, t.flatten()]
+			if logits_topk is not None:
+				parts.append(torch.cat(top_olen).to(torch.int64))
 			host = torch.cat(parts).cpu()
+			if logits_topk is not None:
+				top_values, top_indices = torch.cat(top_values).cpu(), torch.cat(top_indices).cpu()
 	finally:
 		model.train(training)
 		Fn._DropoutState.offset = drop_offset
@@ -608,6 +659,9 @@ def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_sp
 	utt['loss'], utt['entropy'], utt['uncertainty'] = utt['loss'].float(), utt['entropy'].float(), utt['uncertainty'].float()
 	res = {k: _finite_mean(utt[k]) for k in names if k != 'uncertainty'}
 	res['utterances'] = utt
+	if logits_topk is not None:
+		counts = host[-table.shape[1]:].tolist()
+		utt['logits'] = [dict(values = v.t(), indices = i.t()) for v, i in zip(top_values.split(counts), top_indices.split(counts))]
 	if return_text or error_analyzer is not None:
 		texts, pos = [], table.numel()
 		for t, l in hyp_tokens + ref_tokens:

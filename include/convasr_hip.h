@@ -865,6 +865,58 @@ int convasr_span_uncertainty(const float* log_probs, const int64_t* idx, const f
                              int Tp, int32_t* n_events_out, float* confidence, float* confidence_min, float* margin_out, float* entropy_out,
                              float* uncertainty, int64_t N, int B, int T, int C, float eps, void* stream);
 
+/* ---- Distillation: the k largest logits of every frame (models.py:788-809 sparse_topk / sparse_topk_todense, the storage format behind
+ * train.py --logits / --logits-topk) and the frame-level KL term of a student against such a teacher ---------------------------------- */
+
+/* The k largest logits of every frame of channels-last fp32 logits (B, T, C) and their classes, in descending order, in ONE read.
+ * Order: a strict total order on (value, class) pairs.  A larger value comes first; equal values (-0.0 == 0.0 included) go lower class
+ *   first; a NaN ranks above every number (torch.topk's rule) and among NaNs the lower class comes first.  Entry j of a frame is the j-th
+ *   pair of that order: the result does not depend on the mapping, and two runs are bit-equal.
+ * values (B, T, k): fp32 (CONVASR_F32; the logit's own bits, the sign of a zero included) or fp16 (CONVASR_F16: round-to-nearest-even,
+ *   +-inf beyond 65504 -- the bits of tensor.to(torch.float16)).  indices (B, T, k): CONVASR_INDEX_U8 (uint8), CONVASR_INDEX_I16 (int16) or
+ *   CONVASR_INDEX_I32 (int32).
+ * Mapping: C <= convasr_frame_uncertainty_row_classes() one thread per frame over rows staged through LDS; above it one wave per frame
+ * (csrc/distill.hip).  The logits become unsigned keys in LDS whose integer order is the value order; k rounds of "take the largest key
+ * left, lowest class first": k * C integer compares a frame.
+ * One launch, no workspace, no memset or copy, no atomics: the call can be captured into a graph.  Envelope, checked before any launch:
+ * B >= 1, T >= 1, B * T < 2^31, 2 <= C <= CONVASR_UNCERTAINTY_MAX_CLASSES, 1 <= k <= min(C, CONVASR_TOPK_MAX_K), a value and an index
+ * type of the lists above, C <= 256 with uint8 indices, no NULL pointer; outside it CONVASR_EINVAL with a message and nothing written. */
+#define CONVASR_TOPK_MAX_K 32
+#define CONVASR_INDEX_U8 0
+#define CONVASR_INDEX_I16 1
+#define CONVASR_INDEX_I32 2
+int convasr_topk_frames_max_k(void);
+int convasr_topk_frames(const float* logits, void* values, int values_dtype, void* indices, int indices_dtype, int B, int T, int C, int k,
+                        void* stream);
+
+/* KL of a truncated teacher against a student, per frame and per utterance, with the gradient, in one pass over the student's logits.
+ * Inputs: logits (B, T, C) channels-last fp32 (the student); values / indices (B, T, k) as convasr_topk_frames writes them (the teacher's
+ * k kept logits of every frame and their classes, any order); lengths (B,) int64, n_b = clamp(lengths[b], 0, T); a temperature tau > 0.
+ * Per frame t < n_b, in fp32, with it = 1 / tau rounded once:
+ *   s_c = z_c * it over all C classes, m = max_c s_c, S = sum_c expf(s_c - m):         q = softmax(z / tau), log q_c = s_c - m - logf(S)
+ *   u_j = v_j * it over the k kept logits, mu = max_j u_j, Sp = sum_j expf(u_j - mu):   p = softmax(v / tau) over the kept classes ONLY --
+ *     the truncated teacher, renormalised; a class that was not kept carries no mass
+ *   KL_t = sum_j p_j (log p_j - log q[idx_j]) = (sum_j expf(u_j - mu) ((u_j - mu) - (s_idx_j - m))) / Sp - (logf(Sp) - logf(S))
+ *   (both softmaxes subtract their maximum; the differences are formed before they are weighted, so a student equal to the teacher gives 0
+ *   up to the rounding of the two logf).
+ * Outputs:
+ *   kd_frames (B, T) fp32, always written: tau^2 KL_t, and 0 at the frames t >= n_b.
+ *   kd (B,) fp32 or NULL: the sum of kd_frames[b, t] over t < n_b -- a second small launch, one workgroup per utterance, thread i adds the
+ *     frames i, i + 256, ... in fp64, a xor butterfly per wave, the four waves in order, one rounding to fp32.  n_b == 0 gives exactly 0.
+ *   grad (B, T, C) fp32 or NULL: d kd[b] / d z = tau (q - p scattered to its classes); exactly 0 at the frames t >= n_b.  A class that the
+ *     teacher names twice loses both shares, subtracted in teacher order.
+ * A teacher index outside [0, C) makes that frame's kd_frames entry and gradient row NaN (and so kd[b]): loud, and no other frame changes.
+ * Non-finite teacher values are OUTSIDE the envelope and not looked for (an inf or NaN among a frame's kept logits gives a NaN or a
+ * meaningless KL for that frame); a NaN student logit gives NaN for its frame.
+ * Sums run in a fixed order -- classes in index order per thread (row mapping), or per-lane partials over c = lane, lane + 64, ... and a
+ * xor butterfly (wave mapping); the teacher's entries in their order, or one per lane and a butterfly.  No atomics; two runs are bit-equal.
+ * Mapping: as convasr_topk_frames; the row mapping writes the gradient over the staged rows in LDS and stores the tile coalesced.
+ * Two launches (one without kd), no workspace beyond kd_frames, no memset or copy: the call can be captured into a graph.  Envelope,
+ * checked before any launch: that of convasr_topk_frames, and 0 < tau < inf; logits, values, indices, lengths and kd_frames not NULL;
+ * outside it CONVASR_EINVAL. */
+int convasr_distill_kl(const float* logits, const void* values, int values_dtype, const void* indices, int indices_dtype,
+                       const int64_t* lengths, float* kd, float* kd_frames, float* grad, int B, int T, int C, int k, float tau, void* stream);
+
 /* ---- Keyword search: where in an utterance is a phrase said, and how sure is the model.  The project's own detector (the reference has
  * none): unpinned against any outside keyword spotter ------------------------------------------------------------------------------------- */
 
