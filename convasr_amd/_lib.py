@@ -194,6 +194,11 @@ _SIGNATURES = dict(
 	convasr_augment_params = (c_int, [c_p, c_p, c_p, c_int, c_i64, c_u64, c_i64, ctypes.POINTER(c_u64), c_int, c_u32, c_int, c_u32, c_i64, c_i64, c_int, c_u32, c_p, c_p, c_p]),
 	convasr_augment_waveform = (c_int, [c_p, c_int, c_int, c_i64, c_p, c_p, c_int, c_int, c_p, c_int, c_p, c_i64, c_i64, c_p, c_p, c_p]),
 	convasr_augment_mix = (c_int, [c_p, c_int, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_int, c_p, c_p, c_p]),
+	convasr_augment_reverb_block = (c_int, []),
+	convasr_augment_reverb_direct = (c_int, []),
+	convasr_augment_reverb_workspace_bytes = (c_i64, [c_int, c_i64, c_i64]),
+	convasr_augment_reverb_params = (c_int, [c_p, c_int, c_u64, c_i64, c_i64, c_u32, c_p, c_p]),
+	convasr_augment_reverb = (c_int, [c_p, c_int, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p]),
 	convasr_spec_augment_tile = (c_int, []),
 	convasr_spec_augment = (c_int, [c_p, c_p, c_p, c_p, c_u64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_u32, c_int, c_f32, c_p, c_p, c_p, c_p]),
 )

@@ -1,5 +1,6 @@
 // Training-time augmentation of a collated batch on the GPU: speed perturbation, gain and noise mixing on the waveforms (convasr_augment_params,
-// convasr_augment_waveform, convasr_augment_mix) and SpecAugment on the log-mel features (convasr_spec_augment).  The rules live in
+// convasr_augment_waveform, convasr_augment_mix), room reverberation between gain and noise (convasr_augment_reverb_params,
+// convasr_augment_reverb: the last section of this file) and SpecAugment on the log-mel features (convasr_spec_augment).  The rules live in
 // include/convasr_hip.h; this is the project's own augmentation, unpinned against any outside library.
 //
 // Every random decision is word 0 of one Philox4x32-10 block: counter = (key low word, key high word, epoch, purpose << 16 | index), Philox key =
@@ -403,5 +404,251 @@ extern "C" int convasr_spec_augment(const float* x, const float* xlen, const int
 	hipLaunchKernelGGL(spec_augment_kernel, dim3((unsigned)split, (unsigned)B), dim3(SPEC_THREADS), 0, (hipStream_t)stream, x, xlen, keys, epoch, seed, F, T, freq_masks, freq_width, time_masks,
 	                   time_width, time_fraction_q24, fill_mean, fill_value, out, fill_out, masks_out);
 	CONVASR_CHECK_LAUNCH("spec_augment");
+	return 0;
+}
+
+// ================================================================================================ room reverberation
+//
+// z[n] = sum_k h[k] y[n + d - k] for n < out_len, h one row of a bank of room impulse responses, d the index of its direct path: uniformly
+// partitioned overlap-save convolution.  Blocks of RV_BK outputs, FFTs of RV_N = 2 RV_BK complex points in LDS, the impulse response cut into
+// P = ceil(rir_len / RV_BK) parts.  With y'[n] = y[n + d] (0 outside the utterance), segment j = y'[(j - 1) RV_BK, (j + 1) RV_BK) and H_p the
+// spectrum of part p behind RV_BK zeros, output block m is the upper half of IFFT(sum_p X_(m - p) H_p).  Two real blocks share one complex FFT
+// WITHOUT being separated: a convolution with a real h is linear over the complex numbers, so with Mh = ceil(M / 2) of the utterance's M
+// blocks, C_j = FFT(segment j + i segment (j + Mh)) gives IFFT(sum_p C_(m - p) H_p) = block m + i block (m + Mh).
+//
+// An utterance whose shorter operand, min(rir_len, out_len), has at most RV_DIRECT samples skips the FFTs: reverb_finish_kernel sums its at most
+// RV_DIRECT products per sample directly, in ascending tap index.
+//
+// Three launches: reverb_spectra_kernel (one workgroup per C_j, j in [-P, Mh), and per H_p, into the workspace), reverb_apply_kernel (one
+// workgroup per pair of output blocks: the P complex multiply-adds per bin in registers in ascending p, the inverse FFT, the samples) and
+// reverb_finish_kernel (the zeros behind out_len, the bit-exact copy of the utterances without a row, and the two energies in the tile
+// ownership and order of augment_waveform_kernel, so that augment_mix_kernel reads them unchanged).  The FFT is a radix-2 Stockham autosort
+// between two LDS buffers with the caller's twiddle table; nothing depends on B or on the utterance's place.  A twiddle is TWO floats per
+// component, the float64 value rounded to fp32 and the remainder: with one float |w| misses 1 by up to 3e-8, and the few twiddles of the early
+// passes are used so often that a transform loses 3e-8 of its amplitude, a convolution (three transforms) 1e-7 -- more than one fp32 ulp of
+// the noise scale that convasr_augment_mix derives from the energy.  The low parts enter the product's fma chain first, so they are not
+// rounded away.
+#define RV_BK 1024
+#define RV_N (2 * RV_BK)
+#define RV_THREADS 256
+#define RV_PER_LANE (RV_N / RV_THREADS)
+#define RV_MAX_LEN 32768
+#define RV_DIRECT 32  // min(rir_len, out_len) up to here: the at most RV_DIRECT products per sample are summed directly
+enum { AS_REVERB_FIRE = 12, AS_REVERB_ROW = 13 };
+
+__global__ __launch_bounds__(256) void reverb_params_kernel(const int64_t* __restrict__ keys, int B, uint64_t seed, unsigned epoch, int64_t rows, unsigned thr, int64_t* __restrict__ rir_row) {
+	const int b = blockIdx.x * 256 + threadIdx.x;
+	if (b >= B) return;
+	const uint64_t key = (uint64_t)keys[b];
+	int64_t row = -1;
+	if (aug_fires(aug_draw(seed, epoch, key, AS_REVERB_FIRE, 0), thr)) row = aug_uint(aug_draw(seed, epoch, key, AS_REVERB_ROW, 0), rows - 1);
+	rir_row[b] = row;
+}
+
+// what one utterance convolves with, every field forced into the range the kernels index with; row < 0: nothing
+struct RvRow { int64_t row, len, delay, out_len; int P, Mh; bool direct; };
+__device__ __forceinline__ RvRow rv_row(const int64_t* __restrict__ params, const int64_t* __restrict__ rir_row, const int64_t* __restrict__ rir_len, const int64_t* __restrict__ rir_delay, int b,
+                                        int64_t T, int64_t R, int64_t Lmax, int pmax) {
+	RvRow r;
+	r.out_len = params[(int64_t)b * AUG_PARAMS + AP_OUT_LEN];
+	r.out_len = r.out_len < 0 ? 0 : (r.out_len > T ? T : r.out_len);
+	r.row = rir_row[b]; r.len = 0; r.delay = 0; r.P = 0;
+	if (r.row < 0 || r.row >= R) r.row = -1;
+	else {
+		r.len = rir_len[r.row]; r.delay = rir_delay[r.row];
+		if (r.len < 1 || r.len > Lmax || r.len > (int64_t)pmax * RV_BK || r.delay < 0 || r.delay >= r.len) r.row = -1;
+		else r.P = (int)((r.len + RV_BK - 1) / RV_BK);
+	}
+	r.Mh = (int)(((r.out_len + RV_BK - 1) / RV_BK + 1) / 2);
+	r.direct = r.row >= 0 && (r.len < r.out_len ? r.len : r.out_len) <= RV_DIRECT;
+	return r;
+}
+
+// RV_N points from `a` (scratch `b`), forward or inverse (unscaled): eleven radix-2 Stockham passes, every lane four butterflies per pass.
+// Returns the buffer that holds the result in natural order; the caller's fill of `a` needs no barrier of its own.
+__device__ __forceinline__ float2* rv_fft(float2* a, float2* b, const float4* tw, bool inverse) {
+	const int tid = threadIdx.x;
+	for (int ns = 1; ns < RV_N; ns <<= 1) {
+		__syncthreads();
+		const int shift = RV_BK / ns;  // W_(2 ns)^k = tw[k * RV_BK / ns]
+#pragma unroll
+		for (int q = 0; q < RV_BK / RV_THREADS; ++q) {
+			const int j = tid + q * RV_THREADS, k = j & (ns - 1);
+			const float4 w = tw[k * shift];  // (cos hi, -sin hi, cos lo, -sin lo)
+			const float sh = inverse ? -w.y : w.y, sl = inverse ? -w.w : w.w;
+			const float2 u0 = a[j], u1 = a[j + RV_BK];
+			const float tx = fmaf(u1.x, w.x, fmaf(-u1.y, sh, fmaf(u1.x, w.z, -u1.y * sl))), ty = fmaf(u1.x, sh, fmaf(u1.y, w.x, fmaf(u1.x, sl, u1.y * w.z)));
+			const int j0 = (j << 1) - k;
+			b[j0] = make_float2(u0.x + tx, u0.y + ty);
+			b[j0 + ns] = make_float2(u0.x - tx, u0.y - ty);
+		}
+		float2* t = a; a = b; b = t;
+	}
+	__syncthreads();
+	return a;
+}
+
+__global__ __launch_bounds__(RV_THREADS) void reverb_spectra_kernel(const float* __restrict__ y, const int64_t* __restrict__ params, const int64_t* __restrict__ rir_row, const float* __restrict__ rir,
+                                                                    const int64_t* __restrict__ rir_len, const int64_t* __restrict__ rir_delay, int64_t R, int64_t Lmax, int pmax, int mh_max,
+                                                                    const float4* __restrict__ twiddles, float2* __restrict__ ws, int64_t T) {
+	__shared__ float2 buf[2][RV_N];
+	__shared__ float4 tw[RV_BK];
+	const int tid = threadIdx.x, b = blockIdx.y, s = blockIdx.x, nsig = mh_max + pmax;
+	const RvRow r = rv_row(params, rir_row, rir_len, rir_delay, b, T, R, Lmax, pmax);
+	if (r.row < 0 || r.direct) return;  // (uniform over the workgroup, like the one below; out_len == 0 is direct)
+	if (s < nsig ? s >= r.Mh + r.P : s - nsig >= r.P) return;
+	for (int i = tid; i < RV_BK; i += RV_THREADS) tw[i] = twiddles[i];
+	if (s < nsig) {  // C_j, j = s - P: segment j in the real parts, segment j + Mh in the imaginary ones
+		const float* yrow = y + (int64_t)b * T;
+		const int64_t n0 = ((int64_t)(s - r.P) - 1) * RV_BK + r.delay, n1 = n0 + (int64_t)r.Mh * RV_BK;
+		for (int t = tid; t < RV_N; t += RV_THREADS) {
+			const int64_t i0 = n0 + t, i1 = n1 + t;
+			buf[0][t] = make_float2(i0 >= 0 && i0 < r.out_len ? yrow[i0] : 0.f, i1 >= 0 && i1 < r.out_len ? yrow[i1] : 0.f);
+		}
+	} else {  // H_p: part p of the impulse response behind RV_BK zeros
+		const float* h = rir + r.row * Lmax;
+		const int64_t k0 = (int64_t)(s - nsig) * RV_BK;
+		for (int t = tid; t < RV_N; t += RV_THREADS) buf[0][t] = make_float2(t < RV_BK && k0 + t < r.len ? h[k0 + t] : 0.f, 0.f);
+	}
+	const float2* res = rv_fft(buf[0], buf[1], tw, false);
+	float2* dst = ws + ((int64_t)b * (nsig + pmax) + s) * RV_N;
+	for (int t = tid; t < RV_N; t += RV_THREADS) dst[t] = res[t];
+}
+
+__global__ __launch_bounds__(RV_THREADS) void reverb_apply_kernel(const int64_t* __restrict__ params, const int64_t* __restrict__ rir_row, const int64_t* __restrict__ rir_len,
+                                                                  const int64_t* __restrict__ rir_delay, int64_t R, int64_t Lmax, int pmax, int mh_max, const float4* __restrict__ twiddles,
+                                                                  const float2* __restrict__ ws, float* __restrict__ out, int64_t T) {
+	__shared__ float2 buf[2][RV_N];
+	__shared__ float4 tw[RV_BK];
+	const int tid = threadIdx.x, b = blockIdx.y, m = blockIdx.x, nsig = mh_max + pmax;
+	const RvRow r = rv_row(params, rir_row, rir_len, rir_delay, b, T, R, Lmax, pmax);
+	if (r.row < 0 || r.direct || m >= r.Mh) return;  // (uniform over the workgroup)
+	for (int i = tid; i < RV_BK; i += RV_THREADS) tw[i] = twiddles[i];
+	const float2* wb = ws + (int64_t)b * (nsig + pmax) * RV_N;
+	float2 acc[RV_PER_LANE];
+#pragma unroll
+	for (int q = 0; q < RV_PER_LANE; ++q) acc[q] = make_float2(0.f, 0.f);
+	for (int p = 0; p < r.P; ++p) {  // slot of C_(m - p) = m - p + P in [1, Mh + P), slot of H_p = nsig + p: both written by reverb_spectra_kernel
+		const float2* X = wb + (int64_t)(m - p + r.P) * RV_N;
+		const float2* H = wb + (int64_t)(nsig + p) * RV_N;
+#pragma unroll
+		for (int q = 0; q < RV_PER_LANE; ++q) {
+			const float2 a = X[tid + q * RV_THREADS], h = H[tid + q * RV_THREADS];
+			acc[q].x = fmaf(-a.y, h.y, fmaf(a.x, h.x, acc[q].x));
+			acc[q].y = fmaf(a.y, h.x, fmaf(a.x, h.y, acc[q].y));
+		}
+	}
+#pragma unroll
+	for (int q = 0; q < RV_PER_LANE; ++q) buf[0][tid + q * RV_THREADS] = acc[q];
+	const float2* res = rv_fft(buf[0], buf[1], tw, true);
+	float* orow = out + (int64_t)b * T;
+	const int64_t n0 = (int64_t)m * RV_BK, n1 = n0 + (int64_t)r.Mh * RV_BK;
+	for (int i = tid; i < RV_BK; i += RV_THREADS) {  // the upper half is free of the circular wrap; 1 / RV_N is a power of two
+		const float2 v = res[RV_BK + i];
+		if (n0 + i < r.out_len) orow[n0 + i] = v.x * (1.0f / RV_N);
+		if (n1 + i < r.out_len) orow[n1 + i] = v.y * (1.0f / RV_N);
+	}
+}
+
+__global__ __launch_bounds__(AUG_THREADS) void reverb_finish_kernel(const float* __restrict__ y, const int64_t* __restrict__ params, const int64_t* __restrict__ rir_row, const float* __restrict__ rir, const int64_t* __restrict__ rir_len,
+                                                                    const int64_t* __restrict__ rir_delay, int64_t R, int64_t Lmax, int pmax, const float* __restrict__ noise, int64_t noise_rows,
+                                                                    int64_t noise_len, float* __restrict__ out, double* __restrict__ partials, int64_t T, int64_t ntiles) {
+	__shared__ double red[AUG_RED_DOUBLES];
+	const int tid = threadIdx.x, b = blockIdx.y, part = blockIdx.x, nparts = gridDim.x;
+	const AugRow r = aug_row(params, b, T, -1, 0, noise_rows, noise_len, AUG_MAX_STEPS);
+	const RvRow rv = rv_row(params, rir_row, rir_len, rir_delay, b, T, R, Lmax, pmax);
+	const bool copy = rv.row < 0;
+	const float* h = rir + (copy ? 0 : rv.row) * Lmax;
+	const float* yrow = y + (int64_t)b * T;
+	float* orow = out + (int64_t)b * T;
+	const float* nz = (noise != nullptr && r.noise >= 0) ? noise + r.noise * noise_len : nullptr;
+	const int64_t dm = AUG_THREADS % (nz ? noise_len : 1);
+	double ex = 0.0, en = 0.0;
+	for (int64_t tile = part; tile < ntiles; tile += nparts) {
+		const int64_t n0 = tile * AUG_TILE;
+		int64_t m = nz ? (r.offset + n0 + tid) % noise_len : 0;
+		for (int i = 0; i < AUG_TILE / AUG_THREADS; ++i) {
+			const int64_t n = n0 + tid + i * AUG_THREADS;
+			if (n < T) {
+				if (n < r.out_len) {
+					float z;
+					if (copy) z = yrow[n];
+					else if (rv.direct) {  // taps k with 0 <= n + d - k < out_len, ascending
+						const int64_t k_lo = n + rv.delay - r.out_len + 1 > 0 ? n + rv.delay - r.out_len + 1 : 0, k_hi = n + rv.delay < rv.len - 1 ? n + rv.delay : rv.len - 1;
+						z = 0.f;
+						for (int64_t k = k_lo; k <= k_hi; ++k) z = fmaf(h[k], yrow[n + rv.delay - k], z);
+					} else z = orow[n];
+					if (copy || rv.direct) orow[n] = z;
+					ex += (double)z * (double)z;
+					if (nz) { const float v = nz[m]; en += (double)v * (double)v; }
+				} else orow[n] = 0.f;
+			}
+			if (nz) { m += dm; if (m >= noise_len) m -= noise_len; }
+		}
+	}
+	ex = aug_block_sum(ex, red, AUG_THREADS / 64);
+	en = aug_block_sum(en, red, AUG_THREADS / 64);
+	if (tid == 0) {
+		double* p = partials + ((int64_t)b * AUG_PARTS + part) * 2;
+		p[0] = ex; p[1] = en;
+	}
+}
+
+extern "C" int convasr_augment_reverb_block(void) { return RV_BK; }
+extern "C" int convasr_augment_reverb_direct(void) { return RV_DIRECT; }
+
+static int64_t rv_parts(int64_t max_rir_len) { return ceil_div64(max_rir_len < 1 ? 1 : (max_rir_len > RV_MAX_LEN ? RV_MAX_LEN : max_rir_len), RV_BK); }
+static int64_t rv_half_blocks(int64_t T) { return (ceil_div64(T, RV_BK) + 1) / 2; }
+
+extern "C" int64_t convasr_augment_reverb_workspace_bytes(int B, int64_t T, int64_t max_rir_len) {
+	if (B <= 0 || T <= 0) return 0;
+	return (int64_t)B * (rv_half_blocks(T) + 2 * rv_parts(max_rir_len)) * RV_N * (int64_t)sizeof(float2);
+}
+
+extern "C" int convasr_augment_reverb_params(const int64_t* keys, int B, uint64_t seed, int64_t epoch, int64_t rir_rows, uint32_t reverb_thr, int64_t* rir_row, void* stream) {
+	if (const int e = aug_check_batch("augment_reverb_params", B, 0)) return e;
+	CONVASR_CHECK_ARG(epoch >= 0 && epoch < (1ll << 32), "augment_reverb_params: epoch %lld outside [0, 2^32)", (long long)epoch);
+	CONVASR_CHECK_ARG(reverb_thr <= (1u << 24), "augment_reverb_params: a probability threshold above 2^24");
+	CONVASR_CHECK_ARG(rir_rows >= 1, "augment_reverb_params: a bank of %lld impulse responses", (long long)rir_rows);
+	if (rir_rows >= (1ll << 31)) return convasr_fail(CONVASR_EUNSUPPORTED, "augment_reverb_params: a bank of %lld impulse responses, 2^31 or more", (long long)rir_rows);
+	if (B == 0) return 0;
+	CONVASR_CHECK_ARG(keys && rir_row, "augment_reverb_params: NULL pointer");
+	hipLaunchKernelGGL(reverb_params_kernel, dim3((unsigned)ceil_div64(B, 256)), dim3(256), 0, (hipStream_t)stream, keys, B, seed, (unsigned)epoch, rir_rows, reverb_thr, rir_row);
+	CONVASR_CHECK_LAUNCH("augment_reverb_params");
+	return 0;
+}
+
+extern "C" int convasr_augment_reverb(const float* y, int B, int64_t T, const int64_t* params, const int64_t* rir_row, const float* rir, int64_t rir_rows, int64_t rir_max_len, const int64_t* rir_len,
+                                      const int64_t* rir_delay, const int64_t* rir_len_host, const int64_t* rir_delay_host, const float* twiddles, const float* noise, int64_t noise_rows,
+                                      int64_t noise_len, float* out, double* partials, void* workspace, int64_t workspace_bytes, void* stream) {
+	if (const int e = aug_check_batch("augment_reverb", B, T)) return e;
+	CONVASR_CHECK_ARG(rir != nullptr && rir_len != nullptr && rir_delay != nullptr && rir_len_host != nullptr && rir_delay_host != nullptr, "augment_reverb: NULL bank pointer");
+	CONVASR_CHECK_ARG(rir_rows >= 1 && rir_max_len >= 1, "augment_reverb: a bank of %lld impulse responses x %lld taps", (long long)rir_rows, (long long)rir_max_len);
+	if (rir_rows >= (1ll << 31)) return convasr_fail(CONVASR_EUNSUPPORTED, "augment_reverb: a bank of %lld impulse responses, 2^31 or more", (long long)rir_rows);
+	int64_t longest = 0;
+	for (int64_t i = 0; i < rir_rows; ++i) {
+		const int64_t len = rir_len_host[i], d = rir_delay_host[i];
+		CONVASR_CHECK_ARG(len >= 1 && len <= rir_max_len, "augment_reverb: impulse response %lld has %lld taps, outside [1, %lld]", (long long)i, (long long)len, (long long)rir_max_len);
+		if (len > RV_MAX_LEN) return convasr_fail(CONVASR_EUNSUPPORTED, "augment_reverb: impulse response %lld has %lld taps > %d", (long long)i, (long long)len, RV_MAX_LEN);
+		CONVASR_CHECK_ARG(d >= 0 && d < len, "augment_reverb: impulse response %lld has its delay %lld outside [0, %lld)", (long long)i, (long long)d, (long long)len);
+		longest = len > longest ? len : longest;
+	}
+	if (const int e = aug_check_noise("augment_reverb", noise, noise_rows, noise_len)) return e;
+	if (B == 0 || T == 0) return 0;
+	CONVASR_CHECK_ARG(y && params && rir_row && twiddles && out && partials, "augment_reverb: NULL pointer");
+	CONVASR_CHECK_ARG(y != out, "augment_reverb: in place");
+	const int64_t need = convasr_augment_reverb_workspace_bytes(B, T, longest);
+	CONVASR_CHECK_ARG(workspace != nullptr && workspace_bytes >= need, "augment_reverb: a workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+	const int pmax = (int)rv_parts(longest), mh_max = (int)rv_half_blocks(T);
+	const int64_t ntiles = ceil_div64(T, AUG_TILE);
+	hipLaunchKernelGGL(reverb_spectra_kernel, dim3((unsigned)(mh_max + 2 * pmax), (unsigned)B), dim3(RV_THREADS), 0, (hipStream_t)stream, y, params, rir_row, rir, rir_len, rir_delay, rir_rows, rir_max_len,
+	                   pmax, mh_max, (const float4*)twiddles, (float2*)workspace, T);
+	CONVASR_CHECK_LAUNCH("augment_reverb (spectra)");
+	hipLaunchKernelGGL(reverb_apply_kernel, dim3((unsigned)mh_max, (unsigned)B), dim3(RV_THREADS), 0, (hipStream_t)stream, params, rir_row, rir_len, rir_delay, rir_rows, rir_max_len, pmax, mh_max,
+	                   (const float4*)twiddles, (const float2*)workspace, out, T);
+	CONVASR_CHECK_LAUNCH("augment_reverb (apply)");
+	hipLaunchKernelGGL(reverb_finish_kernel, dim3((unsigned)(ntiles < AUG_PARTS ? ntiles : AUG_PARTS), (unsigned)B), dim3(AUG_THREADS), 0, (hipStream_t)stream, y, params, rir_row, rir, rir_len, rir_delay, rir_rows,
+	                   rir_max_len, pmax, noise, noise_rows, noise_len, out, partials, T, ntiles);
+	CONVASR_CHECK_LAUNCH("augment_reverb (finish)");
 	return 0;
 }

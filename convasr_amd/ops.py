@@ -1909,11 +1909,98 @@ def augment_params(xlen, keys, T, seed, epoch, steps, speed_thr = 1 << 24, gain_
 	return params, xlen_out
 
 
-def augment_waveform(x, params, table = None, gain_table = None, noise = None, snr_table = None):
+def reverb_block():
+	"""Outputs per block Bk of convasr_augment_reverb's partitioned convolution; its FFTs have 2 Bk points (tests straddle it)."""
+	return _cached_query('convasr_augment_reverb_block')
+
+
+def reverb_direct():
+	"""min(rir_len, out_len) up to which convasr_augment_reverb sums an utterance's products directly instead of through FFTs."""
+	return _cached_query('convasr_augment_reverb_direct')
+
+
+_reverb_twiddles = {}
+
+
+def reverb_twiddles(device):
+	"""The (Bk, 4) fp32 table (c_hi, s_hi, c_lo, s_lo) of convasr_augment_reverb on `device`, c = cos(pi t / Bk), s = -sin(pi t / Bk): float64 on the
+	host, each split once into its fp32 rounding and the fp32 remainder, kept."""
+	import numpy as np
+	t = _reverb_twiddles.get(device)
+	if t is None:
+		a = np.pi * np.arange(reverb_block(), dtype = np.float64) / reverb_block()
+		w = np.stack([np.cos(a), -np.sin(a)], axis = 1)
+		hi = w.astype(np.float32)
+		t = _reverb_twiddles[device] = torch.from_numpy(np.concatenate([hi, (w - hi.astype(np.float64)).astype(np.float32)], axis = 1)).to(device)
+	return t
+
+
+def rir_delays(rir, rir_len):
+	"""d_r, the index of the first largest |h_r[k]| over k < rir_len[r] (the direct path): (R,) int64 on the CPU.  Host work, done once per bank."""
+	h = rir.detach().cpu().abs()
+	n = torch.as_tensor(rir_len, dtype = torch.int64).cpu()
+	return torch.tensor([int(h[r, :max(int(n[r]), 1)].argmax()) for r in range(h.shape[0])], dtype = torch.int64)
+
+
+def reverb_params(keys, seed, epoch, rir_rows, reverb_thr):
+	"""convasr_augment_reverb_params: rir_row (B,) int64, the row of the bank of rir_rows impulse responses each utterance is convolved with, -1
+	= none (purposes 12 and 13 of the generator; reverb_thr from prob_threshold).  One launch; B == 0: none."""
+	require_cuda(keys)
+	if keys.ndim != 1 or keys.dtype != torch.int64:
+		raise ValueError(f'reverb_params: keys must be a (B,) int64 tensor, got {tuple(keys.shape)} {keys.dtype}')
+	keys = keys.contiguous()
+	rir_row = torch.empty(keys.shape[0], dtype = torch.int64, device = keys.device)
+	call('convasr_augment_reverb_params', ptr(keys), keys.shape[0], int(seed) & 0xffffffffffffffff, int(epoch), int(rir_rows), int(reverb_thr), ptr(rir_row), stream_ptr())
+	return rir_row
+
+
+def augment_reverb(y, params, rir_row, rir, rir_len, rir_delay, noise = None, host = None):
+	"""convasr_augment_reverb: y (B, T) float32, the output of the speed and gain pass, convolved per utterance with row rir_row[b] of the bank
+	rir (R, Lmax) float32, shifted by the row's direct-path delay and cut at out_len -> (out (B, T) float32, partials (B, parts, 2) float64, the
+	energies of the result and of the noise window that convasr_augment_mix reads; a view of a workspace, valid until the next call).  rir_len,
+	rir_delay: (R,) int64 device tensors; host: their (rir_len, rir_delay) copies as CPU int64 tensors, which the argument checks read -- None
+	copies them back from the device, which synchronises.  Three launches; B == 0 or T == 0 launches nothing."""
+	require_cuda(y, params, rir_row, rir, rir_len, rir_delay, noise)
+	if y.ndim != 2 or y.dtype != torch.float32:
+		raise ValueError(f'augment_reverb: a (B, T) float32 batch expected, got {tuple(y.shape)} {y.dtype}')
+	dev = y.device
+	B, T = y.shape
+	_same_device('augment_reverb', dev, params = params, rir_row = rir_row, rir = rir, rir_len = rir_len, rir_delay = rir_delay, noise = noise)
+	if params.shape != (B, len(AUG_FIELDS)) or params.dtype != torch.int64 or rir_row.shape != (B,) or rir_row.dtype != torch.int64:
+		raise ValueError(f'augment_reverb: params must be ({B}, {len(AUG_FIELDS)}) int64 and rir_row ({B},) int64, got {tuple(params.shape)} {params.dtype} and {tuple(rir_row.shape)} {rir_row.dtype}')
+	if rir.ndim != 2 or rir.dtype != torch.float32 or (noise is not None and (noise.ndim != 2 or noise.dtype != torch.float32)):
+		raise ValueError(f'augment_reverb: the bank must be a (R, Lmax) float32 tensor (the noise a (N, L) one), got {tuple(rir.shape)} {rir.dtype}')
+	R, Lmax = rir.shape
+	if host is None:
+		host = (rir_len.cpu(), rir_delay.cpu())
+	for what, t in (('rir_len', rir_len), ('rir_delay', rir_delay), ('host rir_len', host[0]), ('host rir_delay', host[1])):
+		if t.shape != (R,) or t.dtype != torch.int64:
+			raise ValueError(f'augment_reverb: {what} must be a ({R},) int64 tensor, got {tuple(t.shape)} {t.dtype}')
+	if host[0].is_cuda or host[1].is_cuda:
+		raise ValueError('augment_reverb: host = (rir_len, rir_delay) must be CPU tensors')
+	y, params, rir_row, rir, rir_len, rir_delay = (t.contiguous() for t in (y, params, rir_row, rir, rir_len, rir_delay))
+	len_host, delay_host = host[0].contiguous(), host[1].contiguous()
+	noise = None if noise is None else noise.contiguous()
+	parts = _cached_query('convasr_augment_parts')
+	out = torch.empty(B, T, dtype = torch.float32, device = dev)
+	partials = workspace(max(B, 1) * parts * 16, dev, 'augment')
+	longest = int(len_host.max()) if R > 0 else 0
+	nbytes = _cached_query('convasr_augment_reverb_workspace_bytes', B, T, longest)
+	ws = workspace(nbytes, dev, 'reverb')
+	rows, samples = (0, 0) if noise is None else noise.shape
+	call('convasr_augment_reverb', ptr(y), B, T, ptr(params), ptr(rir_row), ptr(rir), R, Lmax, ptr(rir_len), ptr(rir_delay), ptr(len_host), ptr(delay_host), ptr(reverb_twiddles(dev)), ptr(noise),
+	     rows, samples, ptr(out), ptr(partials), ptr(ws), ws.numel(), stream_ptr())
+	return out, partials[:B * parts * 16].view(torch.float64).view(B, parts, 2)
+
+
+def augment_waveform(x, params, table = None, gain_table = None, noise = None, snr_table = None, rir = None, rir_len = None, rir_delay = None, rir_row = None, rir_host = None):
 	"""convasr_augment_waveform + convasr_augment_mix: x (B, T) float32 or int16 (scaled by 1 / 32767) -> (out (B, T) float32 of the same padded
 	length, scales (B,) float32, the factor each utterance's noise was added with; 0 = none).  params: augment_params' tensor; table
 	(n_speeds, taps, phases + 1), gain_table, noise (N, L) and snr_table float32 device tensors (None: no speeds other than 1.0 / no gain / no
-	noise).  Two launches, a third with a noise bank; B == 0 or T == 0 launches nothing."""
+	noise).  Two launches, a third with a noise bank; B == 0 or T == 0 launches nothing.
+	With a bank of room impulse responses -- rir (R, Lmax) float32, rir_len and rir_delay (R,) int64, rir_row (B,) int64 from reverb_params,
+	rir_host as augment_reverb's `host` -- convasr_augment_reverb runs between the two (three more launches) and the noise is mixed at an SNR
+	relative to the reverberated speech; without one, nothing changes."""
 	x = _augment_batch('augment_waveform', x)
 	dev = x.device
 	B, T = x.shape
@@ -1927,6 +2014,8 @@ def augment_waveform(x, params, table = None, gain_table = None, noise = None, s
 		raise ValueError(f'augment_waveform: a table of {augment_phases() + 1} columns expected, got {tuple(table.shape)}')
 	if noise is not None and snr_table is None:
 		raise ValueError('augment_waveform: a noise bank needs an SNR table')
+	if rir is not None and (rir_len is None or rir_delay is None or rir_row is None):
+		raise ValueError('augment_waveform: a bank of impulse responses needs rir_len, rir_delay and rir_row')
 	params, table, gain_table, noise, snr_table = (None if t is None else t.contiguous() for t in (params, table, gain_table, noise, snr_table))
 	out = torch.empty(B, T, dtype = torch.float32, device = dev)
 	scales = torch.zeros(B, dtype = torch.float32, device = dev) if noise is None or B == 0 or T == 0 else torch.empty(B, dtype = torch.float32, device = dev)
@@ -1934,6 +2023,9 @@ def augment_waveform(x, params, table = None, gain_table = None, noise = None, s
 	rows, samples = (0, 0) if noise is None else noise.shape
 	call('convasr_augment_waveform', ptr(x), dtype_code(x.dtype), B, T, ptr(params), ptr(table), 0 if table is None else table.shape[0], 0 if table is None else table.shape[1], ptr(gain_table),
 	     0 if gain_table is None else gain_table.numel(), ptr(noise), rows, samples, ptr(out), ptr(ws), stream_ptr())
+	if rir is not None:
+		out, partials = augment_reverb(out, params, rir_row, rir, rir_len, rir_delay, noise, rir_host)  # (the partials are the same workspace, rewritten)
+		ws = partials
 	if noise is not None:
 		call('convasr_augment_mix', ptr(out), B, T, ptr(params), ptr(noise), rows, samples, ptr(snr_table), snr_table.numel(), ptr(ws), ptr(scales), stream_ptr())
 	return out, scales

@@ -1276,6 +1276,45 @@ int convasr_augment_waveform(const void* x, int x_dtype, int B, int64_t T, const
 int convasr_augment_mix(float* out, int B, int64_t T, const int64_t* params, const float* noise, int64_t noise_rows, int64_t noise_len,
                         const float* snr_table, int snr_steps, const double* partials, float* scales, void* stream);
 
+/* Room reverberation, between the gain and the noise: the order per utterance is speed, gain, reverberation, noise.  Like the rest of the
+ * section it is this project's own and unpinned.
+ *   The bank: rir (R, Lmax) fp32 on the device, rir_len (R,) int64 with 1 <= rir_len[r] <= Lmax, rir_delay (R,) int64 = d_r, the index of the
+ *     first largest |h_r[k]| (the direct path), computed once by the caller.  rir_len and rir_delay are passed twice: on the device for the
+ *     kernels and ON THE HOST (rir_len_host, rir_delay_host) for the checks below, which therefore cost no synchronisation.
+ *   Two more purposes of the generator: 12 "reverb fires", 13 the row, uniform in [0, R - 1]; purposes 0 - 11 keep their meaning and draws.
+ * convasr_augment_reverb_params -- one launch, one lane per utterance -- writes rir_row (B,) int64: the row when the draw fires (threshold
+ *   reverb_thr = floor(p * 2^24)), else -1.  The (B, 8) params tensor is untouched.
+ * convasr_augment_reverb -- three launches -- y (B, T) fp32 = convasr_augment_waveform's output, out (B, T) fp32, y != out.  With out_len =
+ *   params' out_len clamped to [0, T], r = rir_row[b], y[k] = 0 outside [0, out_len):
+ *     z[n] = sum over k < rir_len[r] of h_r[k] * y[n + d_r - k]  for n < out_len,   z[n] = 0 for out_len <= n < T:
+ *   the output is shifted by the direct-path delay and cut at out_len, so xlen_out does not change and the labels stay aligned.  r == -1
+ *   copies y bit for bit; a row outside the bank, or whose device-side length or delay is outside its range, is read as -1.
+ *   Method: uniformly partitioned overlap-save, blocks of Bk = convasr_augment_reverb_block() = 1024 outputs, FFTs of 2 Bk complex points in
+ *     LDS (radix-2 Stockham), P = ceil(rir_len / Bk) parts; two output blocks share one complex FFT (block m in the real parts, block m +
+ *     ceil(M / 2) of the utterance's M blocks in the imaginary ones); per frequency bin the P complex products are added in ascending part
+ *     index, four fma each.  The order is fixed and depends neither on B nor on the utterance's place in the batch: two runs are bit-equal,
+ *     and an utterance's output is bit-equal wherever it sits.  An utterance with min(rir_len, out_len) <= convasr_augment_reverb_direct() = 32
+ *     skips the FFTs: the at most 32 products of a sample with 0 <= n + d_r - k < out_len are summed directly, one fma each in ascending k.
+ *   twiddles: (Bk, 4) fp32 on the device, 16-byte aligned, (c_hi, s_hi, c_lo, s_lo) for t < Bk with c = cos(pi t / Bk), s = -sin(pi t / Bk)
+ *     computed in float64 by the caller, hi = the value rounded to fp32 and lo = the remainder rounded to fp32: a twiddle of one float per
+ *     component misses |w| = 1 by up to 3e-8, which biases the energy of z by more than the noise scale's last fp32 bit.
+ *   partials: (B, convasr_augment_parts(), 2) float64, (sum of z^2, sum of v^2) over n < out_len in exactly the layout, tile ownership and
+ *     order that convasr_augment_waveform leaves them in (for r == -1 the same bits), so convasr_augment_mix runs unchanged afterwards and its
+ *     SNR is relative to the reverberated speech.  noise may be NULL (rows 0).
+ *   workspace: convasr_augment_reverb_workspace_bytes(B, T, the longest rir_len) bytes, uninitialised.
+ * Plain launches only: no memset or copy nodes, no atomics, no host synchronisation.  B == 0 or T == 0 launches nothing.
+ * Envelope, checked before any launch: every rir_len <= 32768, R < 2^31, B <= 65535, T < 2^31; outside it CONVASR_EUNSUPPORTED.  A NULL pointer,
+ * R or Lmax or a length of 0, a length above Lmax, a delay outside [0, rir_len), y == out or a workspace that is too small: CONVASR_EINVAL. */
+int convasr_augment_reverb_block(void);
+int convasr_augment_reverb_direct(void);
+int64_t convasr_augment_reverb_workspace_bytes(int B, int64_t T, int64_t max_rir_len);
+int convasr_augment_reverb_params(const int64_t* keys, int B, uint64_t seed, int64_t epoch, int64_t rir_rows, uint32_t reverb_thr,
+                                  int64_t* rir_row, void* stream);
+int convasr_augment_reverb(const float* y, int B, int64_t T, const int64_t* params, const int64_t* rir_row, const float* rir, int64_t rir_rows,
+                           int64_t rir_max_len, const int64_t* rir_len, const int64_t* rir_delay, const int64_t* rir_len_host,
+                           const int64_t* rir_delay_host, const float* twiddles, const float* noise, int64_t noise_rows, int64_t noise_len,
+                           float* out, double* partials, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* SpecAugment (Park et al. 2019, without time warping) on x (B, F, T) fp32 log-mel features, out of the same shape, x != out.
  *   valid = ceil(xlen[b] * T) in fp32, clamped to [0, T];
  *   frequency mask i < freq_masks: w = uniform in [0, min(freq_width, F)], start = uniform in [0, F - w];
