@@ -63,6 +63,12 @@ _SIGNATURES = dict(
 	convasr_ctc_loss_long_chunk_frames = (c_int, []),
 	convasr_ctc_loss_long_workspace_bytes = (c_i64, [c_int, c_int, c_int, c_int]),
 	convasr_ctc_loss_long = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_star_ctc_states_per_wave = (c_int, []),
+	convasr_star_ctc_renorm_frames = (c_int, []),
+	convasr_star_ctc_max_states = (c_int, []),
+	convasr_star_ctc_supported = (c_int, [c_int, c_int, c_int, c_int]),
+	convasr_star_ctc_workspace_bytes = (c_i64, [c_int, c_int, c_int, c_int]),
+	convasr_star_ctc_loss = (c_int, [c_p, c_p, c_p, c_p, c_p, c_f32, c_f32, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_scale_rows = (c_int, [c_p, c_p, c_p, c_i64, c_p, c_int, c_i64, c_p]),
 	convasr_loss_head = (c_int, [c_p, c_p, c_i64, c_p, c_int, c_f32, c_p, c_p, c_p, c_p, c_f32, c_p]),
 	convasr_entropy = (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_f32, c_p]),

@@ -45,3 +45,51 @@ def search_bct(log_probs_bct, tokens, token_lengths, blank, thresholds, lengths 
 	"""Same for the model's own output layout: logical (B, C, T) whose memory is (B, T, C)."""
 	assert ops.is_cl(log_probs_bct)
 	return ops.ctc_keyword_search(log_probs_bct, tokens, token_lengths, blank, thresholds, lengths = lengths, min_gap = min_gap, max_hits = max_hits, dense = dense)
+
+
+STAR_GAP_MODES = ('ends', 'words', 'all')
+
+
+def star_gaps(targets, ylen, mode, space = None):
+	"""Where a star may stand (functional.star_ctc_loss's star_mask): targets (B, S_max), ylen (B,) -> (B, S_max + 1) bool on the targets'
+	device, built with elementwise torch ops only (kernel nodes under graph capture).  Gap g lies before label g, gap ylen[b] after the last
+	label; entries past ylen[b] are False.  mode: 'ends' -- gaps 0 and ylen (the recording was cut inside speech); 'words' -- the ends and
+	the gap before every `space` label (whole words are missing); 'all' -- every gap."""
+	if mode not in STAR_GAP_MODES:
+		raise ValueError(f'star_gaps: mode {mode!r} is none of {STAR_GAP_MODES}')
+	if mode == 'words' and space is None:
+		raise ValueError("star_gaps: mode 'words' needs the label of the space")
+	if targets.ndim != 2 or ylen.shape != targets.shape[:1]:
+		raise ValueError(f'star_gaps: targets (B, S_max) and ylen (B,) expected, got {tuple(targets.shape)}, {tuple(ylen.shape)}')
+	S_max = targets.shape[1]
+	idx = torch.arange(S_max + 1, device = targets.device).unsqueeze(0)
+	n = ylen.to(device = targets.device).unsqueeze(1)
+	if mode == 'all':
+		return idx <= n
+	mask = (idx == 0) | (idx == n)
+	if mode == 'words' and S_max > 0:
+		label = targets.gather(1, idx.clamp(max = S_max - 1).expand(targets.shape[0], -1))  # label g at gap g (the last column: masked by g < ylen)
+		mask = mask | ((label == int(space)) & (idx < n))
+	return mask
+
+
+class StarCTC:
+	"""The training option behind JasperNet.ctc_star: every head's CTC loss runs over partial transcripts, with a star allowed in the gaps
+	`gaps` names (star_gaps) at the costs `penalty` per frame and `enter` per star used (natural log, <= 0).  The two costs have no
+	defaults: the rule is this project's own and nothing has been tuned on speech."""
+
+	def __init__(self, gaps = 'words', *, penalty, enter, space = None):
+		if gaps not in STAR_GAP_MODES:
+			raise ValueError(f'StarCTC: gaps {gaps!r} is none of {STAR_GAP_MODES}')
+		if gaps == 'words' and space is None:
+			raise ValueError("StarCTC: gaps = 'words' needs the label of the space")
+		for name, v in (('penalty', penalty), ('enter', enter)):
+			if not isinstance(v, (int, float)) or isinstance(v, bool) or not v <= 0 or v == float('-inf'):
+				raise ValueError(f'StarCTC: {name} must be a finite natural-log cost <= 0, got {v!r}')
+		self.gaps, self.penalty, self.enter, self.space = gaps, float(penalty), float(enter), (None if space is None else int(space))
+
+	def mask(self, targets, ylen):
+		return star_gaps(targets, ylen, self.gaps, self.space)
+
+	def __repr__(self):
+		return f'StarCTC(gaps = {self.gaps!r}, penalty = {self.penalty}, enter = {self.enter}, space = {self.space})'

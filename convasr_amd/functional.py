@@ -1059,6 +1059,36 @@ def ctc_loss(log_probs, targets, olen, ylen, blank, norm = None):
 	return CtcLossFunction.apply(log_probs, targets, olen, ylen, blank, norm)
 
 
+class StarCtcLossFunction(torch.autograd.Function):
+	"""CtcLossFunction over partial transcripts (ops.star_ctc_loss; include/convasr_hip.h: convasr_star_ctc_loss has the rule): returns
+	(nll or nll / norm, star_frames); star_frames (B, S_max + 1) takes no gradient.  Backward is the same per-utterance scaling."""
+
+	@staticmethod
+	def forward(ctx, log_probs, targets, olen, ylen, blank, star_mask, star_penalty, star_enter, norm = None):
+		lp = ops.as_cl(log_probs, torch.float32)
+		need = log_probs.requires_grad
+		nll, grad, frames = ops.star_ctc_loss(lp, targets, olen, ylen, blank, star_mask, star_penalty, star_enter, need_grad = need)
+		ctx.norm = norm
+		if need:
+			ctx.save_for_backward(grad)
+		ctx.mark_non_differentiable(frames)
+		if norm is None:
+			return nll, frames
+		if norm.dtype == torch.int64 and norm.ndim == 1 and norm.device == nll.device:
+			return ops.scale_rows(nll, None, norm), frames
+		return nll / norm, frames
+
+	@staticmethod
+	def backward(ctx, g, _):
+		grad, = ctx.saved_tensors
+		return ops.scale_rows(grad, g, ctx.norm), None, None, None, None, None, None, None, None
+
+
+def star_ctc_loss(log_probs, targets, olen, ylen, blank, star_mask, star_penalty, star_enter, norm = None):
+	"""(loss (B,), star_frames (B, S_max + 1)): ctc_loss with a star allowed in the gaps star_mask names (ctc.star_gaps builds it)."""
+	return StarCtcLossFunction.apply(log_probs, targets, olen, ylen, blank, star_mask, float(star_penalty), float(star_enter), norm)
+
+
 def _teacher_pair(teacher):
 	"""(values, indices) of logical shape (B, k, T) from a models.sparse_topk dict over the class dimension of (B, C, T) logits, or from
 	such a pair itself."""

@@ -472,6 +472,7 @@ class JasperNet(nn.Module):
 		self.num_epilogue_modules = 2
 		self.frontend = frontend
 		self.feature_transform = None  # e.g. augment.SpecAugment: applied to the frontend's features in train() mode only
+		self.ctc_star = None  # a ctc.StarCTC: in train() mode every head's loss is the star-token CTC loss over partial transcripts (eval() keeps the plain loss)
 		self.normalize_features = MaskedInstanceNorm1d(num_input_features, affine = False, eps = normalize_features_eps, track_running_stats = normalize_features_track_running_stats, temporal_mask = normalize_features_temporal_mask, legacy = normalize_features_legacy) if normalize_features else None
 		self.decoder = Decoder(width(out_width_factors_large[1]), num_classes, type = decoder_type)
 		self.residual, self.dict, self.bpe_only, self.check_time_dim_padded = residual, dict, bpe_only, check_time_dim_padded
@@ -554,12 +555,19 @@ class JasperNet(nn.Module):
 		olen = [ops.output_lengths(xlen, l.shape[0], l.shape[-1], l.device) for l in logits]  # compute_output_lengths (models.py:611-614) as one launch
 		aux = {}
 		if y is not None and ylen is not None:
-			loss = [Fn.ctc_loss(lp, y[:, i], olen[i], ylen[:, i], lp.shape[1] - 1, norm = ylen[:, 0]) for i, lp in enumerate(log_probs)]
+			star = self.ctc_star if self.training else None
+			if star is not None:
+				pairs = [Fn.star_ctc_loss(lp, y[:, i], olen[i], ylen[:, i], lp.shape[1] - 1, star.mask(y[:, i], ylen[:, i]), star.penalty, star.enter, norm = ylen[:, 0]) for i, lp in enumerate(log_probs)]
+				loss, star_frames = [p[0] for p in pairs], [p[1] for p in pairs]
+			else:
+				loss = [Fn.ctc_loss(lp, y[:, i], olen[i], ylen[:, i], lp.shape[1] - 1, norm = ylen[:, 0]) for i, lp in enumerate(log_probs)]
 			heads = loss if not self.bpe_only else loss[1:]
 			if not heads:  # bpe_only with a single head: the reference's sum(loss[1:]) over nothing is 0 (models.py:325)
 				aux = dict(loss = torch.zeros_like(loss[0]))
 			else:
 				aux = dict(loss = heads[0] if len(heads) == 1 else sum(heads[1:], heads[0]))  # (Python's sum() would start from 0 + tensor: an ATen launch per step)
+			if star is not None:
+				aux['star_frames'] = star_frames
 		return self.dict(logits = logits, log_probs = log_probs, olen = olen, **aux)
 
 	def freeze(self, backbone = 0, decoder0 = False, frontend = False):

@@ -981,7 +981,35 @@ def ctc_loss(log_probs, targets, olen, ylen, blank, need_grad = True):
 	return nll, grad
 
 
-CTC_LONG_WORKSPACE_CAP = 16 << 30  # bytes of workspace one convasr_ctc_loss_long call may take; a resource bound like ALIGN_LONG_WORKSPACE_CAP, not a measurement
+def star_ctc_tiles():
+	"""(states per wave, frames per renormalisation block, largest state count) of convasr_star_ctc_loss (tests straddle them)."""
+	return _cached_query('convasr_star_ctc_states_per_wave'), _cached_query('convasr_star_ctc_renorm_frames'), _cached_query('convasr_star_ctc_max_states')
+
+
+def star_ctc_loss(log_probs, targets, olen, ylen, blank, star_mask, star_penalty, star_enter, need_grad = True):
+	"""CTC over partial transcripts (include/convasr_hip.h: convasr_star_ctc_loss has the rule): log_probs channels-last fp32 (B, C, T),
+	star_mask (B, S_max + 1) bool -- gap g, before label g, may hold a star -- star_penalty / star_enter <= 0 in natural log.  Returns
+	(nll (B,), grad channels-last (B, C, T) or None, star_frames (B, S_max + 1) fp32).  A shape outside the kernel's envelope raises
+	ConvasrHipError: there is no fall-back to the plain loss."""
+	require_cuda(log_probs)
+	B, C, T = log_probs.shape
+	assert is_cl(log_probs) and log_probs.dtype == torch.float32
+	dev = log_probs.device
+	targets, olen, ylen = _ctc_targets(targets, olen, ylen, B, dev)
+	S_max = targets.shape[1]
+	if star_mask.shape != (B, S_max + 1) or star_mask.dtype != torch.bool:
+		raise ValueError(f'star_ctc_loss: a bool star_mask of shape {(B, S_max + 1)} expected, got {star_mask.dtype} {tuple(star_mask.shape)}')
+	star_mask = star_mask.to(device = dev).contiguous()
+	ws = workspace(_query('convasr_star_ctc_workspace_bytes', B, T, C, S_max), dev, 'star_ctc')
+	nll = torch.empty(B, dtype = torch.float32, device = dev)
+	frames = torch.empty(B, S_max + 1, dtype = torch.float32, device = dev)
+	grad = empty_cl(B, C, T, torch.float32, dev) if need_grad else None
+	call('convasr_star_ctc_loss', ptr(log_probs), ptr(targets), ptr(olen), ptr(ylen), ptr(star_mask), float(star_penalty), float(star_enter), ptr(nll), ptr(grad), ptr(frames), ptr(ws),
+	     B, T, C, S_max, int(blank), stream_ptr())
+	return nll, grad, frames
+
+
+CTC_LONG_WORKSPACE_CAP = 16 << 30 # bytes of workspace one convasr_ctc_loss_long call may take; a resource bound like ALIGN_LONG_WORKSPACE_CAP, not a measurement
 
 
 def ctc_loss_long_tiles():

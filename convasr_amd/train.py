@@ -289,6 +289,8 @@ def train_step(model, optimizer, x, xlen, y, ylen, max_norm = 100.0, accumulate_
 		skipped = _NonFinite(scalars, 1, engine)
 	loss_cur = scalars[1]
 	res = dict(loss = scalars[0], loss_cur = loss_cur, entropy = scalars[2], grad_norm = None, skipped = skipped)
+	if 'star_frames' in out:  # model.ctc_star is set: per head, the expected frames every gap's star absorbed (B, S_max + 1)
+		res['star_frames'] = out['star_frames']
 	gate_source = scalars
 	losses, seeds = [loss_vec], [grad_loss_vec]
 	if teacher is not None:

@@ -301,6 +301,43 @@ int convasr_ctc_loss_long_chunk_frames(void);
 int64_t convasr_ctc_loss_long_workspace_bytes(int B, int T, int C, int S_max);
 int convasr_ctc_loss_long(const float* log_probs, const int64_t* targets, const int64_t* olen, const int64_t* ylen, float* nll, float* grad,
                           void* workspace, int64_t workspace_bytes, int B, int T, int C, int S_max, int blank, int chunk_frames, void* stream);
+/* CTC over PARTIAL transcripts: a star token -- "any stretch of frames may stand here, or nothing at all" -- in the gaps of the transcript
+ * that star_mask allows (csrc/star_ctc.hip).  The rule is this project's own (the W-CTC / Star Temporal Classification family), pinned
+ * against no outside implementation.  log_probs, targets, olen, ylen, blank, nll as in convasr_ctc_loss; star_mask (B, S_max + 1) bytes:
+ * entry g != 0 allows a star in gap g, which lies before label g (gap ylen[b]: after the last label; entries past ylen[b] are ignored);
+ * star_penalty <= 0: natural log, paid per frame spent in a star; star_enter <= 0: natural log, paid once per star that is used.
+ *   Units: the labels with a star unit inserted in every allowed gap, n <= 2 S + 1 of them (two stars are never adjacent).  State 2i is
+ *   the blank before unit i, state 2i + 1 is unit i, state 2n the last blank.  A blank emits lp[t, blank], a label lp[t, y], a star the
+ *   constant star_penalty (it matches every frame, silence included, and takes no gradient).
+ *   Arcs into state s from frame t - 1: s; s - 1; s - 2 when s is a unit that differs from unit s - 2 (a star differs from every label);
+ *   the arcs s - 1 and s - 2 INTO a star also pay star_enter (its self arc does not); and, a star being optional, when unit s - 2 is a
+ *   star: s - 3 (the blank before that star) and s - 4 (the unit before it) when that unit differs from unit s.
+ *   Start states: 0 and 1 (state 1 pays star_enter when unit 0 is a star), and 3 when unit 0 is a star.  End states: 2n and 2n - 1, and
+ *   2n - 2 and 2n - 3 when the last unit is a star.  nll = -log of the sum over all paths; +inf where there is none.
+ *   Equivalently exp(-nll) = sum over the subsets A of the allowed gaps of exp(|A| star_enter) * P_ctc(labels with a star class at the gaps
+ *   in A | log_probs with one more column holding star_penalty)  (tests/test_star_ctc_ref.py checks that through F.ctc_loss).
+ * grad (B,T,C; may be NULL) in convasr_ctc_loss's convention: occ[b,t] * exp(lp[b,t,c]) - post[b,t,c] for t < olen[b], 0 beyond and for an
+ * infeasible utterance; post = the posterior mass of the label and blank states of class c, occ = sum_c post = the share of the paths
+ * that is not inside a star at frame t (1 everywhere with an all-zero mask: the plain formula; any multiple of exp(lp) vanishes in
+ * log_softmax's backward, so the logits' gradient is the true one).  star_frames (B, S_max + 1) fp32: the expected number of frames
+ * every gap's star absorbs (0 for a gap without one): where it is large the transcript lacks speech.
+ * One workgroup per utterance, both sweeps in one loop with a workgroup barrier per frame, every loop bounded by T or the state count;
+ * fp32 in base 2 with convasr_ctc_loss's finite sentinel, every (blank, unit) pair of states renormalised by an integer offset of its
+ * own every convasr_star_ctc_renorm_frames() frames; a wave holds convasr_star_ctc_states_per_wave() states, the lattice rows are that
+ * many states rounded up over 4 S_max + 3 (what the tests straddle).  Two plain launches, no memset or copy, no host synchronisation; nll and grad
+ * are bit-reproducible, star_frames (fp32 atomics between workgroups) to rounding.  workspace: convasr_star_ctc_workspace_bytes bytes,
+ * uninitialised.  Envelope, checked before any launch: S_max <= 255 (convasr_star_ctc_max_states() = 1,023 states with every gap
+ * starred), T <= 8192, 2 <= C <= 8192, B <= 65535; outside it CONVASR_EUNSUPPORTED (the workspace query returns that code) -- never a
+ * silent plain loss; a positive or NaN penalty, NULL, blank outside [0, C): CONVASR_EINVAL.  What only the device sees is read
+ * defensively: olen outside [0, T] or ylen outside [0, S_max] give +inf, a label outside [0, C) is a unit nothing matches. */
+int convasr_star_ctc_states_per_wave(void);
+int convasr_star_ctc_renorm_frames(void);
+int convasr_star_ctc_max_states(void);
+int convasr_star_ctc_supported(int B, int T, int C, int S_max);
+int64_t convasr_star_ctc_workspace_bytes(int B, int T, int C, int S_max);
+int convasr_star_ctc_loss(const float* log_probs, const int64_t* targets, const int64_t* olen, const int64_t* ylen, const uint8_t* star_mask,
+                          float star_penalty, float star_enter, float* nll, float* grad, float* star_frames, void* workspace,
+                          int B, int T, int C, int S_max, int blank, void* stream);
 /* out[b,t,c] = grad[b,t,c] * gscale[b]   (chain rule for reduction='none'); with gdiv != NULL the factor is
  * gscale[b] / (float)gdiv[b * gdiv_stride]: the "/ ylen[:, 0]" of models.py:323 folded into the same pass.  gscale NULL (gdiv given):
  * the factor is 1 / gdiv -- the same division in the forward direction (per_b = 1: nll[b] / ylen[b, 0]). */
