@@ -69,6 +69,13 @@ _SIGNATURES = dict(
 	convasr_star_ctc_supported = (c_int, [c_int, c_int, c_int, c_int]),
 	convasr_star_ctc_workspace_bytes = (c_i64, [c_int, c_int, c_int, c_int]),
 	convasr_star_ctc_loss = (c_int, [c_p, c_p, c_p, c_p, c_p, c_f32, c_f32, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_mwer_states_per_wave = (c_int, []),
+	convasr_mwer_renorm_frames = (c_int, []),
+	convasr_mwer_max_labels = (c_int, []),
+	convasr_mwer_max_hyps = (c_int, []),
+	convasr_mwer_supported = (c_int, [c_int, c_int, c_int, c_int, c_int]),
+	convasr_mwer_workspace_bytes = (c_i64, [c_int, c_int, c_int, c_int, c_int]),
+	convasr_mwer_loss = (c_int, [c_p, c_p, c_p, c_p, c_p, c_f32, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_scale_rows = (c_int, [c_p, c_p, c_p, c_i64, c_p, c_int, c_i64, c_p]),
 	convasr_loss_head = (c_int, [c_p, c_p, c_i64, c_p, c_int, c_f32, c_p, c_p, c_p, c_p, c_f32, c_p]),
 	convasr_entropy = (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_f32, c_p]),

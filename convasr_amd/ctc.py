@@ -93,3 +93,78 @@ class StarCTC:
 
 	def __repr__(self):
 		return f'StarCTC(gaps = {self.gaps!r}, penalty = {self.penalty}, enter = {self.enter}, space = {self.space})'
+
+
+MWER_UNITS = ('words', 'chars')
+
+
+class MWER:
+	"""The training option behind JasperNet.ctc_mwer: in train() mode head `head` also gets the N-best minimum-word-error-rate term
+	(functional.mwer_loss; include/convasr_hip.h: convasr_mwer_loss has the rule) and the step's loss becomes ctc_weight * the plain loss +
+	weight * mwer_loss.  The N-best list is decoded from the detached log-probs of the same step (ops.ctc_beam_search at beam_width, topk =
+	n_best) and every hypothesis is scored against the reference by ops.edit_distance in `unit`s ('words' needs the label of the space).
+	include_reference: where no hypothesis equals the reference, the last slot becomes the reference with risk 0.  weight and ctc_weight
+	have no defaults: the rule is this project's own, nothing has been tuned on speech, and no effect on word error rate is shown."""
+
+	def __init__(self, n_best, beam_width, weight, ctc_weight, unit = 'words', space = None, scale = 1.0, include_reference = False, head = 0):
+		n_best, beam_width = int(n_best), int(beam_width)
+		max_hyps = ops.mwer_tiles()[3]
+		if not 2 <= n_best <= max_hyps:
+			raise ValueError(f'MWER: n_best {n_best} is outside [2, {max_hyps}] (one hypothesis has no gradient)')
+		if beam_width < n_best:
+			raise ValueError(f'MWER: beam_width {beam_width} is below n_best {n_best}')
+		if unit not in MWER_UNITS:
+			raise ValueError(f'MWER: unit {unit!r} is none of {MWER_UNITS}')
+		if unit == 'words' and space is None:
+			raise ValueError("MWER: unit = 'words' needs the label of the space")
+		for name, v in (('weight', weight), ('ctc_weight', ctc_weight)):
+			if not isinstance(v, (int, float)) or isinstance(v, bool) or not 0 <= v < float('inf'):
+				raise ValueError(f'MWER: {name} must be a finite number >= 0, got {v!r}')
+		if not isinstance(scale, (int, float)) or isinstance(scale, bool) or not 0 < scale < float('inf'):
+			raise ValueError(f'MWER: scale must be a finite number > 0, got {scale!r}')
+		self.n_best, self.beam_width, self.weight, self.ctc_weight = n_best, beam_width, float(weight), float(ctc_weight)
+		self.unit, self.space, self.scale = unit, (None if space is None else int(space)), float(scale)
+		self.include_reference, self.head = bool(include_reference), int(head)
+		self.skipped = None  # of the last hypotheses() call: how many utterances had a hypothesis past the kernel's envelope (0-d int64 on the device)
+
+	def hypotheses(self, log_probs, olen, y, ylen, blank = None):
+		"""log_probs (B, C, T) of one head, olen (B,), references y (B, Lr) with ylen (B,) -> (hyps (B, n_best, L) int64, hyp_lengths (B,
+		n_best) int64 with -1 for an absent hypothesis, risk (B, n_best) fp32), on the device.  A slot the search could not fill is absent;
+		an utterance with a hypothesis of more than convasr_mwer_max_labels() labels has all of them absent and is counted in self.skipped.
+		blank: the last class by default, as in the model."""
+		max_labels = ops.mwer_tiles()[2]
+		with torch.no_grad():
+			lp = log_probs.detach()
+			blank = lp.shape[1] - 1 if blank is None else int(blank)
+			tokens, _, lengths, score = ops.ctc_beam_search(lp, olen, blank, self.beam_width, topk = self.n_best)
+			L = max(int(lengths.max()), 1)
+			hyps = tokens[:, :, :L]
+			lengths = torch.where(score == float('-inf'), torch.full_like(lengths, -1), lengths)
+			y, ylen = y.to(device = lp.device, dtype = torch.int64), ylen.to(device = lp.device, dtype = torch.int64)
+			if self.unit == 'words':
+				distance, _ = ops.edit_distance(hyps, lengths.clamp(min = 0), y, ylen, ops._lib.METRIC_WORDS, self.space)
+			else:
+				distance, _ = ops.edit_distance(hyps, lengths.clamp(min = 0), y, ylen, ops._lib.METRIC_CHARS)
+			risk = distance.to(torch.float32)
+			if self.include_reference:
+				Lr = y.shape[1]
+				if Lr > L:
+					hyps = torch.nn.functional.pad(hyps, (0, Lr - L))
+				ref = torch.nn.functional.pad(y, (0, hyps.shape[2] - Lr))
+				idx = torch.arange(hyps.shape[2], device = lp.device)
+				same = (lengths == ylen.unsqueeze(1)) & ((hyps == ref.unsqueeze(1)) | (idx >= ylen.view(-1, 1, 1))).all(dim = 2)
+				put = ~same.any(dim = 1)  # (B,): the reference is not in the list
+				hyps = hyps.clone()
+				hyps[:, -1] = torch.where(put.unsqueeze(1), ref, hyps[:, -1])
+				lengths = lengths.clone()
+				lengths[:, -1] = torch.where(put, ylen, lengths[:, -1])
+				risk[:, -1] = torch.where(put, torch.zeros_like(risk[:, -1]), risk[:, -1])
+			long = (lengths > max_labels).any(dim = 1)
+			self.skipped = long.sum()
+			lengths = torch.where(long.unsqueeze(1), torch.full_like(lengths, -1), lengths)
+			hyps = hyps[:, :, :max_labels].contiguous()
+		return hyps, lengths, risk
+
+	def __repr__(self):
+		return (f'MWER(n_best = {self.n_best}, beam_width = {self.beam_width}, weight = {self.weight}, ctc_weight = {self.ctc_weight}, unit = {self.unit!r}, space = {self.space}, '
+		        f'scale = {self.scale}, include_reference = {self.include_reference}, head = {self.head})')

@@ -1089,6 +1089,32 @@ def star_ctc_loss(log_probs, targets, olen, ylen, blank, star_mask, star_penalty
 	return StarCtcLossFunction.apply(log_probs, targets, olen, ylen, blank, star_mask, float(star_penalty), float(star_enter), norm)
 
 
+class MwerLossFunction(torch.autograd.Function):
+	"""N-best MWER loss over the hypotheses' CTC likelihoods (ops.mwer_loss; include/convasr_hip.h: convasr_mwer_loss has the rule): returns
+	(loss (B,), hyp_nll (B, N), hyp_posterior (B, N)); the last two take no gradient.  Backward is CtcLossFunction's per-utterance scaling."""
+
+	@staticmethod
+	def forward(ctx, log_probs, hyps, hyp_lengths, olen, risk, blank, scale = 1.0):
+		lp = ops.as_cl(log_probs, torch.float32)
+		need = log_probs.requires_grad
+		loss, grad, hyp_nll, post = ops.mwer_loss(lp, hyps, hyp_lengths, olen, risk, blank, scale, need_grad = need)
+		if need:
+			ctx.save_for_backward(grad)
+		ctx.mark_non_differentiable(hyp_nll, post)
+		return loss, hyp_nll, post
+
+	@staticmethod
+	def backward(ctx, g, _nll, _post):
+		grad, = ctx.saved_tensors
+		return ops.scale_rows(grad, g, None), None, None, None, None, None, None
+
+
+def mwer_loss(log_probs, hyps, hyp_lengths, olen, risk, blank, scale = 1.0):
+	"""(loss (B,), hyp_nll (B, N), hyp_posterior (B, N)): the expected risk of the N-best list hyps under softmax(scale * CTC log-likelihood),
+	minus the list's mean risk (ctc.MWER builds hyps and risk).  This project's own rule, unpinned against any outside implementation."""
+	return MwerLossFunction.apply(log_probs, hyps, hyp_lengths, olen, risk, blank, scale)
+
+
 def _teacher_pair(teacher):
 	"""(values, indices) of logical shape (B, k, T) from a models.sparse_topk dict over the class dimension of (B, C, T) logits, or from
 	such a pair itself."""

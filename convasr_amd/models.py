@@ -473,6 +473,7 @@ class JasperNet(nn.Module):
 		self.frontend = frontend
 		self.feature_transform = None  # e.g. augment.SpecAugment: applied to the frontend's features in train() mode only
 		self.ctc_star = None  # a ctc.StarCTC: in train() mode every head's loss is the star-token CTC loss over partial transcripts (eval() keeps the plain loss)
+		self.ctc_mwer = None  # a ctc.MWER: in train() mode head ctc_mwer.head also gets the N-best MWER term, loss = ctc_weight * the plain loss + weight * mwer_loss (eval() keeps the plain loss; eager only)
 		self.normalize_features = MaskedInstanceNorm1d(num_input_features, affine = False, eps = normalize_features_eps, track_running_stats = normalize_features_track_running_stats, temporal_mask = normalize_features_temporal_mask, legacy = normalize_features_legacy) if normalize_features else None
 		self.decoder = Decoder(width(out_width_factors_large[1]), num_classes, type = decoder_type)
 		self.residual, self.dict, self.bpe_only, self.check_time_dim_padded = residual, dict, bpe_only, check_time_dim_padded
@@ -568,6 +569,18 @@ class JasperNet(nn.Module):
 				aux = dict(loss = heads[0] if len(heads) == 1 else sum(heads[1:], heads[0]))  # (Python's sum() would start from 0 + tensor: an ATen launch per step)
 			if star is not None:
 				aux['star_frames'] = star_frames
+			mwer = getattr(self, 'ctc_mwer', None) if self.training else None  # (a model pickled before the option existed has no such attribute)
+			if mwer is not None:
+				if star is not None:
+					raise ValueError('JasperNet: ctc_mwer and ctc_star are both set; the MWER term scores whole hypotheses against the reference, which a partial transcript is not')
+				if not 0 <= mwer.head < len(log_probs):
+					raise ValueError(f'JasperNet: ctc_mwer.head {mwer.head} of {len(log_probs)} heads')
+				h = mwer.head
+				hyps, hyp_lengths, risk = mwer.hypotheses(log_probs[h], olen[h], y[:, h], ylen[:, h])
+				term, _, post = Fn.mwer_loss(log_probs[h], hyps, hyp_lengths, olen[h], risk, log_probs[h].shape[1] - 1, mwer.scale)
+				term = term / ylen[:, 0].clamp(min = 1)  # per reference label, as the plain loss is: train_step's loss head multiplies both back
+				aux.update(loss = mwer.ctc_weight * aux['loss'] + mwer.weight * term, mwer_loss = term, mwer_expected_risk = (post * risk).sum(dim = 1), mwer_best_risk = risk[:, 0],
+				           mwer_skipped = mwer.skipped)
 		return self.dict(logits = logits, log_probs = log_probs, olen = olen, **aux)
 
 	def freeze(self, backbone = 0, decoder0 = False, frontend = False):

@@ -1009,6 +1009,47 @@ def star_ctc_loss(log_probs, targets, olen, ylen, blank, star_mask, star_penalty
 	return nll, grad, frames
 
 
+MWER_WORKSPACE_CAP = 8 << 30  # bytes of workspace one convasr_mwer_loss call may take (two lattices per hypothesis); a resource bound, not a measurement
+
+
+def mwer_tiles():
+	"""(states per wave, frames per renormalisation block, most labels of a hypothesis, most hypotheses of an utterance) of
+	convasr_mwer_loss (tests straddle them)."""
+	return _cached_query('convasr_mwer_states_per_wave'), _cached_query('convasr_mwer_renorm_frames'), _cached_query('convasr_mwer_max_labels'), _cached_query('convasr_mwer_max_hyps')
+
+
+def mwer_loss(log_probs, hyps, hyp_lengths, olen, risk, blank, scale = 1.0, need_grad = True):
+	"""N-best MWER loss (include/convasr_hip.h: convasr_mwer_loss has the rule; this project's own, unpinned against any outside
+	implementation): log_probs channels-last fp32 (B, C, T); hyps (B, N, L_max) int64 collapsed label sequences with hyp_lengths (B, N)
+	(< 0: the hypothesis is absent); risk (B, N) errors of every hypothesis; scale > 0.  Returns (loss (B,) = E[risk] - mean risk, grad
+	channels-last (B, C, T) or None, hyp_nll (B, N), hyp_posterior (B, N)).  A shape outside the kernel's envelope, or one whose workspace
+	is above MWER_WORKSPACE_CAP, raises ConvasrHipError: there is no composed fall-back."""
+	require_cuda(log_probs)
+	B, C, T = log_probs.shape
+	assert is_cl(log_probs) and log_probs.dtype == torch.float32
+	dev = log_probs.device
+	if hyps.ndim != 3 or hyps.shape[0] != B or hyps.dtype != torch.int64:
+		raise ValueError(f'mwer_loss: int64 hyps of shape (B = {B}, N, L_max) expected, got {hyps.dtype} {tuple(hyps.shape)}')
+	N, L_max = hyps.shape[1:]
+	if tuple(hyp_lengths.shape) != (B, N) or tuple(risk.shape) != (B, N):
+		raise ValueError(f'mwer_loss: hyp_lengths and risk of shape {(B, N)} expected, got {tuple(hyp_lengths.shape)}, {tuple(risk.shape)}')
+	if tuple(olen.shape) != (B,):
+		raise ValueError(f'mwer_loss: olen of shape {tuple(olen.shape)} for a batch of {B}')
+	if not (isinstance(scale, (int, float)) and not isinstance(scale, bool) and 0 < scale < float('inf')):
+		raise ValueError(f'mwer_loss: scale must be a finite number > 0, got {scale!r}')
+	hyps, hyp_lengths, olen = (t.to(device = dev, dtype = torch.int64).contiguous() for t in (hyps, hyp_lengths, olen))
+	risk = risk.to(device = dev, dtype = torch.float32).contiguous()
+	nbytes = _query('convasr_mwer_workspace_bytes', B, N, T, C, L_max)
+	ws = _call_workspace(nbytes, dev, MWER_WORKSPACE_CAP, 'mwer_loss', f'B {B}, N {N}, T {T}, L_max {L_max}')
+	loss = torch.empty(B, dtype = torch.float32, device = dev)
+	hyp_nll = torch.empty(B, N, dtype = torch.float32, device = dev)
+	post = torch.empty(B, N, dtype = torch.float32, device = dev)
+	grad = empty_cl(B, C, T, torch.float32, dev) if need_grad else None
+	call('convasr_mwer_loss', ptr(log_probs), ptr(hyps) if L_max else None, ptr(hyp_lengths), ptr(olen), ptr(risk), float(scale), ptr(loss), ptr(grad), ptr(hyp_nll), ptr(post), ptr(ws),
+	     B, N, T, C, L_max, int(blank), stream_ptr())
+	return loss, grad, hyp_nll, post
+
+
 CTC_LONG_WORKSPACE_CAP = 16 << 30 # bytes of workspace one convasr_ctc_loss_long call may take; a resource bound like ALIGN_LONG_WORKSPACE_CAP, not a measurement
 
 

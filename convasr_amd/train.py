@@ -291,6 +291,9 @@ def train_step(model, optimizer, x, xlen, y, ylen, max_norm = 100.0, accumulate_
 	res = dict(loss = scalars[0], loss_cur = loss_cur, entropy = scalars[2], grad_norm = None, skipped = skipped)
 	if 'star_frames' in out:  # model.ctc_star is set: per head, the expected frames every gap's star absorbed (B, S_max + 1)
 		res['star_frames'] = out['star_frames']
+	for name in ('mwer_loss', 'mwer_expected_risk', 'mwer_best_risk', 'mwer_skipped'):  # model.ctc_mwer is set: the term and its statistics per utterance, and the skipped utterances
+		if name in out:
+			res[name] = out[name].detach()
 	gate_source = scalars
 	losses, seeds = [loss_vec], [grad_loss_vec]
 	if teacher is not None:
@@ -404,6 +407,7 @@ class GraphedTrainStep:
 
 	def __init__(self, model, optimizer, max_norm = 100.0, warmup = 1, enabled = True, linear = os.environ.get('CONVASR_GRAPH_FORKED') != '1', max_graphs = 64, world_size = 1, sync_metrics = True):
 		self.model, self.optimizer, self.max_norm, self.warmup, self.linear = model, optimizer, max_norm, max(int(warmup), 1), linear
+		self._refuse_mwer()
 		self.world_size, self.sync_metrics = world_size, sync_metrics  # (for the eager fall-through of a data-parallel engine: what train_step averages the logged metrics over)
 		self.max_graphs = max_graphs  # batch shapes beyond this many stay eager (a loader that does not pad to bucket ceilings produces a new shape per batch: every capture keeps its static inputs and outputs alive)
 		engine = model if hasattr(model, 'finish_gradient_sync') else None
@@ -503,7 +507,12 @@ class GraphedTrainStep:
 			self.non_kernel_nodes = True  # (arms _fence_transition; a capture that cannot be inspected is treated like one that holds other nodes)
 		self.captures += 1
 
+	def _refuse_mwer(self):
+		if getattr(M.master_module(self.model), 'ctc_mwer', None) is not None:
+			raise ValueError('GraphedTrainStep: the model has ctc_mwer set; its N-best beam search allocates per call and reads a length on the host, so the MWER route is eager only: use train_step')
+
 	def __call__(self, x, xlen, y, ylen, iteration = 0):
+		self._refuse_mwer()
 		if not self.enabled:
 			return self._eager(x, xlen, y, ylen, iteration)
 		if self.epoch != W.structure_epoch():  # conv modules were replaced (fuse_conv_bn_eval): the captured pointers are stale

@@ -338,7 +338,43 @@ int64_t convasr_star_ctc_workspace_bytes(int B, int T, int C, int S_max);
 int convasr_star_ctc_loss(const float* log_probs, const int64_t* targets, const int64_t* olen, const int64_t* ylen, const uint8_t* star_mask,
                           float star_penalty, float star_enter, float* nll, float* grad, float* star_frames, void* workspace,
                           int B, int T, int C, int S_max, int blank, void* stream);
-/* out[b,t,c] = grad[b,t,c] * gscale[b]   (chain rule for reduction='none'); with gdiv != NULL the factor is
+/* N-best minimum-word-error-rate (MWER) loss: the expected number of errors over an N-best list weighted by the hypotheses' CTC
+ * likelihoods (csrc/mwer.hip).  The rule is this project's own (the sequence-level family of Prabhavalkar et al. 2018, Povey's sMBR),
+ * pinned against no outside implementation; whether it lowers word error rate on speech is not shown anywhere in this project.
+ * log_probs, olen, blank as in convasr_ctc_loss.  For utterance b and hypothesis n = 0 .. N - 1: hyps (B, N, L_max) int64, the first
+ * hyp_lengths[b, n] entries are a collapsed label sequence (no blanks); hyp_lengths (B, N) int64: < 0 = the hypothesis is absent, 0 = the
+ * empty transcript (a lattice of one blank state, valid); risk (B, N) fp32: a number of errors, any finite value, the caller's;
+ * scale > 0, finite.
+ *   ll[b,n] = log P_ctc(hyps[b,n] | log_probs[b, :olen[b]]), the ordinary CTC sum over alignments; hyp_nll = -ll, +inf where no
+ *   alignment fits, where the hypothesis is absent, hyp_lengths[b,n] > L_max or olen[b] is outside [1, T].
+ *   A hypothesis TAKES PART iff hyp_nll is finite.  Over those that take part: p[b,n] = softmax_n(scale * ll[b,n]) (hyp_posterior),
+ *   E[b] = sum_n p risk, rbar[b] = the plain mean of their risks, loss[b] = E[b] - rbar[b], w[b,n] = scale p[b,n] (risk[b,n] - E[b]),
+ *   grad[b,t,c] = sum_n w[b,n] posterior_{b,n}(class c at frame t) for t < olen[b], 0 beyond.  The others have p = 0 and w = 0.  With
+ *   no hypothesis taking part, or only one (p = 1), loss and grad are exactly 0.
+ *   sum_n w = 0, so the gradient's class sum is 0 in every frame: the true derivative with respect to the log-probs and
+ *   convasr_ctc_loss's exp(lp) - posterior convention are the same tensor, and log_softmax's backward passes it unchanged.
+ * grad (B,T,C) may be NULL (the third launch is left out).  Three plain launches on `stream`, no memset, copy, host synchronisation or
+ * atomics on global memory: loss, hyp_nll, hyp_posterior and grad are bit-reproducible.  (1) one workgroup per (b, n), all N reading the
+ * utterance's slab in place: both sweeps in one loop with a workgroup barrier per frame, every loop bounded by T or the state count,
+ * fp32 in base 2 with convasr_ctc_loss's finite sentinel, every (blank, label) pair of states renormalised by an integer offset of its
+ * own every convasr_mwer_renorm_frames() frames; a wave holds convasr_mwer_states_per_wave() states, a workgroup has a thread per 2 L_max + 1
+ * states rounded up to that (what the tests straddle); (2) one wave per utterance, a lane per hypothesis; (3) one wave per (b, t).
+ * workspace: convasr_mwer_workspace_bytes bytes, uninitialised: (2 B N T ls + B N (T / renorm + 1) ls + 5 B N) * 4 with ls = 2 L_max + 2
+ * (both lattices of every hypothesis and their offsets).
+ * Envelope, checked before any launch: N <= convasr_mwer_max_hyps() = 64, L_max <= convasr_mwer_max_labels() = 511 (1,023 states),
+ * T <= 8192, 2 <= C <= 8192, B <= 65535; outside it CONVASR_EUNSUPPORTED (the workspace query returns that code) and nothing is
+ * launched; scale <= 0 or not finite, NULL, blank outside [0, C): CONVASR_EINVAL.  What only the device sees is read defensively: a
+ * label outside [0, C) matches nothing (hyp_nll = +inf). */
+int convasr_mwer_states_per_wave(void);
+int convasr_mwer_renorm_frames(void);
+int convasr_mwer_max_labels(void);
+int convasr_mwer_max_hyps(void);
+int convasr_mwer_supported(int B, int N, int T, int C, int L_max);
+int64_t convasr_mwer_workspace_bytes(int B, int N, int T, int C, int L_max);
+int convasr_mwer_loss(const float* log_probs, const int64_t* hyps, const int64_t* hyp_lengths, const int64_t* olen, const float* risk, float scale,
+                      float* loss, float* grad, float* hyp_nll, float* hyp_posterior, void* workspace,
+                      int B, int N, int T, int C, int L_max, int blank, void* stream);
+/* out[b,t,c] = grad[b,t,c] * gscale[b]  (chain rule for reduction='none'); with gdiv != NULL the factor is
  * gscale[b] / (float)gdiv[b * gdiv_stride]: the "/ ylen[:, 0]" of models.py:323 folded into the same pass.  gscale NULL (gdiv given):
  * the factor is 1 / gdiv -- the same division in the forward direction (per_b = 1: nll[b] / ylen[b, 0]). */
 int convasr_scale_rows(const float* grad, const float* gscale, const int64_t* gdiv, int64_t gdiv_stride, float* out, int B, int64_t per_b, void* stream);
