@@ -102,6 +102,11 @@ _SIGNATURES = dict(
 	convasr_wgrad1x1_grouped_plan = (c_int, [c_int, c_p, c_p, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
 	convasr_wgrad1x1_grouped = (c_int, [c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p]),
 	convasr_copy = (c_int, [c_p, c_p, c_i64, c_p]),
+	convasr_ema_update = (c_int, [c_p, c_p, c_p, c_int, c_i64, c_f32, c_p, c_p, c_p, c_p, c_p]),
+	convasr_ema_update_span = (c_i64, []),
+	convasr_ema_update_max_blocks = (c_i64, []),
+	convasr_swap = (c_int, [c_p, c_p, c_i64, c_p]),
+	convasr_swap_span_bytes = (c_i64, []),
 	convasr_colsum_workspace_bytes = (c_i64, [c_i64, c_int]),
 	convasr_colsum = (c_int, [c_p, c_int, c_i64, c_int, c_p, c_p, c_int, c_p]),
 	convasr_cast_scale = (c_int, [c_p, c_int, c_p, c_int, c_i64, c_f32, c_p]),

@@ -1115,6 +1115,26 @@ def adamw_step(p, g, exp_avg, exp_avg_sq, n, sumsq_buf, max_norm, lr, beta1, bet
 	call('convasr_adamw_step', ptr(p), ptr(g), ptr(exp_avg), ptr(exp_avg_sq), n, ptr(sumsq_buf), float(max_norm), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), ptr(step_in), ptr(step_out), ptr(loss_gate), float(grad_scale), ptr(p16), _lib.BF16 if p16 is None else dtype_code(p16.dtype), ptr(s_in), ptr(s_out), ptr(lr_dev), stream_ptr())
 
 
+def ema_update(w, e, decay, k_in, k_out, e16 = None, loss_gate = None, scaler_state = None):
+	"""e += (1 - d) (w - e) over two fp32 arenas, d = min(decay, (1 + k) / (10 + k)) with k = k_in[0] read on the device (k == 0: e = w); k_out[0] = k + 1.
+	e16: optional 16-bit mirror of e (bf16 or fp16), rewritten with it; loss_gate: the optimizer step's gate; scaler_state: the loss scaler's state
+	AFTER that step -- a non-finite gate or a recorded overflow leaves e, e16 and the counter as they were (include/convasr_hip.h has the rule)."""
+	require_cuda(w, e, k_in, k_out, e16, loss_gate, scaler_state)
+	assert w.dtype == e.dtype == torch.float32 and w.is_contiguous() and e.is_contiguous() and w.numel() == e.numel()
+	assert k_in.dtype == k_out.dtype == torch.float32 and k_in.numel() == k_out.numel() == 1 and k_in.data_ptr() != k_out.data_ptr()
+	assert e16 is None or (e16.dtype in HALF_DTYPES and e16.is_contiguous() and e16.numel() == e.numel())
+	assert loss_gate is None or (loss_gate.dtype == torch.float32 and loss_gate.numel() == 1)
+	assert scaler_state is None or (scaler_state.dtype == torch.float32 and scaler_state.is_contiguous() and scaler_state.numel() == _lib.LOSS_SCALER_FLOATS)
+	call('convasr_ema_update', ptr(w), ptr(e), ptr(e16), _lib.BF16 if e16 is None else dtype_code(e16.dtype), e.numel(), float(decay), ptr(k_in), ptr(k_out), ptr(loss_gate), ptr(scaler_state), stream_ptr())
+
+
+def swap_(a, b):
+	"""Exchange the contents of two device buffers of equal size and dtype in place (one launch; the addresses do not move)."""
+	require_cuda(a, b)
+	assert a.dtype == b.dtype and a.numel() == b.numel() and a.is_contiguous() and b.is_contiguous()
+	call('convasr_swap', ptr(a), ptr(b), a.numel() * a.element_size(), stream_ptr())
+
+
 def novograd_work_table(offsets_host, device):
 	"""Static work table of the fused NovoGrad step: every tensor (segment of the arena) cut into items of bounded size.
 	Returns (items (n_items, 3) int64, seg_first (n_seg + 1,) int64, item_part (n_items,) fp64 scratch), all on `device`."""

@@ -10,6 +10,7 @@ Conv weights live in the arena TAP-MAJOR ([K][Cout][Cin], include/convasr_hip.h 
 That is the element order of the packed MFMA operand and of the weight-gradient slabs, so (a) the optimizer kernel also writes a
 bf16 mirror of the arena whose conv segments ARE the packed forward weights (no packing launches per step), and (b) the split-K
 combine of the weight gradient is a streaming sum instead of a transpose."""
+import contextlib
 import math
 import os
 
@@ -19,6 +20,7 @@ from . import ops, _lib
 from . import models as M
 from . import functional as Fn
 from . import weights as W
+from .optimizers import _advance
 
 
 class FlatParameters:
@@ -62,6 +64,7 @@ class FlatParameters:
 		self.grad_scale = 1.0  # pending scale of .grad (the data-parallel engine's 1 / world_size), consumed by the next optimizer step
 		self._sumsq = torch.zeros(1, dtype = torch.float64, device = dev)
 		self.loss_scaler = None  # a LossScaler (fp16 training): .grad then holds gradients of the SCALED loss until the optimizer step unscales them
+		self.averaged = None  # the WeightEMA whose average_parameters() context is open: the arena then holds the AVERAGE, and nothing may step it
 
 	def mirror(self, dtype = torch.bfloat16):
 		"""The arena's 16-bit mirror in `dtype` (one at a time: asking for the other type re-allocates it and drops what was current)."""
@@ -74,6 +77,8 @@ class FlatParameters:
 	def mirror_carried_over(self, run):
 		"""Run one fused optimizer launch `run(p16)` that rewrites the 16-bit mirror together with the parameters (or leaves both
 		untouched when the device-side gate skips the step): segments that were current before it are current after it."""
+		if self.averaged is not None:
+			raise _lib.ConvasrHipError('the arena holds the averaged weights (inside WeightEMA.average_parameters()): no optimizer step, step-graph replay or copy_to until the context is left')
 		W.mirror_carried_over(self, run)
 
 	def param_views(self, flat_tensor):
@@ -235,6 +240,128 @@ class SGD:
 			g.update(s)
 
 
+class WeightEMA:
+	"""An exponential moving average of every trainable parameter, kept on the device as a second arena, for validation and for export.
+
+	update() is ONE fused launch over the arena (convasr_ema_update): average += (1 - d) (w - average) with d = min(decay, (1 + k) / (10 + k)),
+	k the number of updates applied so far -- a device counter, so a captured step graph replays the warm-up schedule; the first applied
+	update copies the weights.  When the arena has a 16-bit mirror (flat.data16) the launch writes the average's mirror with it.  Call it
+	after optimizer.step with the step's loss_gate (train_step(..., ema = ema) does): a step the optimizer skipped on the device -- a
+	non-finite loss, or an overflow under flat.loss_scaler, whose verdict the kernel reads from the scaler's state -- leaves the average, its
+	mirror and the counter untouched, without the host learning of it.
+
+	average_parameters() EXCHANGES the contents of the arena and the average (and of the two mirrors), it does not re-point the parameters: the
+	arena's address is baked into captured step graphs and keys every packed weight copy (weights.param_version).  Only parameters are
+	averaged.  Buffers -- the batch-norm running statistics -- are not: inside the context the model runs the averaged parameters with its
+	CURRENT running statistics.
+
+	Data-parallel training needs nothing extra: every rank applies the same updates to equal weights, so the ranks hold equal averages."""
+
+	def __init__(self, flat, decay = 0.999):
+		if not 0.0 <= decay <= 1.0:
+			raise ValueError(f'WeightEMA: decay {decay} is not in [0, 1]')
+		self.flat, self.decay = flat, float(decay)
+		self.average = flat.data.clone()  # (before the first update the average IS the weights; the first applied update overwrites it anyway)
+		self.average16 = None  # 16-bit mirror of `average` in flat.data16's type: made by _mirror(), rewritten by every update
+		self.count = torch.zeros(2, 1, dtype = torch.float32, device = flat.data.device)  # [_cur] is current: updates applied so far (the launch reads it and writes the other row)
+		self._cur = 0
+		self._pinned = False  # set by the first step-graph capture (pin): from then on the counter is handed back to the row the graphs read
+		self._mirror()
+
+	def _mirror(self):
+		"""The average's mirror, following flat.data16: made from the average (round-to-nearest-even, what the kernel writes) when the arena
+		has a mirror and this one is missing or of the other 16-bit type."""
+		d16 = self.flat.data16
+		if d16 is not None and (self.average16 is None or self.average16.dtype != d16.dtype):
+			if Fn.capturing():
+				raise _lib.ConvasrHipError('WeightEMA: the update that allocates the average\'s 16-bit mirror cannot be the one captured into a step graph')
+			self.average16 = self.average.to(d16.dtype)
+		return self.average16 if d16 is not None else None
+
+	def pin(self):
+		"""Called by GraphedTrainStep before a capture: the mirror exists, and the counter's current row stops moving."""
+		self._mirror()
+		self._pinned = True
+
+	@property
+	def updates(self):
+		"""Updates applied so far (host read: synchronises)."""
+		return int(self.count[self._cur, 0].item())
+
+	def _refuse_inside(self, what):
+		if self.flat.averaged is not None:
+			raise _lib.ConvasrHipError(f'WeightEMA.{what}: the arena holds the averaged weights (inside average_parameters()); leave the context first')
+
+	def update(self, loss_gate = None):
+		"""One launch (plus, once a step graph has been captured, the one-float hand-back of the counter).  loss_gate: the 1-element gate the
+		optimizer step was given, or None."""
+		self._refuse_inside('update')
+		flat, cur = self.flat, self._cur
+		scaler = flat.loss_scaler
+		ops.ema_update(flat.data, self.average, self.decay, self.count[cur], self.count[1 - cur], e16 = self._mirror(), loss_gate = loss_gate, scaler_state = None if scaler is None else scaler.current)
+		_advance(self, self.count)
+
+	def _exchange(self, d16, was):
+		"""arena <-> average, and d16 <-> the average's mirror while d16 is still the arena's mirror.  Every packed copy goes stale (the epoch);
+		the mirror segments `was` vouched for are vouched for again: each mirror was current for its own fp32 buffer and travels with it."""
+		flat = self.flat
+		ops.swap_(flat.data, self.average)
+		W.bump_param_epoch()
+		if flat.data16 is d16:
+			if d16 is not None:
+				ops.swap_(d16, self.average16)
+			flat.mirror_vouchers = {k: W.param_version(flat._by_id[k]) for k in was} if d16 is not None else {}
+		else:  # the arena's mirror was (re)allocated inside the context: it vouches for nothing, and the average's old mirror is of the wrong type
+			W.mirror_reallocated(flat)
+			self.average16 = None
+
+	@contextlib.contextmanager
+	def average_parameters(self):
+		"""with ema.average_parameters(): the model's parameters ARE the average (two exchange launches on entry, two on exit, also when the body
+		raises); buffers stay the model's own.  Packed weight copies made from the raw weights are not served for the averaged ones, or the
+		reverse; mirror segments that were current stay current, so entering forces no re-round of the arena.  Inside, optimizer steps, update(),
+		copy_to() and step-graph replays raise ConvasrHipError."""
+		self._refuse_inside('average_parameters')
+		if Fn.capturing():
+			raise _lib.ConvasrHipError('WeightEMA.average_parameters: not inside a step-graph capture')
+		flat = self.flat
+		self._mirror()
+		d16 = flat.data16
+		was = [k for k, v in flat.mirror_vouchers.items() if v == W.param_version(flat._by_id[k])]
+		self._exchange(d16, was)
+		flat.averaged = self
+		try:
+			yield self
+		finally:
+			flat.averaged = None
+			self._exchange(d16, was)
+
+	def copy_to(self):
+		"""Write the average into the parameters for good (and its mirror into the arena's): the route to model.fuse_conv_bn_eval() and to export."""
+		self._refuse_inside('copy_to')
+		a16, nbytes = self._mirror(), 4 * self.flat.numel
+
+		def run(p16):
+			_lib.call('convasr_copy', _lib.ptr(self.average), _lib.ptr(self.flat.data), nbytes, _lib.stream_ptr())
+			if p16 is not None:
+				_lib.call('convasr_copy', _lib.ptr(a16), _lib.ptr(p16), nbytes // 2, _lib.stream_ptr())
+		self.flat.mirror_carried_over(run)
+
+	def state_dict(self):
+		"""decay, the update count, and the average as one tensor per parameter in the reference's shapes (flat.export_state: independent of the
+		arena's element order), in flat.params order."""
+		held = self.flat.data if self.flat.averaged is self else self.average  # (inside the context the two have changed places)
+		return dict(format = 1, decay = self.decay, updates = self.updates, average = self.flat.export_state(held))
+
+	def load_state_dict(self, sd):
+		self._refuse_inside('load_state_dict')
+		self.flat.import_state(self.average, sd['average'], 'WeightEMA.load_state_dict(average)')
+		self.decay = float(sd['decay'])
+		self.count[self._cur, 0] = float(sd['updates'])
+		if self.average16 is not None:
+			self.average16.copy_(self.average)
+
+
 class _NonFinite:
 	"""`not isfinite(t[i])`, evaluated (with the stream joins and the host read it takes) only when somebody asks: bool(flag)."""
 
@@ -247,7 +374,7 @@ class _NonFinite:
 		return not bool(torch.isfinite(self.t[self.i]))
 
 
-def train_step(model, optimizer, x, xlen, y, ylen, max_norm = 100.0, accumulate_iterations = 1, iteration = 0, world_size = 1, sync_metrics = True, device_gate = True, teacher = None, distill_weight = 0.0, distill_temperature = 1.0, distill_head = 0):
+def train_step(model, optimizer, x, xlen, y, ylen, max_norm = 100.0, accumulate_iterations = 1, iteration = 0, world_size = 1, sync_metrics = True, device_gate = True, teacher = None, distill_weight = 0.0, distill_temperature = 1.0, distill_head = 0, ema = None):
 	"""One iteration of the reference loop, train.py:745-783.
 
 	Returns dict(loss, loss_cur, entropy, grad_norm, skipped) of 0-d device tensors (read them lazily: no forced host sync).
@@ -261,7 +388,10 @@ def train_step(model, optimizer, x, xlen, y, ylen, max_norm = 100.0, accumulate_
 	distill.TeacherStore.batch): the step minimises the CTC loss as above + distill_weight * mean_b(kd[b]) / accumulate_iterations, with
 	kd = functional.distill_loss(logits[distill_head], teacher, olen[distill_head], distill_temperature); one backward over both loss
 	vectors.  The result gains `distill`, the mean of kd (0-d, on the device), and both gates read non-finite when either mean is.
-	Without a teacher the step launches exactly what it launched before the argument existed."""
+	Without a teacher the step launches exactly what it launched before the argument existed.
+
+	ema (a WeightEMA of optimizer.flat): ema.update follows every optimizer step, with the step's device-side gate, so the average skips
+	the steps the optimizer skips.  Without one the step launches exactly what it launched before the argument existed."""
 	Fn.begin_step(x.device)  # the device-resident dropout key of this step (one single-thread launch; the same whether the step is launched eagerly or replayed from a graph)
 	out = model(x, xlen, y = y, ylen = ylen)
 	log_probs, olen, loss_vec = out['log_probs'], out['olen'], out['loss']
@@ -341,6 +471,8 @@ def train_step(model, optimizer, x, xlen, y, ylen, max_norm = 100.0, accumulate_
 			optimizer.step(loss_gate = gate)
 		else:
 			optimizer.step()
+		if ema is not None:
+			ema.update(loss_gate = gate)
 		if own_norm:
 			res['grad_norm'] = optimizer.total_norm[0]
 		optimizer.zero_grad()
@@ -403,10 +535,14 @@ class GraphedTrainStep:
 	all-reduces are recorded on the communication stream, which forks off the capturing stream at the buckets' ready events and rejoins it in
 	finish_gradient_sync, so a replayed step overlaps the exchange with the backward pass like the eager one and costs the host one launch
 	(eagerly every rank spends ~4 / ~19 ms of Python per Wav2Letter / JasperNetLarge step).  gloo engines (host waits) stay eager: the call
-	falls through to train_step (with this object's world_size / sync_metrics)."""
+	falls through to train_step (with this object's world_size / sync_metrics).
 
-	def __init__(self, model, optimizer, max_norm = 100.0, warmup = 1, enabled = True, linear = os.environ.get('CONVASR_GRAPH_FORKED') != '1', max_graphs = 64, world_size = 1, sync_metrics = True):
+	ema (a WeightEMA of optimizer.flat): every step, eager or replayed, is followed by ema.update with the step's gate; the captured step holds
+	it as kernel nodes (the update, then the hand-back of its counter to the row the graph reads), nothing else."""
+
+	def __init__(self, model, optimizer, max_norm = 100.0, warmup = 1, enabled = True, linear = os.environ.get('CONVASR_GRAPH_FORKED') != '1', max_graphs = 64, world_size = 1, sync_metrics = True, ema = None):
 		self.model, self.optimizer, self.max_norm, self.warmup, self.linear = model, optimizer, max_norm, max(int(warmup), 1), linear
+		self.ema = ema  # a WeightEMA of optimizer.flat, or None: its update is captured behind the optimizer step (kernel nodes: the update and the hand-back of its counter)
 		self._refuse_mwer()
 		self.world_size, self.sync_metrics = world_size, sync_metrics  # (for the eager fall-through of a data-parallel engine: what train_step averages the logged metrics over)
 		self.max_graphs = max_graphs  # batch shapes beyond this many stay eager (a loader that does not pad to bucket ceilings produces a new shape per batch: every capture keeps its static inputs and outputs alive)
@@ -447,7 +583,7 @@ class GraphedTrainStep:
 	def _eager(self, x, xlen, y, ylen, iteration):
 		self.eager_steps += 1
 		self._fence_transition(x.device, eager = True)
-		return train_step(self.model, self.optimizer, x, xlen, y, ylen, max_norm = self.max_norm, iteration = iteration, world_size = self.world_size, sync_metrics = self.sync_metrics)
+		return train_step(self.model, self.optimizer, x, xlen, y, ylen, max_norm = self.max_norm, iteration = iteration, world_size = self.world_size, sync_metrics = self.sync_metrics, ema = self.ema)
 
 	def _sync_lr(self):
 		lr = float(self.optimizer.param_groups[0]['lr'])
@@ -477,6 +613,8 @@ class GraphedTrainStep:
 		W.GRAPHS_CAPTURED[0] = True
 		if getattr(opt.flat, 'loss_scaler', None) is not None:
 			opt.flat.loss_scaler.pinned = True
+		if self.ema is not None:
+			self.ema.pin()
 		# every version-keyed packed copy (padded-Cout forward operands, the folded prologue, the padded head, fp32 / split operands) is
 		# declared stale, so that ALL per-step pack launches are recorded in the graph: a copy that happens to be current now -- a validation
 		# forward ran since the last optimizer step -- would otherwise get no pack node and go stale under replays
@@ -495,7 +633,7 @@ class GraphedTrainStep:
 		Fn.CAPTURING[0] = True
 		try:
 			with torch.cuda.graph(graph, pool = self.pool):
-				res = train_step(self.model, opt, *static, max_norm = self.max_norm, iteration = iteration, world_size = self.world_size, sync_metrics = self.sync_metrics)
+				res = train_step(self.model, opt, *static, max_norm = self.max_norm, iteration = iteration, world_size = self.world_size, sync_metrics = self.sync_metrics, ema = self.ema)
 				kinds = capture_node_kinds(dev)
 		finally:
 			Fn.CAPTURING[0] = False
@@ -540,24 +678,27 @@ class GraphedTrainStep:
 		return g['res']
 
 
-def train_epoch(model, optimizer, batches, sampler = None, scheduler = None, iteration = 0, world_size = 1, max_norm = 100.0, accumulate_iterations = 1, max_iterations = None, on_step = None, graphs = None, teacher_fn = None, distill_weight = 0.0, distill_temperature = 1.0, distill_head = 0):
+def train_epoch(model, optimizer, batches, sampler = None, scheduler = None, iteration = 0, world_size = 1, max_norm = 100.0, accumulate_iterations = 1, max_iterations = None, on_step = None, graphs = None, teacher_fn = None, distill_weight = 0.0, distill_temperature = 1.0, distill_head = 0, ema = None):
 	"""The body of the reference's epoch loop (train.py:739-808) over an iterable of (meta, s, x, xlen, y, ylen) batches whose
 	tensors are already on the device (convasr_amd.datasets.gpu_batches): train_step, scheduler.step(iteration) after every
 	optimizer step (train.py:783), iteration += 1, sampler.batch_idx += world_size (train.py:807-808, what makes a resumed
 	epoch start where it stopped).  Metrics stay on the device; on_step(iteration, batch, result) may read them.
 	teacher_fn(batch) -> the teacher of train_step for the batch (meta, s, x, xlen, y, ylen), with distill_weight / distill_temperature /
 	distill_head handed on; not together with graphs (GraphedTrainStep does not distil): ValueError.
+	ema: a WeightEMA handed on to train_step; a GraphedTrainStep carries its own (GraphedTrainStep(..., ema = ema)), and the two must agree: ValueError.
 	Returns the next iteration number."""
 	if graphs is not None and teacher_fn is not None:
 		raise ValueError('train_epoch: graphs and teacher_fn do not combine (GraphedTrainStep does not capture the distillation term)')
+	if graphs is not None and ema is not None and graphs.ema is not ema:
+		raise ValueError('train_epoch: the step graphs were built without this WeightEMA: pass it as GraphedTrainStep(..., ema = ema)')
 	for meta, s, x, xlen, y, ylen in batches:
 		if graphs is not None and accumulate_iterations == 1 and world_size == 1:
 			res = graphs(x, xlen, y, ylen, iteration = iteration)  # a GraphedTrainStep(model, optimizer, max_norm): replayed per batch shape
 		elif teacher_fn is not None:
 			res = train_step(model, optimizer, x, xlen, y, ylen, max_norm = max_norm, accumulate_iterations = accumulate_iterations, iteration = iteration, world_size = world_size, sync_metrics = world_size > 1,
-				teacher = teacher_fn((meta, s, x, xlen, y, ylen)), distill_weight = distill_weight, distill_temperature = distill_temperature, distill_head = distill_head)
+				teacher = teacher_fn((meta, s, x, xlen, y, ylen)), distill_weight = distill_weight, distill_temperature = distill_temperature, distill_head = distill_head, ema = ema)
 		else:
-			res = train_step(model, optimizer, x, xlen, y, ylen, max_norm = max_norm, accumulate_iterations = accumulate_iterations, iteration = iteration, world_size = world_size, sync_metrics = world_size > 1)
+			res = train_step(model, optimizer, x, xlen, y, ylen, max_norm = max_norm, accumulate_iterations = accumulate_iterations, iteration = iteration, world_size = world_size, sync_metrics = world_size > 1, ema = ema)
 		# train.py:769-783: the scheduler steps only inside the not-skipped branch.  Where the host knows the verdict (a host-side gate
 		# returned skipped = True) the reference's behaviour is reproduced exactly; with the device-side gate the host does not wait
 		# for it, and after a skipped iteration the next step's lr is one scheduler tick ahead of the reference's
@@ -580,7 +721,7 @@ def _finite_mean(values):
 	return sum(vals) / len(vals) if vals else -1.0
 
 
-def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_space = 10, return_text = False, error_analyzer = None, logits_topk = None, logits_dtype = torch.float16):
+def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_space = 10, return_text = False, error_analyzer = None, logits_topk = None, logits_dtype = torch.float16, ema = None):
 	"""One validation set through the reference's apply_model + evaluate_model (train.py:119-300), for the first target head.
 
 	batches yields (meta, s, x, xlen, y, ylen) with the tensors on the device, as for train_epoch.  Per batch, under no_grad with the model
@@ -612,14 +753,18 @@ def evaluate_model(model, batches, tokenizer, decoder = None, blank_amount_to_sp
 	with `values` (k, olen_b) in logits_dtype and `indices` (k, olen_b) (uint8 up to 256 classes, else int16): the k largest logits of
 	every frame of the utterance's own olen_b frames (ops.topk_frames on the first head's logits; the padding is cut on the device, the
 	reference's unpad) -- what distill.TeacherStore.add_utterances takes.  They reach the host in one more copy at the end.  Without it the
-	result is what it was."""
+	result is what it was.
+
+	ema: a WeightEMA of the model's arena, or None.  With one the whole pass runs inside ema.average_parameters(): the averaged parameters with
+	the model's current batch-norm running statistics; the raw parameters are back on return, also after an exception.  Without one the pass
+	launches what it launched before the argument existed."""
 	from . import metrics
 	training, drop_offset = model.training, Fn._DropoutState.offset
 	cols, hyp_tokens, ref_tokens, n_batches = [], [], [], 0
 	top_values, top_indices, top_olen = [], [], []
 	model.eval()
 	try:
-		with torch.no_grad():
+		with torch.no_grad(), (ema.average_parameters() if ema is not None else contextlib.nullcontext()):
 			for meta, s, x, xlen, y, ylen in batches:
 				out = model(x, xlen, y = y, ylen = ylen)
 				lp, olen = out['log_probs'][0], out['olen'][0]

@@ -589,6 +589,33 @@ int convasr_step_begin(uint64_t* state, void* stream);
  * (loss scaler, NovoGrad EMAs, AdamW step count) back to the buffer a captured graph reads. */
 int convasr_copy(const void* src, void* dst, int64_t nbytes, void* stream);
 
+/* ---- weight averaging: an exponential moving average of the parameter arena (train.WeightEMA) ------------------------ */
+
+/* One streaming pass over n fp32 elements (n a multiple of 8; w, e and e16 16-byte aligned; w != e), in this order of operations:
+ *   k = k_in[0]                                 the number of updates APPLIED so far (a device float, saturating at 2^24)
+ *   d = min(decay, (1 + k) / (10 + k))          fp32: each sum and the quotient correctly rounded;  omd = 1 - d, rounded
+ *   e[i] = k == 0 ? w[i] : fma(omd, w[i] - e[i], e[i])      i.e. e + (1 - d) (w - e): the difference is rounded, then one fused multiply-add
+ *   e16[i] = e[i] rounded to nearest-even in e16_dtype (CONVASR_BF16 / CONVASR_F16), when e16 != NULL
+ *   k_out[0] = min(k + 1, 2^24)
+ * k_in / k_out: one device float each, distinct buffers the caller swaps per call (every workgroup reads k while one thread writes the
+ * next value), as convasr_adamw_step's step_in / step_out.  decay in [0, 1].
+ * Skip rule -- the one of the three fused optimizer steps, which return early on `gated || overflow`: when loss_gate != NULL and
+ * *loss_gate is inf or NaN, or when scaler_state != NULL and scaler_state[2] (the loss scaler's "did the last step overflow") is not 0,
+ * the call writes k_out[0] = k_in[0] and nothing else.  Called after an optimizer step with that step's loss_gate and the scaler state
+ * that step WROTE (its scaler_out), it skips exactly when the step did: the step records its overflow verdict there unless it was gated,
+ * and a gated step is caught by loss_gate itself.  No atomics, one kernel node under capture. */
+int convasr_ema_update(const float* w, float* e, void* e16, int e16_dtype, int64_t n, float decay, const float* k_in, float* k_out,
+                       const float* loss_gate, const float* scaler_state, void* stream);
+/* elements one workgroup of convasr_ema_update covers per grid pass, and the largest grid it launches (larger arenas loop) */
+int64_t convasr_ema_update_span(void);
+int64_t convasr_ema_update_max_blocks(void);
+/* Exchanges the contents of a[0..nbytes) and b[0..nbytes) in place (device buffers, 16-byte aligned, nbytes a multiple of 16, not
+ * overlapping): one kernel, every lane reads and writes its own 16 bytes of both.  The addresses stay what they were -- captured step
+ * graphs and packed weight copies that are keyed by the arena's address stay valid. */
+int convasr_swap(void* a, void* b, int64_t nbytes, void* stream);
+/* bytes one workgroup of convasr_swap covers per grid pass */
+int64_t convasr_swap_span_bytes(void);
+
 /* ---- SURVEY 8(f) "next" rows ------------------------------------------------------------------------------------ */
 
 /* NovoGrad.step (optimizers.py:66-90) with torch.nn.utils.clip_grad_norm_ (train.py:777) folded in, over a flat arena of n
