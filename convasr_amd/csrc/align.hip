@@ -30,34 +30,8 @@ struct NwScores {
 	int match, sub, del, ins;
 };
 
-template <int CTRL, int ROWS = 0xf>
-__device__ __forceinline__ int nw_dpp(int old, int src) {
-	return __builtin_amdgcn_update_dpp(old, src, CTRL, ROWS, 0xf, false);
-}
-
-// inclusive prefix maximum over the 64 lanes: row_shr 1, 2, 4, 8 inside each row of 16, then the two row broadcasts
-__device__ __forceinline__ int nw_prefix_max(int x) {
-	x = max(x, nw_dpp<0x111>(NW_NEG, x));
-	x = max(x, nw_dpp<0x112>(NW_NEG, x));
-	x = max(x, nw_dpp<0x114>(NW_NEG, x));
-	x = max(x, nw_dpp<0x118>(NW_NEG, x));
-	x = max(x, nw_dpp<0x142, 0xa>(NW_NEG, x));  // row_bcast:15 into rows 1 and 3
-	x = max(x, nw_dpp<0x143, 0xc>(NW_NEG, x));  // row_bcast:31 into rows 2 and 3
-	return x;
-}
-
-__device__ __forceinline__ int nw_clamp(int n, int hi) { return n < 0 ? 0 : n > hi ? hi : n; }
-
 // (value, index) as one key: the larger value wins, then the lower index
 __device__ __forceinline__ long long nw_key(int value, int index) { return (long long)value * 65536 + (0xFFFF - index); }
-
-__device__ __forceinline__ long long nw_wave_max(long long k) {
-	for (int off = 32; off >= 1; off >>= 1) {
-		const long long o = __shfl_xor(k, off);
-		k = o > k ? o : k;
-	}
-	return k;
-}
 
 // The part of a chunk after the scan, shared by both tiers: x = prefix max of E - j * ins over the chunk, run / left_carry = the running
 // maximum and M[i][j0 - 1] carried from the chunk before.  Returns M[i][j] (0 in a column past lb) and stores the chunk's directions.
@@ -65,7 +39,7 @@ __device__ __forceinline__ int nw_finish_chunk(int x, int& run, int& left_carry,
 	const int v = max(x, run);
 	run = __builtin_amdgcn_readlane(v, NW_THREADS - 1);
 	const int m = valid ? v + j * s.ins : 0;
-	const int left = nw_dpp<0x138>(left_carry, m);  // wave_shr:1, lane 0 <- M[i][j0 - 1]
+	const int left = wave_dpp<0x138>(left_carry, m);  // wave_shr:1, lane 0 <- M[i][j0 - 1]
 	left_carry = __builtin_amdgcn_readlane(m, NW_THREADS - 1);
 	const bool is_ins = m == left + s.ins;
 	const bool is_del = !is_ins && m == up + s.del;
@@ -95,9 +69,9 @@ __device__ long long nw_fill_regs(const int32_t* __restrict__ a, const int32_t* 
 #pragma unroll
 		for (int c = 0; c < R; ++c) {  // independent scans: row i - 1 is all they read
 			const int j = 1 + NW_THREADS * c + lane;
-			const int diag = nw_dpp<0x138>(c == 0 ? 0 : __builtin_amdgcn_readlane(up[c > 0 ? c - 1 : 0], NW_THREADS - 1), up[c]);
+			const int diag = wave_dpp<0x138>(c == 0 ? 0 : __builtin_amdgcn_readlane(up[c > 0 ? c - 1 : 0], NW_THREADS - 1), up[c]);
 			const int e = max(diag + (id[c] == ai ? s.match : s.sub), up[c] + s.del);
-			x[c] = nw_prefix_max(j <= lb ? e - j * s.ins : NW_NEG);
+			x[c] = wave_prefix_max(j <= lb ? e - j * s.ins : NW_NEG, NW_NEG);
 		}
 		int run = 0, left_carry = 0;
 #pragma unroll
@@ -122,7 +96,7 @@ __device__ long long nw_fill_regs(const int32_t* __restrict__ a, const int32_t* 
 			k = kj > k ? kj : k;
 		}
 	}
-	return nw_wave_max(k);
+	return wave_max(k);
 }
 
 // The fill with the row (row[j] = M[i-1][j], j <= lb) and the reference ids (bid[j-1]) in LDS, one chunk after the other.
@@ -145,10 +119,10 @@ __device__ long long nw_fill_lds(const int32_t* __restrict__ a, const int32_t* _
 			const int j = 1 + NW_THREADS * c + lane;
 			const bool valid = j <= lb;
 			const int up = valid ? row[j] : 0;
-			const int diag = nw_dpp<0x138>(diag_carry, up);
+			const int diag = wave_dpp<0x138>(diag_carry, up);
 			diag_carry = __builtin_amdgcn_readlane(up, NW_THREADS - 1);
 			const int e = max(diag + (valid && bid[j - 1] == ai ? s.match : s.sub), up + s.del);
-			const int x = nw_prefix_max(valid ? e - j * s.ins : NW_NEG);
+			const int x = wave_prefix_max(valid ? e - j * s.ins : NW_NEG, NW_NEG);
 			const int m = nw_finish_chunk(x, run, left_carry, up, j, valid, s, dirs + 2 * ((size_t)(i - 1) * cb + c));
 			if (valid) row[j] = m;
 			if (c == cl && m > best) {
@@ -163,7 +137,7 @@ __device__ long long nw_fill_lds(const int32_t* __restrict__ a, const int32_t* _
 		const long long kj = nw_key(row[j], j);
 		k = kj > k ? kj : k;
 	}
-	return nw_wave_max(k);
+	return wave_max(k);
 }
 
 __device__ __forceinline__ uint32_t nw_pack(int ai, int bj) { return (uint32_t)(ai + 1) | ((uint32_t)(bj + 1) << 16); }
@@ -176,7 +150,7 @@ __global__ __launch_bounds__(NW_THREADS) void nw_align_kernel(const int32_t* __r
 	extern __shared__ __align__(16) int nw_smem[];
 	const int lane = threadIdx.x;
 	const int pair = blockIdx.x;
-	const int la = nw_clamp(a_lengths[pair], La), lb = nw_clamp(b_lengths[pair], Lb);
+	const int la = clamp_len(a_lengths[pair], La), lb = clamp_len(b_lengths[pair], Lb);
 	const int32_t* pa = a + (size_t)pair * La;
 	const int32_t* pb = b + (size_t)pair * Lb;
 	const int CB = (Lb + NW_THREADS - 1) / NW_THREADS;

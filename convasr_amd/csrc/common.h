@@ -118,16 +118,7 @@ template <typename H> __device__ __forceinline__ void split3_store8(H* out, int 
 #define CONVASR_DISPATCH_HALF(dtype, T, ...) do { if ((dtype) == CONVASR_F16) { typedef f16_t T; __VA_ARGS__; } else { typedef bf16_t T; __VA_ARGS__; } } while (0)
 static inline bool convasr_is_half(int dtype) { return dtype == CONVASR_BF16 || dtype == CONVASR_F16; }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-	return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-	return v;
-}
+#include "wave.h"
 
 // Dynamic loss scaler (fp16 training; the role of apex.amp's LossScaler behind train.py:770-772): state = CONVASR_LOSS_SCALER_FLOATS
 // floats on the device, read by the loss head (backward seed x scale), the gradient-norm kernel and the fused optimizer steps

@@ -10,7 +10,7 @@
 // of the frame it needs, the producer never waits, so nothing can deadlock), and the consumer trails its producer by about a frame.
 // (Measured alternatives: six waves with a workgroup barrier per frame 0.40 ms, six polled waves 0.43 ms -- waves that share a SIMD
 // share its issue slots.)  The parity of a state is the register it lives in, so a blank's update is a two-term log-sum-exp; the
-// s-1 / s-2 neighbours are registers and one DPP wave shift (two for beta).  "Impossible" is the finite sentinel CTC_NEG = -1e30, not
+// s-1 / s-2 neighbours are registers and one DPP wave shift (two for beta).  "Impossible" is the finite sentinel LOG2_NEG = -1e30, not
 // -inf: max + log2(sum of exp2) then needs no guard against inf - inf, the sentinel absorbs every finite score added to it and
 // exp2(sentinel - anything real) is 0; a log-prob of -inf is staged as the sentinel.
 // log-sum-exp in fp32 in BASE 2 (v_exp_f32 and v_log_f32 are base-2 instructions: log-probs are scaled by log2(e) once while they are
@@ -24,11 +24,8 @@
 // Kernel 2 -- one wave per frame: posterior[c] = sum_{s: l'_s = c} exp2(alpha + beta - total - lp) accumulated in LDS bins,
 // grad = exp(lp) - posterior for t < olen, 0 beyond.
 #include "common.h"
+#include "log2_domain.h"
 
-#define CTC_NEG (-1e30f)
-#define CTC_DEAD (-1e29f)        // anything below is "impossible"
-#define CTC_LOG2E 1.4426950408889634f
-#define CTC_LN2 0.6931471805599453
 #define CTC_RENORM 8
 #define CTC_RENORM_LOG2 3
 #define CTC_EMPTY 0xFFFFFFFFu    // "not written yet": a NaN bit pattern; published words are mapped away from it (ctc_word)
@@ -39,25 +36,11 @@
 // tests/test_training_features_gpu.py): the producing wave of every sweep "dies" at that frame -- it never publishes the frame's edge states -- so that
 // the consumer's give-up path runs: the loss of every utterance long enough must come out NaN, and the launch must end.
 
-// base-2 log-sum-exp of three / two values >= the sentinel.  The largest term is exp2(0) = 1 exactly, so only the other terms go
-// through v_exp_f32 (max3 / med3 / min3 are single instructions): 3 transcendental instructions per label state, 2 per blank state.
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-	const float m = fmaxf(a, fmaxf(b, c));
-	const float md = __builtin_amdgcn_fmed3f(a, b, c), lo = fminf(a, fminf(b, c));
-	return m + __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(md - m) + __builtin_amdgcn_exp2f(lo - m));
-}
+// base-2 log-sum-exp of two values >= the sentinel, lse3_med3's companion: 3 transcendental instructions per label state, 2 per blank state.
 __device__ __forceinline__ float lse2(float a, float b) {
 	// max / min as v_med3_f32 with +-inf: fmaxf / fminf first canonicalise both operands (one v_max_f32 x, x each) under IEEE rules
 	const float m = __builtin_amdgcn_fmed3f(a, b, INFINITY);
 	return m + __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(a, b, -INFINITY) - m));
-}
-
-// lane i <- lane i - 1 (lane 0 <- fill) / lane i <- lane i + 1 (lane 63 <- fill): one DPP move, no LDS round trip
-__device__ __forceinline__ float wave_shr1(float v, float fill) {
-	return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_shl1(float v, float fill) {
-	return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
 }
 
 // max over the 64 lanes by DPP moves (two quad permutes, the two row mirrors, the two row broadcasts) and one readlane: no LDS round
@@ -73,10 +56,6 @@ __device__ __forceinline__ float wave_max_dpp(float v) {
 #undef CTC_DPP_MAX
 	return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
-
-
-// -inf (and anything below the sentinel) becomes the sentinel; a NaN stays a NaN (fmaxf would drop it)
-__device__ __forceinline__ float ctc_floor(float v) { return v < CTC_NEG ? CTC_NEG : v; }
 
 __device__ __forceinline__ uint32_t ctc_word(float v) {
 	const uint32_t b = __builtin_bit_cast(uint32_t, v);
@@ -132,7 +111,7 @@ __device__ __forceinline__ void ctc_sweep(const CtcSweep& q) {
 		// a label state may take the s-2 (alpha) / s+2 (beta) transition when its neighbour label differs
 		skip[i] = nb && (FWD ? (s >= 3 && q.tg[s >> 1] != q.tg[(s >> 1) - 1]) : (s + 2 < L && q.tg[s >> 1] != q.tg[(s >> 1) + 1]));
 	}
-	auto score = [&](float v, int i) { return LP_LDS ? v : (valid[i] ? ctc_floor(v * CTC_LOG2E) : CTC_NEG); };
+	auto score = [&](float v, int i) { return LP_LDS ? v : (valid[i] ? log2_floor(v * LOG2_E) : LOG2_NEG); };
 	constexpr bool consumes = CONSUMES;   // wave 1 of alpha / wave 0 of beta
 	const bool edge_lane = FWD ? lane == 63 : lane == 0;
 	float* lat = q.lat + s0;
@@ -154,7 +133,7 @@ __device__ __forceinline__ void ctc_sweep(const CtcSweep& q) {
 		for (int i = 0; i < NS; ++i) {
 			const int s = s0 + i;
 			// alpha(0, s) is non-zero for s < 2, beta(Tb-1, s) for s >= L - 2
-			a[i] = ((FWD ? s < 2 : s >= L - 2) && valid[i]) ? score(row[cls[i]], i) : CTC_NEG;
+			a[i] = ((FWD ? s < 2 : s >= L - 2) && valid[i]) ? score(row[cls[i]], i) : LOG2_NEG;
 		}
 		store_states<NS>(lat + (int64_t)t0 * LP, a);
 		if (lane == 0) { q.off[0] = 0.f; if (!consumes) slot_store(q.ecum, ctc_word(0.f)); }
@@ -170,7 +149,7 @@ __device__ __forceinline__ void ctc_sweep(const CtcSweep& q) {
 		// the states beyond the wave's edge as their owner left them in the previous frame, converted to this wave's offset.  The slot was
 		// read one frame ahead (x0, x1): once this wave trails its producer by a full frame the read-ahead always finds the slot filled
 		// and the LDS round trip is off the frame's critical path; until then it re-reads here.
-		float e0 = CTC_NEG, e1 = CTC_NEG;
+		float e0 = LOG2_NEG, e1 = LOG2_NEG;
 		if (consumes) {
 			const uint32_t* e = q.edge + (int64_t)(t - dt) * EW;
 			if (__builtin_expect(x0 == CTC_EMPTY || x1 == CTC_EMPTY, 0)) {
@@ -197,22 +176,22 @@ __device__ __forceinline__ void ctc_sweep(const CtcSweep& q) {
 		}
 		float n[NS];
 		if (FWD) {
-			float p1 = wave_shr1(a[NS - 1], CTC_NEG);   // state s0 - 1
+			float p1 = wave_shr1(a[NS - 1], LOG2_NEG);   // state s0 - 1
 			if (lane == 0) p1 = e0;
 #pragma unroll
 			for (int i = NS - 1; i >= 0; --i) {
 				const float m1 = i >= 1 ? a[i >= 1 ? i - 1 : 0] : p1;
 				const float m2 = i >= 2 ? a[i >= 2 ? i - 2 : 0] : p1;   // i == 1: state s0 - 1 again; i == 0 is a blank
-				n[i] = ((i & 1) ? lse3(a[i], m1, skip[i] ? m2 : CTC_NEG) : lse2(a[i], m1)) + cur[i];
+				n[i] = ((i & 1) ? lse3_med3(a[i], m1, skip[i] ? m2 : LOG2_NEG) : lse2(a[i], m1)) + cur[i];
 			}
 		} else {
-			float q0 = wave_shl1(a[0], CTC_NEG), q1 = wave_shl1(a[1], CTC_NEG);   // states s0 + NS, s0 + NS + 1
+			float q0 = wave_shl1(a[0], LOG2_NEG), q1 = wave_shl1(a[1], LOG2_NEG);   // states s0 + NS, s0 + NS + 1
 			if (lane == 63) { q0 = e0; q1 = e1; }
 #pragma unroll
 			for (int i = 0; i < NS; ++i) {
 				const float m1 = i + 1 < NS ? a[i + 1 < NS ? i + 1 : 0] : q0;
 				const float m2 = i + 2 < NS ? a[i + 2 < NS ? i + 2 : 0] : q1;   // i == NS - 1; i == NS - 2 is a blank
-				n[i] = ((i & 1) ? lse3(a[i], m1, skip[i] ? m2 : CTC_NEG) : lse2(a[i], m1)) + cur[i];
+				n[i] = ((i & 1) ? lse3_med3(a[i], m1, skip[i] ? m2 : LOG2_NEG) : lse2(a[i], m1)) + cur[i];
 			}
 		}
 		if ((k & (CTC_RENORM - 1)) == 0) {
@@ -220,7 +199,7 @@ __device__ __forceinline__ void ctc_sweep(const CtcSweep& q) {
 #pragma unroll
 			for (int i = 1; i < NS; ++i) m = fmaxf(m, n[i]);
 			m = wave_max_dpp(m);
-			if (m > CTC_DEAD && m < INFINITY) {
+			if (m > LOG2_DEAD && m < INFINITY) {
 				const float kk = floorf(m);
 #pragma unroll
 				for (int i = 0; i < NS; ++i) n[i] -= kk;
@@ -275,7 +254,7 @@ __global__ __launch_bounds__(256) void ctc_alpha_beta_kernel(const float* __rest
 		const int n = Tb * (C + 1);
 		for (int i = threadIdx.x; i < n; i += blockDim.x) {
 			const int t = i / (C + 1), c = i - t * (C + 1);
-			lpl[i] = c < C ? ctc_floor(lpg[(int64_t)t * C + c] * CTC_LOG2E) : CTC_NEG;
+			lpl[i] = c < C ? log2_floor(lpg[(int64_t)t * C + c] * LOG2_E) : LOG2_NEG;
 		}
 	}
 	__syncthreads();
@@ -299,10 +278,10 @@ __global__ __launch_bounds__(256) void ctc_alpha_beta_kernel(const float* __rest
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		const float c1 = fcum[L - 1 >= 128 * NPH];
-		const float l1 = fin[L - 1], l2 = L >= 2 ? fin[L - 2] + (fcum[L - 2 >= 128 * NPH] - c1) : CTC_NEG;
+		const float l1 = fin[L - 1], l2 = L >= 2 ? fin[L - 2] + (fcum[L - 2 >= 128 * NPH] - c1) : LOG2_NEG;
 		const float m = fmaxf(l1, l2);
 		const float rem = m + log2f(exp2f(l1 - m) + exp2f(l2 - m));
-		nll[b] = fcum[2] != 0.f ? NAN : (m > CTC_DEAD ? (float)(-CTC_LN2 * ((double)c1 + (double)rem)) : INFINITY);   // NaN log-probs: NaN (as the reference)
+		nll[b] = fcum[2] != 0.f ? NAN : (m > LOG2_DEAD ? (float)(-LOG2_LN2 * ((double)c1 + (double)rem)) : INFINITY);   // NaN log-probs: NaN (as the reference)
 		tot[2 * b] = c1;
 		tot[2 * b + 1] = rem;
 	}
@@ -338,14 +317,14 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
 		// alpha + beta - total = (lattice values - remainder of total) + (offsets - integer part of total): the second group is exact
 		const float ti = tot[2 * b], tr = tot[2 * b + 1];
 		const float oa0 = oa[0] - ti, oa1 = oa[NB] - ti, ob0 = ob[0], ob1 = ob[NB];
-		const float lpb = row[blank] * CTC_LOG2E;
+		const float lpb = row[blank] * LOG2_E;
 		float blank_sum = 0.f;
 		for (int s = lane; s < L; s += 64) {
 			const float shift = ((s >= split_a ? oa1 : oa0) + (s >= split_b ? ob1 : ob0)) - tr;
 			const float ab = ar[s] + br[s];
 			if (s & 1) {
 				const int c = (int)tg[s >> 1];
-				atomicAdd(mybins + c, __builtin_amdgcn_exp2f(ab + (shift - row[c] * CTC_LOG2E)));
+				atomicAdd(mybins + c, __builtin_amdgcn_exp2f(ab + (shift - row[c] * LOG2_E)));
 			} else blank_sum += __builtin_amdgcn_exp2f(ab + (shift - lpb));
 		}
 		blank_sum = wave_sum(blank_sum);

@@ -2,7 +2,7 @@
 // runs one workgroup per utterance and stops at 1,023 labels (16 label pairs per lane) and ~12,000 frames (its per-frame hand-over
 // slots live in LDS); ten minutes of speech are ~30,000 frames against ~9,000 labels = ~18,000 states.
 //
-// The alpha-beta recursion is that of ctc.hip -- fp32 log-sum-exp in base 2, the finite sentinel CL_NEG for "impossible", a -inf
+// The alpha-beta recursion is that of ctc.hip -- fp32 log-sum-exp in base 2, the finite sentinel LOG2_NEG for "impossible", a -inf
 // log-prob staged as the sentinel -- cut like csrc/align_long.hip cuts the alignment: tiles of CL_SB consecutive states (a "block") x
 // `chunk` consecutive frames, one wave per tile, lane l owning states s0 + 4 l .. s0 + 4 l + 3.  An alpha tile depends on the tile before
 // it in time (the carried column), on the tile of the block to its left and on the one diagonally before-left (the last state of the left
@@ -27,11 +27,8 @@
 // Gradient: one wave per frame reduces exp2(alpha + beta - total - lp) over the states that both sweeps reach into LDS bins per class
 // (ctc_grad_kernel's arithmetic with per-block offsets), grad = exp(lp) - posterior for t < olen, 0 beyond.  No atomics on global memory.
 #include "common.h"
+#include "log2_domain.h"
 
-#define CL_NEG (-1e30f)
-#define CL_DEAD (-1e29f)
-#define CL_LOG2E 1.4426950408889634f
-#define CL_LN2 0.6931471805599453
 #define CL_RENORM 8                   // frames between renormalisations (a power of two), as in ctc.hip
 #define CL_NS 4                       // states per lane (even: a lane starts on a blank)
 #define CL_SB (64 * CL_NS)            // states per block
@@ -43,12 +40,7 @@
 #define CL_MAX_CLASSES 8192
 #define CL_MAX_BATCH 65535            // grid.y
 
-// base-2 log-sum-exp of values >= the sentinel (ctc.hip: the largest term is exp2(0) = 1 exactly)
-__device__ __forceinline__ float cl_lse3(float a, float b, float c) {
-	const float m = fmaxf(a, fmaxf(b, c));
-	const float md = __builtin_amdgcn_fmed3f(a, b, c), lo = fminf(a, fminf(b, c));
-	return m + __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(md - m) + __builtin_amdgcn_exp2f(lo - m));
-}
+// base-2 log-sum-exp of two values >= the sentinel (lse3_med3's companion: the largest term is exp2(0) = 1 exactly)
 __device__ __forceinline__ float cl_lse2(float a, float b) {
 	const float m = fmaxf(a, b);
 	return m + __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(fminf(a, b) - m));
@@ -98,10 +90,10 @@ __device__ __forceinline__ void cl_tile(const ClSweep& q, int j, int c, int b) {
 	}
 	bool saw_nan = false;
 	auto score = [&](float v, int i) {
-		if (!valid[i]) return CL_NEG;
+		if (!valid[i]) return LOG2_NEG;
 		saw_nan |= v != v;
-		v *= CL_LOG2E;
-		return v < CL_NEG ? CL_NEG : v;  // -inf becomes the sentinel, a NaN stays a NaN
+		v *= LOG2_E;
+		return log2_floor(v);
 	};
 	float a[NS], r[NS], cum;
 	// renormalise at the frames the absolute index names, then store the frame's states and the block's running offset
@@ -109,7 +101,7 @@ __device__ __forceinline__ void cl_tile(const ClSweep& q, int j, int c, int b) {
 		if ((t & (CL_RENORM - 1)) == 0) {
 			float m = fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3]));
 			m = wave_max(m);
-			if (m > CL_DEAD && m < INFINITY) {
+			if (m > LOG2_DEAD && m < INFINITY) {
 				const float kk = floorf(m);
 #pragma unroll
 				for (int i = 0; i < NS; ++i) a[i] -= kk;
@@ -124,7 +116,7 @@ __device__ __forceinline__ void cl_tile(const ClSweep& q, int j, int c, int b) {
 	if (FWD ? c == 0 : t_end == Tb) {
 		const float* row = lpb + (int64_t)t_first * C;
 #pragma unroll
-		for (int i = 0; i < NS; ++i) a[i] = (FWD ? sl + i < 2 : sl + i >= L - 2) ? score(row[cls[i]], i) : CL_NEG;
+		for (int i = 0; i < NS; ++i) a[i] = (FWD ? sl + i < 2 : sl + i >= L - 2) ? score(row[cls[i]], i) : LOG2_NEG;
 		cum = 0.f;
 		finish(t_first);
 		t = FWD ? 1 : Tb - 2;
@@ -133,7 +125,7 @@ __device__ __forceinline__ void cl_tile(const ClSweep& q, int j, int c, int b) {
 		const float4 v = *reinterpret_cast<const float4*>(lat + tc * LP + sl);  // (inside the workspace whether or not it was written)
 		const float vv[NS] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-		for (int i = 0; i < NS; ++i) a[i] = (FWD ? (int64_t)(sl + i) > 2 * tc + 1 : cl_dead_b(sl + i, tc, L, Tb)) ? CL_NEG : vv[i];
+		for (int i = 0; i < NS; ++i) a[i] = (FWD ? (int64_t)(sl + i) > 2 * tc + 1 : cl_dead_b(sl + i, tc, L, Tb)) ? LOG2_NEG : vv[i];
 		cum = (FWD ? (int64_t)s0 > 2 * tc + 1 : cl_dead_b(s_hi, tc, L, Tb)) ? 0.f : off[tc];  // (the tile that would have written it did not run)
 		t = FWD ? t_begin : t_end - 1;
 	}
@@ -146,7 +138,7 @@ __device__ __forceinline__ void cl_tile(const ClSweep& q, int j, int c, int b) {
 	}
 	for (int done = 0; done < n_left; done += 64) {
 		// lane l fetches what the edge lane needs at this batch's l-th frame: the neighbouring block's edge state(s) at the frame before it in the sweep
-		float q0 = CL_NEG, q1 = CL_NEG, qo = 0.f;
+		float q0 = LOG2_NEG, q1 = LOG2_NEG, qo = 0.f;
 		const int n_here = min(64, n_left - done);
 		if (lane < n_here) {
 			const int64_t tp = (int64_t)t + dt * lane - dt;
@@ -171,17 +163,17 @@ __device__ __forceinline__ void cl_tile(const ClSweep& q, int j, int c, int b) {
 				const float e0 = __shfl(q0, ii, 64) + d;
 				if (lane == 0) p1 = e0;
 				n[0] = cl_lse2(a[0], p1) + r[0];
-				n[1] = cl_lse3(a[1], a[0], skip[1] ? p1 : CL_NEG) + r[1];
+				n[1] = lse3_med3(a[1], a[0], skip[1] ? p1 : LOG2_NEG) + r[1];
 				n[2] = cl_lse2(a[2], a[1]) + r[2];
-				n[3] = cl_lse3(a[3], a[2], skip[3] ? a[1] : CL_NEG) + r[3];
+				n[3] = lse3_med3(a[3], a[2], skip[3] ? a[1] : LOG2_NEG) + r[3];
 			} else {
 				float p0 = __shfl_down(a[0], 1, 64), p1 = __shfl_down(a[1], 1, 64);  // states sl + NS, sl + NS + 1
 				const float e0 = __shfl(q0, ii, 64) + d, e1 = __shfl(q1, ii, 64) + d;
 				if (lane == 63) { p0 = e0; p1 = e1; }
 				n[0] = cl_lse2(a[0], a[1]) + r[0];
-				n[1] = cl_lse3(a[1], a[2], skip[1] ? a[3] : CL_NEG) + r[1];
+				n[1] = lse3_med3(a[1], a[2], skip[1] ? a[3] : LOG2_NEG) + r[1];
 				n[2] = cl_lse2(a[2], a[3]) + r[2];
-				n[3] = cl_lse3(a[3], p0, skip[3] ? p1 : CL_NEG) + r[3];
+				n[3] = lse3_med3(a[3], p0, skip[3] ? p1 : LOG2_NEG) + r[3];
 			}
 #pragma unroll
 			for (int i = 0; i < NS; ++i) a[i] = n[i];
@@ -215,12 +207,12 @@ __global__ void ctc_long_total_kernel(ClSweep q, float* __restrict__ nll, float*
 	const float* row = q.alpha + ((int64_t)b * T + (Tb - 1)) * q.LP;
 	const float* off = q.off_a + (int64_t)b * q.nblocks * T + (Tb - 1);
 	const int64_t reach = 2 * ((int64_t)Tb - 1) + 1;
-	float l1 = CL_NEG, l2 = CL_NEG, c1 = 0.f;
+	float l1 = LOG2_NEG, l2 = LOG2_NEG, c1 = 0.f;
 	if (L - 1 <= reach) { l1 = row[L - 1]; c1 = off[(int64_t)((L - 1) / CL_SB) * T]; }
 	if (L >= 2 && L - 2 <= reach) l2 = row[L - 2] + (off[(int64_t)((L - 2) / CL_SB) * T] - c1);
 	const float m = fmaxf(l1, l2);
 	const float rem = m + log2f(exp2f(l1 - m) + exp2f(l2 - m));
-	nll[b] = q.nan_flag[b] != 0.f ? NAN : (m > CL_DEAD ? (float)(-CL_LN2 * ((double)c1 + (double)rem)) : INFINITY);  // NaN log-probs: NaN (as the reference)
+	nll[b] = q.nan_flag[b] != 0.f ? NAN : (m > LOG2_DEAD ? (float)(-LOG2_LN2 * ((double)c1 + (double)rem)) : INFINITY);  // NaN log-probs: NaN (as the reference)
 	tot[2 * b] = c1;
 	tot[2 * b + 1] = rem;
 }
@@ -250,7 +242,7 @@ __global__ __launch_bounds__(256) void ctc_long_grad_kernel(ClSweep q, const flo
 		const float* ob = q.off_b + (int64_t)b * q.nblocks * T + t;
 		// alpha + beta - total = (lattice values - remainder of total) + (offsets - integer part of total): the second group is exact
 		const float ti = tot[2 * b], tr = tot[2 * b + 1];
-		const float lpb = row[blank] * CL_LOG2E;
+		const float lpb = row[blank] * LOG2_E;
 		// the states both sweeps reach at this frame (the others hold the sentinel, or nothing at all): posterior 0
 		const int64_t lo64 = (int64_t)L - 2 - 2 * ((int64_t)Tb - 1 - t), hi64 = 2 * (int64_t)t + 1;
 		const int s_lo = lo64 > 0 ? (int)lo64 : 0, s_hi = hi64 < L - 1 ? (int)hi64 : L - 1;
@@ -261,7 +253,7 @@ __global__ __launch_bounds__(256) void ctc_long_grad_kernel(ClSweep q, const flo
 			const float ab = ar[s] + br[s];
 			if (s & 1) {
 				const int c = (int)tg[s >> 1];
-				if ((unsigned)c < (unsigned)C) atomicAdd(mybins + c, __builtin_amdgcn_exp2f(ab + (shift - row[c] * CL_LOG2E)));
+				if ((unsigned)c < (unsigned)C) atomicAdd(mybins + c, __builtin_amdgcn_exp2f(ab + (shift - row[c] * LOG2_E)));
 			} else blank_sum += __builtin_amdgcn_exp2f(ab + (shift - lpb));
 		}
 		blank_sum = wave_sum(blank_sum);

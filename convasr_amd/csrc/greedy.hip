@@ -28,38 +28,6 @@ constexpr int GS_TILES = 4;
 constexpr int GS_CHUNK = GS_THREADS * GS_TILES;
 constexpr int GS_WS_ARRAYS = 10;
 
-// DPP move with bound_ctrl off: a lane whose source lies outside its row, or whose row is masked off, gets `old`
-template <int CTRL, int ROWS = 0xf>
-__device__ __forceinline__ int gs_dpp(int old, int src) {
-	return __builtin_amdgcn_update_dpp(old, src, CTRL, ROWS, 0xf, false);
-}
-
-// inclusive prefix maximum over the 64 lanes of values >= -1
-__device__ __forceinline__ int gs_prefix_max(int x) {
-	x = max(x, gs_dpp<0x111>(-1, x));
-	x = max(x, gs_dpp<0x112>(-1, x));
-	x = max(x, gs_dpp<0x114>(-1, x));
-	x = max(x, gs_dpp<0x118>(-1, x));
-	x = max(x, gs_dpp<0x142, 0xa>(-1, x));  // row_bcast:15 into rows 1 and 3
-	x = max(x, gs_dpp<0x143, 0xc>(-1, x));  // row_bcast:31 into rows 2 and 3
-	return x;
-}
-
-// inclusive prefix sum over the 64 lanes (modulo 2^32)
-__device__ __forceinline__ int gs_prefix_sum(int x) {
-	x += gs_dpp<0x111>(0, x);
-	x += gs_dpp<0x112>(0, x);
-	x += gs_dpp<0x114>(0, x);
-	x += gs_dpp<0x118>(0, x);
-	x += gs_dpp<0x142, 0xa>(0, x);
-	x += gs_dpp<0x143, 0xc>(0, x);
-	return x;
-}
-
-__device__ __forceinline__ int gs_clamp_len(int64_t n, int hi) { return n < 0 ? 0 : n > hi ? hi : (int)n; }
-__device__ __forceinline__ int gs_lane_rank(uint64_t mask) {  // set bits of mask below this lane
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 __device__ __forceinline__ int gs_top(uint64_t mask) { return 63 - __clzll((long long)mask); }  // highest set bit, mask != 0
 
 // the workspace: GS_WS_ARRAYS arrays of `stride` ints
@@ -84,7 +52,7 @@ __global__ __launch_bounds__(GS_THREADS) void gs_summary_kernel(const int64_t* _
                                                                 int64_t eps, int64_t space) {
 	const int i = blockIdx.x, b = i / nch, c = i - b * nch, lane = threadIdx.x;
 	const int64_t* p = path + (int64_t)b * T;
-	const int n = gs_clamp_len(lengths[b], T);
+	const int n = clamp_len(lengths[b], T);
 	const int64_t base = (int64_t)c * GS_CHUNK;
 	int last = -1, first = -1;
 #pragma unroll
@@ -108,9 +76,9 @@ __global__ __launch_bounds__(GS_THREADS) void gs_carry_kernel(const int* __restr
 	int run_nb = -1, run_ns = -1;
 	for (int64_t base = 0; base < N; base += GS_THREADS) {
 		const int64_t i = base + lane;
-		const int nb = max(gs_prefix_max(i < N ? last_nb[i] : -1), run_nb);
-		const int ns = max(gs_prefix_max(i < N ? first_ns[i] : -1), run_ns);
-		const int before = gs_dpp<0x138>(run_nb, nb);  // wave_shr:1, lane 0 <- the chunks before this step
+		const int nb = max(wave_prefix_max(i < N ? last_nb[i] : -1, -1), run_nb);   // (every value is >= -1)
+		const int ns = max(wave_prefix_max(i < N ? first_ns[i] : -1, -1), run_ns);
+		const int before = wave_dpp<0x138>(run_nb, nb);  // wave_shr:1, lane 0 <- the chunks before this step
 		if (i < N) {
 			carry_nb[i] = before;
 			start[i] = ns;
@@ -128,9 +96,9 @@ __global__ __launch_bounds__(GS_THREADS) void gs_offsets_kernel(const int* __res
 	for (int64_t base = 0; base < N; base += GS_THREADS) {
 		const int64_t i = base + lane;
 		const int nt = i < N ? ntok[i] : 0, ns = i < N ? nseg[i] : 0;
-		const int tok = gs_prefix_sum(nt) + run_tok, seg = gs_prefix_sum(ns) + run_seg;
-		const int pe = max(gs_prefix_max(i < N ? last_pe[i] : -1), run_pe);
-		const int before = gs_dpp<0x138>(run_pe, pe);
+		const int tok = wave_prefix_sum(nt, 0) + run_tok, seg = wave_prefix_sum(ns, 0) + run_seg;
+		const int pe = max(wave_prefix_max(i < N ? last_pe[i] : -1, -1), run_pe);
+		const int before = wave_dpp<0x138>(run_pe, pe);
 		if (i < N) {
 			tok_off[i] = tok - nt;
 			seg_off[i] = seg - ns;
@@ -156,7 +124,7 @@ __global__ __launch_bounds__(GS_THREADS) void gs_emit_kernel(const int64_t* __re
                                                              int64_t eps, int64_t space, int gap, int split) {
 	const int i = blockIdx.x, b = i / nch, c = i - b * nch, lane = threadIdx.x;
 	const int64_t* p = path + (int64_t)b * T;
-	const int n = gs_clamp_len(lengths[b], T);
+	const int n = clamp_len(lengths[b], T);
 	const int flat0 = b * T;
 	const int64_t base = (int64_t)c * GS_CHUNK;
 	const int mirrored = w.start[i];
@@ -209,7 +177,7 @@ __global__ __launch_bounds__(GS_THREADS) void gs_emit_kernel(const int64_t* __re
 			const bool open = first || dbl;
 			const uint64_t em = __ballot(pe || ins), dm = __ballot(dbl), om = __ballot(open), pem = __ballot(pe);
 			if (WRITE) {
-				const size_t r = (size_t)tok + gs_lane_rank(em) + gs_lane_rank(dm);
+				const size_t r = (size_t)tok + lane_rank(em) + lane_rank(dm);
 				if (pe || ins) {
 					tokens[r] = ins ? space : cls;
 					frames[r] = t;
@@ -219,7 +187,7 @@ __global__ __launch_bounds__(GS_THREADS) void gs_emit_kernel(const int64_t* __re
 					frames[r + 1] = t;
 				}
 				if (open) {
-					const int s = seg + gs_lane_rank(om);
+					const int s = seg + lane_rank(om);
 					seg_first[s] = (int64_t)r;
 					seg_begin[s] = t;
 					if (!first) {  // a space from the path closes the segment before it, at the last frame emitted from the path

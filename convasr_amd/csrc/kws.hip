@@ -64,11 +64,6 @@ __device__ __forceinline__ float kws_d(float v, float m) {
 	return d != d ? -INFINITY : d;
 }
 
-// lane i takes lane i - 1's value: one v_mov_b32 under the DPP control wave_shr:1 (0x138), no trip through the LDS crossbar as __shfl_up's
-// ds_bpermute_b32 makes.  Lane 0 keeps `old`; the caller replaces it.
-__device__ __forceinline__ int kws_lane_below(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ float kws_lane_below(float v) { return __int_as_float(kws_lane_below(__float_as_int(v))); }
-
 // One frame.  Written with & and | on the comparisons' results, not && and ||: hipcc turns the short-circuit forms into divergent branches
 // (an exec-mask save, a scalar branch and a restore each), which cost the first version of this step ~170 instructions and ~900 cycles a frame.
 template <bool DENSE>
@@ -79,8 +74,9 @@ __device__ __forceinline__ void kws_step(KwsWave& w, const KwsArgs& p, float dy,
 	const float ms = a_wins ? w.a : w.z;
 	const int mb = a_wins ? w.ab : w.zb;
 	// what the next label may take: the blank after this label, and this label itself unless the next one repeats it
-	float rs = kws_lane_below(next_differs ? ms : w.z);
-	int rb = kws_lane_below(next_differs ? mb : w.zb);
+	// (lane i takes lane i - 1's: one DPP move, no trip through the LDS crossbar as __shfl_up's ds_bpermute_b32 makes; lane 0 is replaced below)
+	float rs = wave_shr1(next_differs ? ms : w.z, 0.f);
+	int rb = wave_dpp<0x138>(0, next_differs ? mb : w.zb);
 	rs = lane == 0 ? 0.f : rs;  // a span may open at every frame
 	rb = lane == 0 ? t : rb;
 	w.z = ms + db;

@@ -41,23 +41,6 @@ __device__ __forceinline__ uint64_t ed_mix(uint64_t x) {
 	return x;
 }
 
-// DPP move with bound_ctrl off: a lane whose source lies outside its row, or whose row is masked off, gets `old`
-template <int CTRL, int ROWS = 0xf>
-__device__ __forceinline__ int ed_dpp(int old, int src) {
-	return __builtin_amdgcn_update_dpp(old, src, CTRL, ROWS, 0xf, false);
-}
-
-// inclusive prefix minimum over the 64 lanes: row_shr 1, 2, 4, 8 inside each row of 16, then the two row broadcasts; no LDS round trip
-__device__ __forceinline__ int ed_prefix_min(int x) {
-	x = min(x, ed_dpp<0x111>(ED_BIG, x));
-	x = min(x, ed_dpp<0x112>(ED_BIG, x));
-	x = min(x, ed_dpp<0x114>(ED_BIG, x));
-	x = min(x, ed_dpp<0x118>(ED_BIG, x));
-	x = min(x, ed_dpp<0x142, 0xa>(ED_BIG, x));  // row_bcast:15 into rows 1 and 3
-	x = min(x, ed_dpp<0x143, 0xc>(ED_BIG, x));  // row_bcast:31 into rows 2 and 3
-	return x;
-}
-
 // The row DP with the row in registers: lane l holds columns j = 1 + 64 c + l, c < R (column 0 is i).  hid: hypothesis ids (LDS),
 // rid: reference ids (LDS); 1 <= nh <= 64 R, nr >= 1.  Columns past nh compute garbage that no valid column reads: a valid column's
 // diagonal comes from the column before it, also valid.
@@ -77,8 +60,8 @@ __device__ int ed_dp_regs(const uint16_t* hid, const uint16_t* rid, int nh, int 
 #pragma unroll
 		for (int c = 0; c < R; ++c) {  // independent scans: D[i-1] is all they read
 			const int j = 1 + ED_THREADS * c + lane;
-			const int diag = ed_dpp<0x138>(c == 0 ? i - 1 : __builtin_amdgcn_readlane(up[c - 1], ED_THREADS - 1), up[c]);
-			x[c] = ed_prefix_min(j <= nh ? min(up[c] + 1, diag + (id[c] != r)) - j : ED_BIG);
+			const int diag = wave_dpp<0x138>(c == 0 ? i - 1 : __builtin_amdgcn_readlane(up[c - 1], ED_THREADS - 1), up[c]);
+			x[c] = wave_prefix_min(j <= nh ? min(up[c] + 1, diag + (id[c] != r)) - j : ED_BIG, ED_BIG);
 		}
 		int run = i;
 #pragma unroll
@@ -96,12 +79,6 @@ __device__ int ed_dp_regs(const uint16_t* hid, const uint16_t* rid, int nh, int 
 	return __shfl(d, (nh - 1) % ED_THREADS);
 }
 
-__device__ __forceinline__ int clamp_len(int64_t n, int hi) { return n < 0 ? 0 : n > hi ? hi : (int)n; }
-
-__device__ __forceinline__ int ed_lane_rank(uint64_t mask) {  // set bits of mask below this lane
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
 // Compacts the units of tok[0, L).  CHARS: pos[u] = position of unit u.  WORDS: pos[w] = first token of word w, len[w] = its length.
 // Returns the number of units (uniform across the wave).
 __device__ int ed_units(const int64_t* __restrict__ tok, int L, int mode, int64_t space, uint16_t* pos, uint16_t* len) {
@@ -113,7 +90,7 @@ __device__ int ed_units(const int64_t* __restrict__ tok, int L, int mode, int64_
 		const bool unit = t < L && (all || tok[t] != space);
 		if (mode == CONVASR_METRIC_CHARS) {
 			const uint64_t m = __ballot(unit);
-			if (unit) pos[n_start + ed_lane_rank(m)] = (uint16_t)t;
+			if (unit) pos[n_start + lane_rank(m)] = (uint16_t)t;
 			n_start += __popcll(m);
 			continue;
 		}
@@ -122,8 +99,8 @@ __device__ int ed_units(const int64_t* __restrict__ tok, int L, int mode, int64_
 		if (lane == ED_THREADS - 1) next = t + 1 < L && tok[t + 1] != space;
 		const bool first = unit && !prev, last = unit && !next;
 		const uint64_t ms = __ballot(first), me = __ballot(last);
-		if (first) pos[n_start + ed_lane_rank(ms)] = (uint16_t)t;
-		if (last) len[n_end + ed_lane_rank(me)] = (uint16_t)t;  // the last token for now; made a length below
+		if (first) pos[n_start + lane_rank(ms)] = (uint16_t)t;
+		if (last) len[n_end + lane_rank(me)] = (uint16_t)t;  // the last token for now; made a length below
 		n_start += __popcll(ms);
 		n_end += __popcll(me);
 	}
@@ -208,9 +185,9 @@ __global__ __launch_bounds__(ED_THREADS) void edit_distance_kernel(const int64_t
 				const int j = base + lane;
 				const bool v = j <= nh;
 				const int up = v ? row[j] : ED_BIG;
-				const int diag = ed_dpp<0x138>(diag_carry, up);  // wave_shr:1, lane 0 <- D[i-1][base - 1]
+				const int diag = wave_dpp<0x138>(diag_carry, up);  // wave_shr:1, lane 0 <- D[i-1][base - 1]
 				diag_carry = __builtin_amdgcn_readlane(up, ED_THREADS - 1);
-				const int x = min(ed_prefix_min(v ? min(up + 1, diag + (A[j - 1] != rid)) - j : ED_BIG), run);
+				const int x = min(wave_prefix_min(v ? min(up + 1, diag + (A[j - 1] != rid)) - j : ED_BIG, ED_BIG), run);
 				if (v) row[j] = (uint16_t)(x + j);
 				run = __builtin_amdgcn_readlane(x, ED_THREADS - 1);
 			}

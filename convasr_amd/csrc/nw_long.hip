@@ -39,43 +39,8 @@ struct NwlScores {
 	int match, sub, del, ins;
 };
 
-template <int CTRL, int ROWS = 0xf>
-__device__ __forceinline__ int nwl_dpp(int old, int src) {
-	return __builtin_amdgcn_update_dpp(old, src, CTRL, ROWS, 0xf, false);
-}
-
-// inclusive prefix maximum / minimum over the 64 lanes: row_shr 1, 2, 4, 8 inside each row of 16, then the two row broadcasts
-__device__ __forceinline__ int nwl_prefix_max(int x) {
-	x = max(x, nwl_dpp<0x111>(NWL_NEG, x));
-	x = max(x, nwl_dpp<0x112>(NWL_NEG, x));
-	x = max(x, nwl_dpp<0x114>(NWL_NEG, x));
-	x = max(x, nwl_dpp<0x118>(NWL_NEG, x));
-	x = max(x, nwl_dpp<0x142, 0xa>(NWL_NEG, x));  // row_bcast:15 into rows 1 and 3
-	x = max(x, nwl_dpp<0x143, 0xc>(NWL_NEG, x));  // row_bcast:31 into rows 2 and 3
-	return x;
-}
-__device__ __forceinline__ int nwl_prefix_min(int x) {
-	x = min(x, nwl_dpp<0x111>(NWL_BIG, x));
-	x = min(x, nwl_dpp<0x112>(NWL_BIG, x));
-	x = min(x, nwl_dpp<0x114>(NWL_BIG, x));
-	x = min(x, nwl_dpp<0x118>(NWL_BIG, x));
-	x = min(x, nwl_dpp<0x142, 0xa>(NWL_BIG, x));
-	x = min(x, nwl_dpp<0x143, 0xc>(NWL_BIG, x));
-	return x;
-}
-
-__device__ __forceinline__ int nwl_clamp(int n, int hi) { return n < 0 ? 0 : n > hi ? hi : n; }
-
 // (value, index) as one key: the larger value wins, then the lower index (index < 2^18, |value| < 2^29: |key| < 2^48)
 __device__ __forceinline__ long long nwl_key(int value, int index) { return (long long)value * 262144 + (0x3FFFF - index); }
-
-__device__ __forceinline__ long long nwl_wave_max(long long k) {
-	for (int off = 32; off >= 1; off >>= 1) {
-		const long long o = __shfl_xor(k, off);
-		k = o > k ? o : k;
-	}
-	return k;
-}
 
 // M[.][j] of a register row for the column of chunk `which`, lane `at` (both wave-uniform): scalar selects over four readlanes (an
 // indexed read of the register row would be moved to LDS by the compiler)
@@ -102,8 +67,8 @@ __device__ __forceinline__ NwlTile nwl_tile(const int32_t* a_lengths, const int3
 	if (t.pair >= N) return t;
 	t.ti = ti_lo + (int)blockIdx.x;
 	t.tj = diag - t.ti;
-	t.la = nwl_clamp(a_lengths[t.pair], La);
-	t.lb = nwl_clamp(b_lengths[t.pair], Lb);
+	t.la = clamp_len(a_lengths[t.pair], La);
+	t.lb = clamp_len(b_lengths[t.pair], Lb);
 	t.i0 = t.ti * NWL_T + 1;
 	t.j0 = t.tj * NWL_T + 1;
 	t.i_end = min(t.la, t.i0 + NWL_T - 1);
@@ -151,9 +116,9 @@ __global__ __launch_bounds__(64) void nw_long_fill_kernel(const int32_t* __restr
 #pragma unroll
 		for (int c = 0; c < NWL_C; ++c) {  // independent scans: row i - 1 is all they read
 			const int j = j0 + 64 * c + lane;
-			const int diagv = nwl_dpp<0x138>(c == 0 ? prev_left : __builtin_amdgcn_readlane(up[c > 0 ? c - 1 : 0], 63), up[c]);
+			const int diagv = wave_dpp<0x138>(c == 0 ? prev_left : __builtin_amdgcn_readlane(up[c > 0 ? c - 1 : 0], 63), up[c]);
 			const int e = max(diagv + (id[c] == ai ? s.match : s.sub), up[c] + s.del);
-			x[c] = nwl_prefix_max(j <= lb ? e - j * s.ins : NWL_NEG);
+			x[c] = wave_prefix_max(j <= lb ? e - j * s.ins : NWL_NEG, NWL_NEG);
 		}
 		int run = left_i - (j0 - 1) * s.ins, left_carry = left_i;
 		uint64_t w[2 * NWL_C];
@@ -164,7 +129,7 @@ __global__ __launch_bounds__(64) void nw_long_fill_kernel(const int32_t* __restr
 			const int v = max(x[c], run);
 			run = __builtin_amdgcn_readlane(v, 63);
 			const int m = valid ? v + j * s.ins : 0;
-			const int lft = nwl_dpp<0x138>(left_carry, m);  // wave_shr:1, lane 0 <- M[i][j - 1] of the chunk before
+			const int lft = wave_dpp<0x138>(left_carry, m);  // wave_shr:1, lane 0 <- M[i][j - 1] of the chunk before
 			left_carry = __builtin_amdgcn_readlane(m, 63);
 			const bool is_ins = m == lft + s.ins;
 			const bool is_del = !is_ins && m == up[c] + s.del;
@@ -210,7 +175,7 @@ __global__ __launch_bounds__(64) void nw_long_fill_kernel(const int32_t* __restr
 				k = kj > k ? kj : k;
 			}
 		}
-		k = nwl_wave_max(k);
+		k = wave_max(k);
 		if (lane == 0) ek[tj] = k;
 	}
 }
@@ -222,7 +187,7 @@ __global__ __launch_bounds__(64) void nw_long_walk_kernel(const int32_t* __restr
 	__shared__ __align__(16) uint64_t win[NWL_TILE_WORDS];
 	const int lane = threadIdx.x;
 	const int pair = blockIdx.x;
-	const int la = nwl_clamp(a_lengths[pair], La), lb = nwl_clamp(b_lengths[pair], Lb);
+	const int la = clamp_len(a_lengths[pair], La), lb = clamp_len(b_lengths[pair], Lb);
 	const uint64_t* dp = dirs + (size_t)pair * nTi * nTj * NWL_TILE_WORDS;
 	int2* walk = walk_base + (size_t)pair * (La + Lb);
 
@@ -232,7 +197,7 @@ __global__ __launch_bounds__(64) void nw_long_walk_kernel(const int32_t* __restr
 		const int n = (la < lb ? lb - 1 : la - 1) / NWL_T + 1;
 		const long long* ek = endk + (size_t)pair * nEnd;
 		for (int k = lane; k < n; k += 64) key = ek[k] > key ? ek[k] : key;
-		key = nwl_wave_max(key);
+		key = wave_max(key);
 	}
 	const int end_index = 0x3FFFF - (int)(key & 0x3FFFF);
 	const int end_score = (int)((key - (key & 0x3FFFF)) / 262144);
@@ -335,8 +300,8 @@ __global__ __launch_bounds__(64) void ed_long_fill_kernel(const int32_t* __restr
 #pragma unroll
 		for (int c = 0; c < NWL_C; ++c) {
 			const int j = j0 + 64 * c + lane;
-			const int diagv = nwl_dpp<0x138>(c == 0 ? prev_left : __builtin_amdgcn_readlane(up[c > 0 ? c - 1 : 0], 63), up[c]);
-			x[c] = nwl_prefix_min(j <= lb ? min(up[c] + 1, diagv + (id[c] != ai)) - j : NWL_BIG);
+			const int diagv = wave_dpp<0x138>(c == 0 ? prev_left : __builtin_amdgcn_readlane(up[c > 0 ? c - 1 : 0], 63), up[c]);
+			x[c] = wave_prefix_min(j <= lb ? min(up[c] + 1, diagv + (id[c] != ai)) - j : NWL_BIG, NWL_BIG);
 		}
 		int run = left_i - (j0 - 1);
 #pragma unroll
@@ -370,7 +335,7 @@ __global__ __launch_bounds__(256) void ed_long_empty_kernel(const int32_t* __res
                                                             int32_t* __restrict__ distance, int N, int La, int Lb) {
 	const int pair = blockIdx.x * 256 + threadIdx.x;
 	if (pair >= N) return;
-	const int la = nwl_clamp(a_lengths[pair], La), lb = nwl_clamp(b_lengths[pair], Lb);
+	const int la = clamp_len(a_lengths[pair], La), lb = clamp_len(b_lengths[pair], Lb);
 	if (la == 0 || lb == 0) distance[pair] = la + lb;
 }
 
