@@ -128,6 +128,11 @@ _SIGNATURES = dict(
 	convasr_ctc_alignment_long_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
 	convasr_ctc_alignment_long = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
 	convasr_ctc_alignment_long_parts = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
+	convasr_star_alignment_states_per_block = (c_int, []),
+	convasr_star_alignment_chunk_frames = (c_int, []),
+	convasr_star_alignment_workspace_bytes = (c_i64, [c_int, c_int, c_int]),
+	convasr_star_alignment = (c_int, [c_p] * 5 + [c_f32, c_f32] + [c_p] * 5 + [c_i64] + [c_int] * 7 + [c_p]),
+	convasr_star_alignment_parts = (c_int, [c_p] * 5 + [c_f32, c_f32] + [c_p] * 5 + [c_i64] + [c_int] * 8 + [c_p]),
 	convasr_ctc_beam_search_workspace_bytes = (c_i64, [c_int] * 6),
 	convasr_ctc_beam_search = (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32, c_int, c_p]),
 	convasr_ctc_beam_search_lm_workspace_bytes = (c_i64, [c_int] * 6),

@@ -1,4 +1,6 @@
 """Host mirror of the reference's ctc.py: forced alignment on the GPU; and this package's own keyword search (`search`)."""
+import types
+
 import torch
 
 from . import ops
@@ -91,8 +93,58 @@ class StarCTC:
 	def mask(self, targets, ylen):
 		return star_gaps(targets, ylen, self.gaps, self.space)
 
+	def align(self, log_probs_bct, targets, input_lengths, target_lengths, blank, chunk_frames: int = 0):
+		"""star_alignment_bct with this object's gaps and costs: where every label of a partial transcript lies in the recording, and which
+		frames the star of every gap absorbed."""
+		targets = targets.to(log_probs_bct.device)
+		return star_alignment_bct(log_probs_bct, targets, input_lengths, target_lengths, blank, self.mask(targets, target_lengths.to(targets.device)), self.penalty, self.enter, chunk_frames = chunk_frames)
+
 	def __repr__(self):
 		return f'StarCTC(gaps = {self.gaps!r}, penalty = {self.penalty}, enter = {self.enter}, space = {self.space})'
+
+
+def star_alignment(log_probs, targets, input_lengths, target_lengths, blank, star_mask, penalty, enter, chunk_frames: int = 0):
+	"""Align a PARTIAL transcript to a whole recording (this package's own; the rule is unpinned against any outside aligner and the costs
+	are untuned): the best path through star_ctc_loss's lattice -- a star, "any stretch of frames, or nothing", in every gap star_mask
+	allows (star_gaps) at `penalty` per frame and `enter` per star used.  log_probs (T, B, C) as `alignment` takes them.  Returns
+	ops.star_ctc_alignment's namespace: alignment (B, S_max) like `alignment`, star_begin / star_frames (B, S_max + 1) -- the frames gap g's
+	star absorbed: audio the transcript does not cover --, score (B,).  Up to 131,071 labels over 2^20 frames.  True max-plus Viterbi, not
+	`alignment`'s log-sum-exp recursion: with an all-false mask the two agree wherever the best path is unambiguous.  A star absorbs audio,
+	not text: words in the transcript that were never spoken are not handled.  include/convasr_hip.h (convasr_star_alignment) has the rule."""
+	return ops.star_ctc_alignment(log_probs.float().permute(1, 0, 2).contiguous(), targets, input_lengths, target_lengths, blank, star_mask, penalty, enter, chunk_frames = chunk_frames)
+
+
+def star_alignment_bct(log_probs_bct, targets, input_lengths, target_lengths, blank, star_mask, penalty, enter, chunk_frames: int = 0):
+	"""Same for the model's own output layout: logical (B, C, T) whose memory is (B, T, C)."""
+	assert ops.is_cl(log_probs_bct)
+	return ops.star_ctc_alignment(log_probs_bct.permute(0, 2, 1).float().contiguous(), targets, input_lengths, target_lengths, blank, star_mask, penalty, enter, chunk_frames = chunk_frames)
+
+
+def star_pieces(result, targets, target_lengths, min_star_frames):
+	"""What a cutter would write from a star alignment (host code over the small outputs).  result: star_alignment's namespace (its
+	input_lengths are read too); targets (B, S_max), target_lengths (B,).  Per utterance a namespace of
+	  stars: the used stars of at least min_star_frames frames, as (gap, begin_frame, end_frame), end inclusive;
+	  pieces: the stretches of the transcript between them, as (first_label, label_count, begin_frame, end_frame): a piece begins on the
+	    first frame after the star before it (the first piece: frame 0) and ends on the last frame before the star after it (the last piece:
+	    frame Tb - 1 = input_lengths[b] - 1).  A stretch without labels is no piece.
+	An utterance without a path (score -inf) has neither."""
+	begin, frames, score = (t.detach().cpu().tolist() for t in (result.star_begin, result.star_frames, result.score))
+	ylen = [int(n) for n in target_lengths.tolist()]
+	olen = [int(n) for n in result.input_lengths.tolist()]
+	out = []
+	for b, S in enumerate(ylen):
+		stars, pieces = [], []
+		if score[b] != float('-inf'):
+			stars = [(g, begin[b][g], begin[b][g] + frames[b][g] - 1) for g in range(S + 1) if frames[b][g] >= max(1, int(min_star_frames))]
+			first, at = 0, 0
+			for g, lo, hi in stars + [(S, None, None)]:
+				if g > first:
+					last = lo - 1 if lo is not None else olen[b] - 1
+					pieces.append((first, g - first, at, last))
+				if hi is not None:
+					first, at = g, hi + 1
+		out.append(types.SimpleNamespace(stars = stars, pieces = pieces))
+	return out
 
 
 MWER_UNITS = ('words', 'chars')

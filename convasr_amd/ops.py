@@ -1198,6 +1198,81 @@ def ctc_alignment_long(log_probs_btc, targets, input_lengths, target_lengths, bl
 	return out
 
 
+STAR_ALIGN_WORKSPACE_CAP = 16 << 30  # bytes of workspace one convasr_star_alignment call may take; a resource bound like ALIGN_LONG_WORKSPACE_CAP, not a measurement
+STAR_ALIGN_MAX_LABELS, STAR_ALIGN_MAX_FRAMES, STAR_ALIGN_MAX_BATCH = 131071, 1 << 20, 65535  # the envelope of convasr_star_alignment (the library checks it again)
+
+
+def star_alignment_tiles():
+	"""(states per block, default frames per chunk) of convasr_star_alignment's tiles (tests straddle them)."""
+	return _cached_query('convasr_star_alignment_states_per_block'), _cached_query('convasr_star_alignment_chunk_frames')
+
+
+def star_alignment_units(targets, target_lengths, star_mask, C):
+	"""The unit table convasr_star_alignment reads, built on the targets' device by cumsum and scatter: targets (B, S_max) int64,
+	target_lengths (B,), star_mask (B, S_max + 1) bool -> (units (B, 2 S_max + 1) int32, n_units (B,) int32).  Row b lists a star,
+	-(gap + 2), ahead of label g for every allowed gap g <= target_lengths[b], and every label's class (-1 where it lies outside [0, C))."""
+	B, S_max = targets.shape
+	g = torch.arange(S_max + 1, device = targets.device).unsqueeze(0)
+	ylen = target_lengths.clamp(0, S_max).unsqueeze(1)
+	m = (star_mask & (g <= ylen)).to(torch.int64)
+	at = g + m.cumsum(dim = 1) - m  # the unit index of gap g's star; its label follows at + m
+	N = 2 * S_max + 1
+	units = torch.zeros(B, N + 1, dtype = torch.int32, device = targets.device)  # (column N takes what has no unit)
+	units.scatter_(1, torch.where(m > 0, at, N), (-(g + 2)).to(torch.int32).expand(B, -1))
+	cls = torch.where((targets >= 0) & (targets < C), targets, -1).to(torch.int32)
+	units.scatter_(1, torch.where(g[:, :S_max] < ylen, (at + m)[:, :S_max], N), cls)
+	return units[:, :N], (ylen.squeeze(1) + m.sum(dim = 1)).to(torch.int32)
+
+
+def star_ctc_alignment(log_probs_btc, targets, input_lengths, target_lengths, blank, star_mask, star_penalty, star_enter, chunk_frames = 0, workspace_cap = STAR_ALIGN_WORKSPACE_CAP, parts = 3, _reuse = None):
+	"""The best path of a partial transcript through a whole recording (include/convasr_hip.h: convasr_star_alignment has the rule): the
+	star lattice of star_ctc_loss, max-plus Viterbi in fp32, up to 131,071 labels and 2^20 frames.  log_probs_btc contiguous (B, T, C) fp32,
+	star_mask (B, S_max + 1) bool, star_penalty / star_enter finite natural-log costs <= 0 (no defaults: nothing is tuned).  Returns a
+	namespace: alignment (B, S_max) int64 -- the last frame inside every label's state, ctc_alignment's convention --, star_begin and
+	star_frames (B, S_max + 1) int64 -- the first frame and the number of frames gap g's star absorbed, -1 and 0 where it is unused --,
+	score (B,) fp32, -inf where no path exists -- and input_lengths as the kernel read them (ctc.star_pieces wants them).  chunk_frames: 0 = the default tile length, 16 .. 4096 forces it (no output depends on
+	it).  The workspace is allocated for this call; a need above workspace_cap raises ConvasrHipError.  Eager only: the widest row's unit
+	count is read back to size the lattice.  parts / _reuse: measurements time the sweep (1) and the walk (2) apart over one workspace."""
+	if log_probs_btc.ndim != 3:
+		raise ValueError(f'star_ctc_alignment: log_probs (B, T, C) expected, got {tuple(log_probs_btc.shape)}')
+	B, T, C = log_probs_btc.shape
+	for name, v in (('star_penalty', star_penalty), ('star_enter', star_enter)):
+		if not isinstance(v, (int, float)) or isinstance(v, bool) or not v <= 0 or v == float('-inf'):
+			raise ValueError(f'star_ctc_alignment: {name} must be a finite natural-log cost <= 0, got {v!r}')
+	chunk_frames = int(chunk_frames)
+	if chunk_frames != 0 and not 16 <= chunk_frames <= 4096:
+		raise ValueError(f'star_ctc_alignment: chunk_frames {chunk_frames} is neither 0 nor in [16, 4096]')
+	if not 0 <= int(blank) < C:
+		raise ValueError(f'star_ctc_alignment: blank {blank} is outside [0, {C})')
+	targets = targets.view(B, -1) if targets.ndim == 1 else targets
+	S_max = targets.shape[1]
+	if targets.shape[0] != B or tuple(input_lengths.shape) != (B,) or tuple(target_lengths.shape) != (B,):
+		raise ValueError(f'star_ctc_alignment: targets (B, S_max) and lengths (B,) expected for a batch of {B}, got {tuple(targets.shape)}, {tuple(input_lengths.shape)}, {tuple(target_lengths.shape)}')
+	if tuple(star_mask.shape) != (B, S_max + 1) or star_mask.dtype != torch.bool:
+		raise ValueError(f'star_ctc_alignment: a bool star_mask of shape {(B, S_max + 1)} expected, got {star_mask.dtype} {tuple(star_mask.shape)}')
+	if B < 1 or T < 1 or B > STAR_ALIGN_MAX_BATCH or T > STAR_ALIGN_MAX_FRAMES or S_max > STAR_ALIGN_MAX_LABELS:
+		raise _lib.ConvasrHipError(f'star_ctc_alignment: B {B}, T {T}, S_max {S_max} outside the envelope (1 <= B <= {STAR_ALIGN_MAX_BATCH}, 1 <= T <= {STAR_ALIGN_MAX_FRAMES}, S_max <= {STAR_ALIGN_MAX_LABELS})')
+	require_cuda(log_probs_btc)
+	dev = log_probs_btc.device
+	assert log_probs_btc.is_contiguous() and log_probs_btc.dtype == torch.float32
+	targets, il, tl = _ctc_targets(targets, input_lengths, target_lengths, B, dev)
+	if _reuse is None:
+		units, n_units = star_alignment_units(targets, tl, star_mask.to(dev), C)
+		N_max = max(1, int(n_units.max()))  # (a read-back: the lattice and its workspace are as wide as the widest row, not as 2 S_max + 1)
+		units = units[:, :N_max].contiguous()
+		nbytes = _query('convasr_star_alignment_workspace_bytes', B, T, N_max)
+		ws = _call_workspace(nbytes, dev, workspace_cap, 'star_ctc_alignment', f'B {B}, T {T}, {N_max} units')
+	else:
+		units, n_units, N_max, nbytes, ws = _reuse
+	out = types.SimpleNamespace(alignment = torch.empty(B, S_max, dtype = torch.int64, device = dev), star_begin = torch.empty(B, S_max + 1, dtype = torch.int64, device = dev),
+	                            star_frames = torch.empty(B, S_max + 1, dtype = torch.int64, device = dev), score = torch.empty(B, dtype = torch.float32, device = dev), input_lengths = il)
+	call('convasr_star_alignment_parts', ptr(log_probs_btc), ptr(units), ptr(n_units), ptr(il), ptr(tl), float(star_penalty), float(star_enter), ptr(out.alignment), ptr(out.star_begin),
+	     ptr(out.star_frames), ptr(out.score), ptr(ws), nbytes, B, T, C, S_max, N_max, int(blank), chunk_frames, int(parts), stream_ptr())
+	if parts != 3:
+		out._reuse = (units, n_units, N_max, nbytes, ws)
+	return out
+
+
 # ------------------------------------------------------------------------------------------------ keyword search
 
 def ctc_keyword_search_limits():

@@ -27,7 +27,7 @@ import types
 import torch
 
 from . import ctc, models
-from .transcript_generators import BeamCTCGenerator, CharTokenizerLegacy, GreedyCTCGenerator
+from .transcript_generators import BeamCTCGenerator, CharTokenizerLegacy, GreedyCTCGenerator, Segment
 
 RU_ALPHABET = 'абвгдеёжзийклмнопрстуфхцчшщъыьэюя'  # configs/ru_text_config.json:10
 
@@ -116,6 +116,10 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 	xlen (B,) fractions, begin / end (B,) seconds, optional targets y (B, L, S) / ylen (B, L) for --align.
 	Returns a namespace: log_probs, logits, olen, ts (per-frame time stamps), hyp_segments (per utterance: list of word segments with
 	begin / end / hyp), hyp (joined strings) and, when args.align and targets are given, alignment (B, S), ref_segments.
+	args.align_star = ctc.StarCTC(...) (absent = off; with args.align and targets): the alignment is StarCTC.align's -- the transcript may miss
+	words --, alignment and ref_segments are formed from it as before, and star_segments (per utterance: Segment(begin, end, gap, frames) on
+	the batch's clock for the stars of at least args.align_star_min_frames frames, default 1) and ref_pieces (ctc.star_pieces' pieces:
+	Segment(begin, end, first_label, label_count), seconds) are added; both are None otherwise.
 	args.uncertainty (absent = off): every hyp and ref word segment also carries confidence, confidence_min, margin, entropy, uncertainty
 	(GreedyCTCGenerator / BeamCTCGenerator.generate's uncertainty; transcribe_file and transcribe_long pass args on, and transcribe_long's words keep the fields).
 	When args.align_words is set and targets are given, also ref (the decoded, postprocessed targets) and words: per utterance
@@ -127,11 +131,20 @@ def transcribe_batch(args, text_pipeline, model, generator, x, xlen, begin, end,
 	with_uncertainty = bool(getattr(args, 'uncertainty', False))  # every word segment also carries transcript_generators.UNCERTAINTY_KEYS
 	hyp_segments = [alternatives[0] for alternatives in generator.generate(tokenizer = tokenizer, log_probs = log_probs, begin = begin, end = end, output_lengths = olen, time_stamps = ts, segment_text_key = 'hyp', segment_extra_info = segment_extra_info, **(dict(uncertainty = True) if with_uncertainty else {}))]
 	hyp_segments = [map_text(text_pipeline.postprocess, hyp = hyp) for hyp in hyp_segments]
-	out = types.SimpleNamespace(log_probs = log_probs, logits = logits, olen = olen, ts = ts, hyp_segments = hyp_segments, hyp = [join(hyp = h) for h in hyp_segments], alignment = None, ref_segments = None, ref = None, words = None)
+	out = types.SimpleNamespace(log_probs = log_probs, logits = logits, olen = olen, ts = ts, hyp_segments = hyp_segments, hyp = [join(hyp = h) for h in hyp_segments], alignment = None, ref_segments = None, ref = None, words = None, star_segments = None, ref_pieces = None)
 	if getattr(args, 'align', False) and y is not None and y.numel() > 0:
 		y, ylen = y.to(device), ylen.to(device)
-		align = ctc.alignment_long_bct if y.shape[-1] > 8191 else ctc.alignment_bct  # (a whole recording against its transcript: past ctc.alignment's 8,191 labels)
-		out.alignment = align(log_probs, y[:, 0, :], olen, ylen[:, 0], blank = tokenizer.eps_id)
+		star = getattr(args, 'align_star', None)
+		if star is not None:  # a transcript with holes: the stars take the audio it does not cover, the labels keep their own frames
+			result = star.align(log_probs, y[:, 0, :], olen, ylen[:, 0], blank = tokenizer.eps_id)
+			out.alignment = result.alignment
+			out.star_segments, out.ref_pieces = [], []
+			for row, found in zip(ts.tolist(), ctc.star_pieces(result, y[:, 0, :], ylen[:, 0], getattr(args, 'align_star_min_frames', 1))):
+				out.star_segments.append([Segment(begin = row[lo], end = row[hi], gap = g, frames = hi - lo + 1) for g, lo, hi in found.stars])
+				out.ref_pieces.append([Segment(begin = row[lo], end = row[hi], first_label = first, label_count = count) for first, count, lo, hi in found.pieces])
+		else:
+			align = ctc.alignment_long_bct if y.shape[-1] > 8191 else ctc.alignment_bct  # (a whole recording against its transcript: past ctc.alignment's 8,191 labels)
+			out.alignment = align(log_probs, y[:, 0, :], olen, ylen[:, 0], blank = tokenizer.eps_id)
 		aligned_ts = ts.gather(1, out.alignment)
 		one_hot = torch.nn.functional.one_hot(y[:, 0, :], num_classes = log_probs.shape[1]).permute(0, 2, 1).to(torch.float32)
 		ref_generator = generator if isinstance(generator, GreedyCTCGenerator) else GreedyCTCGenerator()  # one-hot targets: the argmax collapse gives back y; a beam search over 0 / 1 "log-probs" would not

@@ -338,6 +338,45 @@ int64_t convasr_star_ctc_workspace_bytes(int B, int T, int C, int S_max);
 int convasr_star_ctc_loss(const float* log_probs, const int64_t* targets, const int64_t* olen, const int64_t* ylen, const uint8_t* star_mask,
                           float star_penalty, float star_enter, float* nll, float* grad, float* star_frames, void* workspace,
                           int B, int T, int C, int S_max, int blank, void* stream);
+/* The BEST PATH through the star lattice above, at the size of whole recordings (csrc/star_align.hip): which frame every label of a
+ * partial transcript occupies, and which frames the star of every gap absorbed -- the untranscribed audio.  The rule is this project's
+ * own and is pinned against no outside aligner; the two costs are untuned.
+ *   Units, states, the arc costs c[d][s] (d = 0 .. 4: 0, star_enter or "no arc" = -inf), start costs and end costs are exactly those
+ *   of convasr_star_ctc_loss.  A star emits star_penalty at every frame, every other state log_probs[b, t, class]; star_penalty and
+ *   star_enter are finite natural-log costs <= 0.  The sum becomes a maximum, in fp32, fl() = one rounding:
+ *     v[0][s] = fl(start[s] + em[0][s]);   v[t][s] = fl(em[t][s] + max_d fl(v[t-1][s-d] + c[d][s]));
+ *     the back-pointer of (t, s) is the SMALLEST d that attains the maximum;
+ *     the path ends in the SMALLEST s that attains max_s (v[Tb-1][s] + end[s]), Tb = input_lengths[b]; only frames < Tb are read.
+ *   This is true max-plus Viterbi.  It is NOT convasr_ctc_alignment's recursion (the reference's ctc.alignment), which carries a
+ *   log-sum-exp and takes the argmax of its addends; with an all-zero mask the two agree wherever the best path is unambiguous.  As only
+ *   max and one rounded addition per step occur, a float32 restatement with the same operations is equal bit for bit
+ *   (tests/_star_align_ref.py).  In exact arithmetic the score is the maximum over the subsets A of the allowed gaps of |A| star_enter +
+ *   the plain CTC Viterbi score of the labels with a star class at the gaps in A (tests/test_star_align_ref.py checks that).
+ * Inputs: log_probs (B, T, C) fp32 contiguous; units (B, N_max) int32: row b's first n_units[b] entries are its units in order -- a class
+ * in [0, C), -1 for a label outside it (it emits -inf), -(gap + 2) for the star of gap `gap` (what csrc/star_ctc.hip writes per state); the
+ * caller builds the table (ops.star_ctc_alignment: cumsum and scatter on the device), the kernels do not scan a mask.  target_lengths (B,):
+ * the labels among the units.  Outputs, all written by the walk kernel (no memset): alignment (B, S_max) int64, the last frame of the path
+ * inside every label's state (convasr_ctc_alignment's convention; 0 past target_lengths[b]); star_begin (B, S_max + 1) int64, the first
+ * frame the path spends in the star of gap g, -1 where that star is unused or absent; star_frames (B, S_max + 1) int64, how many frames
+ * (contiguous by construction); score (B,) fp32.  No path (Tb <= 0, Tb > T, too few frames, n_units outside [0, N_max]): score -inf,
+ * alignment 0, star_begin -1, star_frames 0.
+ * Scheme: tiles of convasr_star_alignment_states_per_block() states x chunk frames, one wave per tile, one plain launch per
+ * anti-diagonal, nothing waits inside a launch; back-pointers take 4 bits per (blank, unit) pair of states.  chunk_frames: 0 =
+ * convasr_star_alignment_chunk_frames(), or 16 .. 4096 (tests and tuning; no output depends on it).  workspace: at least
+ * convasr_star_alignment_workspace_bytes(B, T, N_max) bytes, 16-byte aligned, uninitialised.  Envelope, checked before any launch:
+ * S_max <= 131071, N_max <= 2 * 131071 + 1, T <= 2^20, B <= 65535; outside it CONVASR_EUNSUPPORTED (the workspace query returns -1).
+ * Eager only: the launch sequence depends on the shape and the workspace is per call.  parts: 1 = the sweep, 2 = the walk over a
+ * workspace that a sweep with the same arguments filled, 3 = both. */
+int convasr_star_alignment_states_per_block(void);
+int convasr_star_alignment_chunk_frames(void);
+int64_t convasr_star_alignment_workspace_bytes(int B, int T, int N_max);
+int convasr_star_alignment(const float* log_probs, const int32_t* units, const int32_t* n_units, const int64_t* input_lengths, const int64_t* target_lengths,
+                           float star_penalty, float star_enter, int64_t* alignment, int64_t* star_begin, int64_t* star_frames, float* score,
+                           void* workspace, int64_t workspace_bytes, int B, int T, int C, int S_max, int N_max, int blank, int chunk_frames, void* stream);
+int convasr_star_alignment_parts(const float* log_probs, const int32_t* units, const int32_t* n_units, const int64_t* input_lengths, const int64_t* target_lengths,
+                                 float star_penalty, float star_enter, int64_t* alignment, int64_t* star_begin, int64_t* star_frames, float* score,
+                                 void* workspace, int64_t workspace_bytes, int B, int T, int C, int S_max, int N_max, int blank, int chunk_frames, int parts,
+                                 void* stream);
 /* N-best minimum-word-error-rate (MWER) loss: the expected number of errors over an N-best list weighted by the hypotheses' CTC
  * likelihoods (csrc/mwer.hip).  The rule is this project's own (the sequence-level family of Prabhavalkar et al. 2018, Povey's sMBR),
  * pinned against no outside implementation; whether it lowers word error rate on speech is not shown anywhere in this project.
